@@ -2,7 +2,7 @@
 """
 bench.py — headline metric of the MCMC-over-ODE hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg1]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg1] [--dump-outputs DIR]
 
 One "step" = one launch of the fused MCMC kernel: `iters_per_step` Metropolis proposals for every
 chain of this GPU, each proposal costing one rate-and-state RK4 forward solve of `nsteps` output
@@ -346,6 +346,26 @@ def time_sampler(pkg, model, data, C, ips, steps, warmup, rank, barrier, d=1):
     return wall, kernel_ms, dict(eng.stats(), counters=eng.counters()), eng, traces, nout
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs budget, both files with their headers
+
+
+def dump_outputs(out_dir, traces):
+    """--dump-outputs: what the last timed launch returned to its caller, the sample trace [ips, C, d] and the sigma^2 trace
+    [ips, C] (float64), as out_dir/samples.npy and out_dir/sigma2.npy.  Above DUMP_BYTES in all, a fixed, seeded sample of
+    the chains (ascending chain index, the same columns in both files).  The inputs depend on the arguments only (seeded
+    observation noise, chain seed), so two builds run with the same arguments compare output for output."""
+    import torch
+
+    tq, ts = traces[0], traces[1]
+    ips, C, d = tq.shape
+    n = min(C, (DUMP_BYTES - 1024) // (8 * ips * (d + 1)))
+    idx = np.arange(C) if n == C else np.sort(np.random.default_rng(0).choice(C, n, replace=False))
+    sel = torch.as_tensor(idx, device=tq.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "samples.npy"), tq.index_select(1, sel).cpu().numpy())
+    np.save(os.path.join(out_dir, "sigma2.npy"), ts.index_select(1, sel).cpu().numpy())
+
+
 def roofline_views(workload, custom, C, ips, nout, stats, kernel_ms, d=1, mode="RK4", build_id=None):
     """The two roofline views of one launch of the sampler kernel.  PMC figures stored in
     profiles/pmc_traffic.json are attached only if they were collected on THIS build of the kernels (rsf_build_id(): the
@@ -411,7 +431,12 @@ def main():
                          "scaling run depends only on the torch.distributed exchange")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 path on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed launches, write what the last one returned (rank 0's sample and sigma^2 traces, "
+                         "float64; a seeded sample of the chains above 64 MB) as DIR/samples.npy and DIR/sigma2.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)  # does not return
@@ -508,6 +533,8 @@ def main():
             out["pool_allgather_ms"] = allgather_ms
         if abi_pool is not None:
             out["pool_allgather_c_abi"] = abi_pool
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, traces)
     if world == 1:
         eng.close()
         del traces

@@ -1348,50 +1348,41 @@ def test_wide_proposals_against_the_oracle_with_counters(gpu_engine, cpu_engine,
     print("wide-proposal counters:", cg)
 
 
-def test_early_rejection_changes_nothing_observable(pkg, oracle_mod):
-    """The same chains on the round-3 build of this library (build/base_96c1.so, when present: no early rejection, tier decided
+def test_early_rejection_changes_nothing_observable(pkg, oracle_mod, golden):
+    """The same chains on the round-3 build of this library (rsf_build_id() 96c179e837e4be05: no early rejection, tier decided
     by a wave's worst lane for the whole solve) and on this one: every accept flag and every sample bit-identical — the RNG is
     keyed by the chain id and a rejected proposal leaves nothing behind — and sigma^2 equal to rounding (it sees the accepted
     proposals' sums of squares, whose last bits depend on the tier that integrated them).  Headline-like all-TIGHT chains
-    and the wide-proposal mix."""
-    import ctypes
+    and the wide-proposal mix.  The round-3 run is stored in tests/golden/round3_chains.npz (tools/capture_round3_chains.py,
+    from the start state this library gave): its accept flags, the SHA-256 of its sample trace, and its sigma^2 trace for
+    a fixed sample of the chains."""
+    import hashlib
 
-    old_path = os.path.join(ROOT, "build", "base_96c1.so")
-    if not os.path.exists(old_path):
-        pytest.skip("the round-3 build (build/base_96c1.so) is not in this tree")
-    old = ctypes.CDLL(old_path)
-    for name, (restype, argtypes) in pkg._abi.PROTOTYPES.items():
-        if hasattr(old, name):
-            getattr(old, name).restype, getattr(old, name).argtypes = restype, argtypes
-    assert old.rsf_backend() == b"hip-gfx950" and old.rsf_build_id() == b"96c179e837e4be05"
-    for wide in (False, True):
+    g = golden.npz("round3_chains")
+    for case, wide in (("tight", False), ("wide", True)):
         C, iters, n = 8192, 30, 500
-        out = []
-        for lib in (None, old):
-            with (pkg.Engine(mem="host") if lib is None else pkg.Engine(lib=lib, mem="host")) as e:
-                data = _wide_proposal_problem(e, oracle_mod, C, dc_true=100.0 if wide else 1000.0)
-                q0 = np.random.default_rng(3).uniform(60.0, 1500.0, (C, 1)) if wide else np.full((C, 1), 1000.0)
-                e.mcmc_init(q0, data, [0.0], [1e4], seed=4242, prior_len=3)
-                if wide:
-                    st = e.get_state()
-                    e.set_state(V=np.full_like(st[3], 600.0 ** 2))
-                if out:
-                    e.set_state(*out[0][3])  # the same start state on both builds (the init kernels are not under test here)
-                start = e.get_state()
-                tq, ts, ta = e.mcmc_run(iters)
-                out.append((tq, ts, ta, start))
-        (tq_n, ts_n, ta_n, _), (tq_o, ts_o, ta_o, _) = out
+        with pkg.Engine(mem="host") as e:
+            data = _wide_proposal_problem(e, oracle_mod, C, dc_true=100.0 if wide else 1000.0)
+            q0 = np.random.default_rng(3).uniform(60.0, 1500.0, (C, 1)) if wide else np.full((C, 1), 1000.0)
+            e.mcmc_init(q0, data, [0.0], [1e4], seed=4242, prior_len=3)
+            # the round-3 run's start state (the init kernels are not under test here)
+            e.set_state(*(g[f"{case}_start_{k}"] for k in ("q", "ssq", "std2", "V")))
+            tq_n, ts_n, ta_n = (np.asarray(x) for x in e.mcmc_run(iters))
+        ta_o = np.unpackbits(g[f"{case}_accept_bits"], axis=1, count=C).astype(ta_n.dtype)
         # The round-3 build ACCEPTED a proposal whose sum of squares was NaN (fmin(NaN, 0) = 0 > log u: see accept_test in
         # rsf_kernels.h) — a stiff Dc < 0.35 proposal under fixed-step RK4 — and such a chain then accepts everything.  Those
         # chains are that build's bug, not a difference to explain: they show as a non-finite sigma^2 there, are few, are
         # finite here, and are left out of the comparison.
-        bugged = ~np.isfinite(ts_o).all(axis=0)
+        bugged = np.unpackbits(g[f"{case}_nonfinite_bits"], count=C).astype(bool)
         assert np.isfinite(ts_n).all() and np.isfinite(tq_n).all()
         assert bugged.sum() <= (0.01 * C if wide else 0), f"{bugged.sum()} chains of the old build went non-finite (wide={wide})"
         ok = ~bugged
         assert np.array_equal(ta_n[:, ok], ta_o[:, ok]), f"accept flags differ (wide={wide}): {(ta_n[:, ok] != ta_o[:, ok]).sum()} of {ta_n[:, ok].size}"
-        assert np.array_equal(tq_n[:, ok], tq_o[:, ok]), f"samples differ (wide={wide})"
-        np.testing.assert_allclose(ts_n[:, ok], ts_o[:, ok], rtol=1e-11)
+        digest = hashlib.sha256(np.ascontiguousarray(tq_n[:, ok], dtype=np.float64).tobytes()).digest()
+        assert digest == g[f"{case}_q_sha256"].tobytes(), f"samples differ (wide={wide})"
+        cols = np.sort(np.random.default_rng(0).choice(C, g[f"{case}_std2_sample"].shape[1], replace=False))
+        keep = ok[cols]
+        np.testing.assert_allclose(ts_n[:, cols[keep]], g[f"{case}_std2_sample"][:, keep], rtol=1e-11)
         print(f"old vs new build (wide={wide}): {ok.sum()} chains bit-identical in q and accept; {bugged.sum()} chains of the old build NaN-accepted")
 
 

@@ -300,6 +300,33 @@ def test_bench_self_launch_reports_child_failure(tmp_path):
     assert "child ranks exited with status" in r.stderr
 
 
+def test_bench_dump_outputs_writes_the_last_launch_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the traces the last timed launch returned, float64, whole when they fit the budget and
+    otherwise a fixed sample of whole chains (the same columns in both files, ascending), never more than the budget."""
+    import torch
+
+    import bench
+
+    rng = np.random.default_rng(5)
+    ips, C, d = 7, 300, 3
+    tq, ts = torch.as_tensor(rng.standard_normal((ips, C, d))), torch.as_tensor(rng.standard_normal((ips, C)))
+    bench.dump_outputs(str(tmp_path / "whole"), (tq, ts, None))
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "samples.npy"), tq.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "sigma2.npy"), ts.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1024 + 8 * ips * (d + 1) * 100 + 50)   # room for 100 chains
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), (tq, ts, None))
+    q, s = np.load(tmp_path / "a" / "samples.npy"), np.load(tmp_path / "a" / "sigma2.npy")
+    assert q.dtype == s.dtype == np.float64 and q.shape == (ips, 100, d) and s.shape == (ips, 100)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("samples.npy", "sigma2.npy")) <= bench.DUMP_BYTES
+    cols = [int(np.flatnonzero((ts.numpy() == s[:, [j]]).all(axis=0))[0]) for j in range(100)]
+    assert cols == sorted(set(cols))
+    np.testing.assert_array_equal(q, tq.numpy()[:, cols])
+    for f in ("samples.npy", "sigma2.npy"):   # the same sample every run
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 def _rsf_problem(pkg, meta, engine=None):
     problem = pkg.RSF(**meta["rsf_kwargs"])
     problem.model = pkg.RateStateModel(number_time_steps=meta["number_time_steps"])
