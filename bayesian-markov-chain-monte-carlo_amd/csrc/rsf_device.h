@@ -59,13 +59,19 @@ struct Lane {
   double vk;      // (V_ref/a) k'
   double beta;    // (b/theta dtheta/dt)/(k' d(ms)/dt) coefficient: (V_ref b/Dc)/k' = 10 b V_ref (independent of Dc)
   double kvk;     // (k1/k') vk = k1 V_ref/a : radiation damping, d0 -= kvk w g
-  double cv;      // cacc vk       : acceleration sample = cv * (g-weighted RK4 sum of the step)
-  double h6v;     // (h/6) vk      : velocity increment of a step = h6v * that sum
+  // With radiation damping the incremental tiers carry W = kvk w in place of w (tier_enter): w enters every use there
+  // linearly through a per-lane constant, so the constants absorb 1/kvk and the damping pass needs no product.  The
+  // steps' V-derivative sums are then in units of vk/kvk (the cold step's too: rhs_tail), and cv / h6v include the 1/kvk.
+  // Without damping W = w and these are the plain constants.
+  double vrw;     // V_ref/kvk     : d0 = V_l - vrw W
+  double hhdw, hdw;  // hhd/kvk, hd/kvk: the xr forms of rk4_tight
+  double cv;      // cacc vk / kvk : acceleration sample = cv * (g-weighted RK4 sum of the step)
+  double h6v;     // (h/6) vk / kvk: velocity increment of a step = h6v * that sum
   double boa;     // b/a
   double nhboa;   // -b/2a : (b/a) log1p(rho) = rho (b/a - (b/2a) rho) in the TIGHT tier, two fmas with dlt
   double tc;      // -mu_ref/a
   double hhd, hd, h6d;  // (h/2)/Dc, h/Dc, (h/6)/Dc : theta increments in x units
-  double inv_hhd, bh;   // 1/hhd and beta/hhd: the TIGHT tier carries hhd/x in place of 1/x (rk4_tight)
+  double bh;            // beta/hhd: the TIGHT tier carries hhd/x in place of 1/x (rk4_tight)
   double c_l1p, c_l1q;  // series coefficients of the active tier kept in VGPRs (a VOP3 takes one SGPR source and the first Horner
   double c_em1;         //   term has two non-inline constants), see set_tier: b/3a and -b/4a of log1p, expm1's leading coefficient
 };
@@ -73,6 +79,9 @@ struct Lane {
 template <int T>
 __device__ __forceinline__ void set_tier(Lane &L);
 
+// DAMP: radiation damping, k1 != 0 (with k1 = 0 the host launches the DAMP = false kernels: the damping pass is then an exact
+// identity, and W = kvk w would be 0)
+template <bool DAMP>
 __device__ __forceinline__ Lane make_lane(double dc, double a, double b, const Consts &K) {
   Lane L;
   // reciprocals by rsf_math.h (<= 1 ulp from the IEEE quotient at a fifth of its instruction count)
@@ -88,16 +97,20 @@ __device__ __forceinline__ Lane make_lane(double dc, double a, double b, const C
   L.vk = via * L.kprime;
   L.beta = (b * K.V_ref) * (1.0 / (1e-2 * 10));
   L.kvk = K.k1 * via;
-  L.cv = K.cacc * L.vk;
-  L.h6v = K.h6 * L.vk;
+  const double ikw = DAMP ? fm::rcp(L.kvk) : 1.0;
+  const double vkw = DAMP ? L.vk * ikw : L.vk;
+  L.cv = K.cacc * vkw;
+  L.h6v = K.h6 * vkw;
   L.boa = b * inv_a;
   L.tc = -K.mu_ref * inv_a;
   L.hhd = K.hh * L.vdc;
   L.hd = K.h * L.vdc;
   L.h6d = K.h6 * L.vdc;
+  L.vrw = DAMP ? K.V_ref * ikw : K.V_ref;
+  L.hhdw = DAMP ? L.hhd * ikw : L.hhd;
+  L.hdw = DAMP ? L.hd * ikw : L.hd;
   L.nhboa = -0.5 * L.boa;
-  L.inv_hhd = fm::rcp(L.hhd);
-  L.bh = L.beta * L.inv_hhd;
+  L.bh = L.beta * fm::rcp(L.hhd);
   set_tier<2>(L);
   return L;
 }
@@ -113,12 +126,14 @@ __device__ __forceinline__ Lane make_lane(double dc, double a, double b, const C
 // INSIDE the TIGHT tier's loops rx holds Rh = hhd/x instead and x is NOT carried (tier_enter / tier_leave): the step-end
 // update 1/x' = (1/x)(1 + q) is indifferent to a constant factor, the tier's step works on theta derivatives scaled by
 // Rh and never reads x itself (rk4_tight); where x is needed — a resync, a cold trip, leaving the tier — it is hhd / Rh.
+// With radiation damping w is carried there as W = kvk w as well (Lane::vrw).
 struct State {
   double ms, x, V;
   double w, rx;
 };
 
-// the RHS once w and 1/x are known.  d0 = d(ms)/dt, d1 = d(theta)/dt (so dx = d1/Dc), d2 = (dV/dt)/vk.
+// the RHS once w and 1/x are known.  d0 = d(ms)/dt, d1 = d(theta)/dt (so dx = d1/Dc), d2 = (dV/dt)/vk — with damping
+// (dV/dt) kvk/vk, the units of the incremental tiers' sums (Lane::vrw), from the product the damping pass forms anyway.
 template <bool DAMP>
 __device__ __forceinline__ void rhs_tail(double w, double rx, double x, double vl, const Lane &L,
                                          const Consts &K, double &d0, double &d1, double &d2) {
@@ -127,10 +142,13 @@ __device__ __forceinline__ void rhs_tail(double w, double rx, double x, double v
   const double bt = (L.beta * d1) * rx;              // b/theta * dtheta/dt, in units of k'
   double g = d0 - bt;                                // dV/dt = vk w g:  v/a (dmu/dt - b/theta dtheta/dt), RateStateModel.py:346
   if (DAMP) {                                        // one fixed-point pass, RateStateModel.py:349-353: d0 -= k1/k' * dV/dt,
-    d0 = __builtin_fma(-(L.kvk * w), g, d0);         //   then dV/dt again
+    const double kw = L.kvk * w;                     //   then dV/dt again
+    d0 = __builtin_fma(-kw, g, d0);
     g = d0 - bt;
+    d2 = kw * g;
+  } else {
+    d2 = w * g;
   }
-  d2 = w * g;
 }
 
 // (w, 1/x) by full evaluation
@@ -141,25 +159,36 @@ __device__ __forceinline__ void eval_full(double ms, double x, const Lane &L, co
 
 enum Tier : int { TIGHT = 0, NARROW = 1, WIDE = 2, FULL = 3 };  // FULL: a full evaluation at every stage (struct Wave)
 
-// the TIGHT and NARROW tiers' representation of 1/x (struct State)
-template <int T>
-__device__ __forceinline__ void tier_enter(State &s, const Lane &L) { s.rx *= L.hhd; }
+// a value formed where it is used: opaque to common-subexpression elimination and hoisting, so that it holds no register
+// through the loops (1/hhd and 1/kvk, needed only where a lane leaves the incremental tiers)
+__device__ __forceinline__ double local_value(double x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// the incremental tiers' representation of 1/x and w (struct State, Lane::vrw)
+template <bool DAMP, int T>
+__device__ __forceinline__ void tier_enter(State &s, const Lane &L) {
+  s.rx *= L.hhd;
+  if (DAMP) s.w *= L.kvk;
+}
 template <int T>
 __device__ __forceinline__ void tier_x(State &s, const Lane &L) { s.x = L.hhd * fm::rcp(s.rx); }  // x from Rh
-template <int T>
+template <bool DAMP, int T>
 __device__ __forceinline__ void tier_leave(State &s, const Lane &L) {
   tier_x<T>(s, L);
-  s.rx *= L.inv_hhd;
+  s.rx *= fm::rcp(local_value(L.hhd));
+  if (DAMP) s.w *= fm::rcp(local_value(L.kvk));
 }
-template <int T>
+template <bool DAMP, int T>
 __device__ __forceinline__ void eval_full_t(State &s, const Lane &L, const Consts &K) {  // from (ms, x)
   eval_full(s.ms, s.x, L, K, s.w, s.rx);
-  tier_enter<T>(s, L);
+  tier_enter<DAMP, T>(s, L);
 }
-template <int T>
+template <bool DAMP, int T>
 __device__ __forceinline__ void resync_t(State &s, const Lane &L, const Consts &K) {  // inside tier T's loop
   tier_x<T>(s, L);
-  eval_full_t<T>(s, L, K);
+  eval_full_t<DAMP, T>(s, L, K);
 }
 
 // (w', 1/x') at (ms + dms, x1 = x + dx) from (w, rx) at (ms, x).  With rho = dx/x (= dtheta/theta) and
@@ -263,7 +292,8 @@ __device__ __forceinline__ double rk4_cold(State &s, double vl0, double vlm, dou
 // SCALED by it, d1' = Rh (1 - w x): then rho of a half-step stage IS the previous stage's d1' (of the full-step stage
 // twice it, of the step's end a third of the weighted sum), and with Rh x_0 = h/2Dc =: hhd the scaled derivative needs
 // only constants and the previous d1':
-//     Rh x_s = hhd + c_s d1'_prev  (c_s = hhd, hhd, hd),      d1' = Rh - w (Rh x_s),      (beta/x_s) d1 = bh (1 + q) d1',  bh = beta/hhd,
+//     Rh x_s = hhd + c_s d1'_prev  (c_s = hhd, hhd, hd),      d1' = Rh - w (Rh x_s),      (beta/x_s) d1 = bh (1 + q) d1',  bh = beta/hhd
+//     (with damping W (Rh x_s / kvk), the constants hhdw = hhd/kvk, hdw = hd/kvk: rhs_tight),
 // so neither rho = R d1 (four products per step) nor Rf, R6 and beta/x_0 (three per step) are formed: 5 instructions
 // fewer than the unscaled form.  x itself is not carried at all: Rh IS the state (x = hhd / Rh where a full evaluation
 // needs it), updated once per step, so Rh x_0 = hhd holds by construction.
@@ -303,21 +333,20 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
 }
 
 // d0 = V_l - V_ref w,  d1' = Rh - w xr  (xr = Rh x at the stage),  g = d0 - brx d1'  (brx = bh (1 + q)) and the damping pass.
-// g is the bracket of dV/dt = vk w g, one fma on the two derivatives the stage forms anyway; working on g rather than on
-// vk g makes the damping pass ONE product shared by both corrections: d0 -= (kvk w) g and g -= (kvk w) g; the caller forms
-// w g (the stage's dV/dt in units of vk) inside its weighted sum.  (Rounds 1-2 wrote g linear in w so that all but one fma
+// g is the bracket of dV/dt = vk w g, one fma on the two derivatives the stage forms anyway.  With damping `w` is W = kvk w
+// (Lane::vrw; vr = V_ref/kvk, xr scaled by 1/kvk with it), so the pass d0 -= (kvk w) g, g -= (kvk w) g takes no product; the
+// caller forms W g (the stage's dV/dt in units of vk/kvk) inside its weighted sum.  (Rounds 1-2 wrote g linear in w so that all but one fma
 // was ready before w — the end of the previous stage's dependency chain — arrived: one instruction more per stage for one
 // dependent level less; measured in round 3, profiles/r03/ab_gform.log, the shorter stream wins at every shape.)
 template <bool DAMP>
-__device__ __forceinline__ void rhs_tight(double w, double xr, double Rh, double vl, double brx, const Lane &L, const Consts &K,
-                                          double &d0, double &d1, double &g) {
+__device__ __forceinline__ void rhs_tight(double w, double xr, double Rh, double vl, double brx, double vr, double &d0, double &d1,
+                                          double &g) {
   d1 = __builtin_fma(-w, xr, Rh);
-  d0 = __builtin_fma(-K.V_ref, w, vl);
+  d0 = __builtin_fma(-vr, w, vl);
   g = __builtin_fma(-brx, d1, d0);
   if (DAMP) {
-    const double kw = L.kvk * w;
-    d0 = __builtin_fma(-kw, g, d0);
-    g = __builtin_fma(-kw, g, g);
+    d0 = __builtin_fma(-w, g, d0);
+    g = __builtin_fma(-w, g, g);
   }
 }
 
@@ -325,16 +354,17 @@ template <bool DAMP, int T>
 __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, double vl1, const Lane &L, const Consts &K, Guard &g) {
   double a0, a1, a2, b0, b1, b2, c0, c1, c2, e0, e1, e2, w, q;
   const double Rh = s.rx;
-  rhs_tight<DAMP>(s.w, L.hhd, Rh, vl0, L.bh, L, K, a0, a1, a2);
-  double sv = s.w * a2;  // k1 + k4 of dV/dt (in units of vk), and k2 + k3 below: 5 instructions for the weighted sum
+  const double vr = L.vrw, xh = L.hhdw, xf = L.hdw;  // (V_ref, hhd, hd) / kvk with damping: s.w is W (Lane::vrw)
+  rhs_tight<DAMP>(s.w, xh, Rh, vl0, L.bh, vr, a0, a1, a2);
+  double sv = s.w * a2;  // k1 + k4 of dV/dt (in units of vk, vk/kvk with damping), and k2 + k3 below: 5 instructions for the weighted sum
   tight_incr<T, true>(a1, L.khh * a0, L, s.w, w, q, g);
-  rhs_tight<DAMP>(w, __builtin_fma(L.hhd, a1, L.hhd), Rh, vlm, __builtin_fma(L.bh, q, L.bh), L, K, b0, b1, b2);
+  rhs_tight<DAMP>(w, __builtin_fma(xh, a1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, b0, b1, b2);
   double sm = w * b2;
   tight_incr<T, true>(b1, L.khh * b0, L, s.w, w, q, g);
-  rhs_tight<DAMP>(w, __builtin_fma(L.hhd, b1, L.hhd), Rh, vlm, __builtin_fma(L.bh, q, L.bh), L, K, c0, c1, c2);
+  rhs_tight<DAMP>(w, __builtin_fma(xh, b1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, c0, c1, c2);
   sm = __builtin_fma(w, c2, sm);
   tight_incr<T, false>(c1 + c1, L.kh * c0, L, s.w, w, q, g);
-  rhs_tight<DAMP>(w, __builtin_fma(L.hd, c1, L.hhd), Rh, vl1, __builtin_fma(L.bh, q, L.bh), L, K, e0, e1, e2);
+  rhs_tight<DAMP>(w, __builtin_fma(xf, c1, xh), Rh, vl1, __builtin_fma(L.bh, q, L.bh), vr, e0, e1, e2);
   sv = __builtin_fma(w, e2, sv);
   const double t0 = a0 + 2.0 * b0 + 2.0 * c0 + e0;
   const double t1 = a1 + 2.0 * b1 + 2.0 * c1 + e1;
@@ -446,7 +476,7 @@ __device__ __forceinline__ void trip_cold(const double *v, const Lane &L, const 
 #pragma unroll
     for (int m = 0; m < NU; ++m) dv[m] = m == j ? r : dv[m];
   }
-  eval_full_t<T>(s, L, K);
+  eval_full_t<DAMP, T>(s, L, K);
 }
 
 // the same for a caller that holds the PLAIN state between trips — (ms, x) with rx = 1 / x, as the init kernels do: cold steps
@@ -568,7 +598,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
 #pragma unroll
     for (int j = 0; j < NU; ++j) obs[j] = (WANT_SSQ && S1) ? ld[r + j] : 0.0;
     if (r >= W.next_resync) {
-      resync_t<T>(s, L, K);
+      resync_t<DAMP, T>(s, L, K);
       W.next_resync = (r & ~(kResync - 1)) + kResync;
     }
     const State save = s;
@@ -654,23 +684,23 @@ __device__ __forceinline__ void integrate_tiers(const double *lds, const double 
   Emit em = {0, 0, s.V};
   int r = 0;
   W.next_resync = kResync;  // chunk-local; not at a chunk's first step (see kResync)
-  bool scaled = false;      // s.rx holds Rh = hhd / x (the incremental tiers' state) rather than 1 / x
+  bool scaled = false;      // s.rx holds Rh = hhd / x and s.w holds W (the incremental tiers' state) rather than 1 / x and w
   while (r < nsteps && W.alive != 0) {
     const int tier = wave_tier(W);
     if (tier == FULL) {
-      if (scaled) { tier_leave<WIDE>(s, L); scaled = false; }
+      if (scaled) { tier_leave<DAMP, WIDE>(s, L); scaled = false; }
       r = integrate_full<DAMP, WANT_SSQ, WANT_ACC, S1>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
       eval_full(s.ms, s.x, L, K, s.w, s.rx);  // (w, 1/x) at the point the incremental tiers — or the next chunk — continue from
       continue;
     }
-    if (!scaled) { tier_enter<TIGHT>(s, L); scaled = true; }
+    if (!scaled) { tier_enter<DAMP, TIGHT>(s, L); scaled = true; }
     // the chunk's odd last step (it always completes a sample): with the WIDE series whatever the tier — one instance
     if (nsteps - r == 1) r = integrate_multi<DAMP, WANT_SSQ, WANT_ACC, WIDE, S1, 1>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
     else if (tier == TIGHT) r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, TIGHT, S1, NUT>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
     else if (tier == NARROW) r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, NARROW, S1, kNarrowUnroll>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
     else r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, WIDE, S1, kWiderUnroll>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
   }
-  if (scaled) tier_leave<WIDE>(s, L);
+  if (scaled) tier_leave<DAMP, WIDE>(s, L);
 }
 
 // Integrate kn output intervals from the staged chunk.  Accumulates the sum of squares
@@ -692,7 +722,7 @@ __device__ __forceinline__ void integrate_chunk(const double *lds, const Consts 
 template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int NUT = kTightUnroll>
 __device__ __forceinline__ double solve(double *lds, const Consts &K, bool resident, bool active, double dc, double a,
                                         double b, double thr, double *acc_out, int64_t stride, Wave &W) {
-  const Lane L = make_lane(dc, a, b, K);
+  const Lane L = make_lane<DAMP>(dc, a, b, K);
   State s = initial_state(dc, L, K);
   wave_begin(W, active, L, K);
   double ssq = 0.0;

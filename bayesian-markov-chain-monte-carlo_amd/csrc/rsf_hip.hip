@@ -182,6 +182,13 @@ int mode_of(const rsf_ctx *c) {
   return (c->m.flags & RSF_FLAG_DOP853) ? DOP853 : ((c->m.flags & RSF_FLAG_FP32_SOLVE) ? RK4_F32 : RK4_F64);
 }
 
+// radiation damping in a kernel of integrator `mode`.  The float64 RK4 kernels carry W = kvk v / V_ref = k1 v / a in place of
+// v / V_ref with damping on (rsf_device.h, Lane::vrw), which needs k1 != 0; with k1 = 0 the damping pass is an exact identity
+// and they run without it.
+bool damped(const rsf_ctx *c, int mode) {
+  return (c->m.flags & RSF_FLAG_RADIATION_DAMPING) && (mode != RK4_F64 || c->m.k1 != 0.0);
+}
+
 // chains a lane of the sampler kernel carries: two in the float32 mode (mcmc_f32x2_kernel), else one
 int chains_per_lane(const rsf_ctx *c) { return mode_of(c) == RK4_F32 ? 2 : 1; }
 
@@ -257,7 +264,7 @@ int launch_mcmc_m(rsf_ctx *c, const Consts &K, const McmcArgs &A, bool replay) {
 
 template <int D>
 int launch_mcmc_d(rsf_ctx *c, const Consts &K, const McmcArgs &A, bool replay) {
-  return (c->m.flags & RSF_FLAG_RADIATION_DAMPING) ? launch_mcmc_m<D, true>(c, K, A, replay) : launch_mcmc_m<D, false>(c, K, A, replay);
+  return damped(c, mode_of(c)) ? launch_mcmc_m<D, true>(c, K, A, replay) : launch_mcmc_m<D, false>(c, K, A, replay);
 }
 
 // RSF_MEM_HOST callers with a long run: launches of `per` iterations write their trace rows into one of two device
@@ -328,7 +335,7 @@ const void *replay_kernel_m(const rsf_ctx *c) {
 }
 
 const void *replay_kernel(const rsf_ctx *c) {
-  const bool damp = c->m.flags & RSF_FLAG_RADIATION_DAMPING;
+  const bool damp = damped(c, mode_of(c));
   if (c->mc.n_params == 1) return damp ? replay_kernel_m<1, true>(c) : replay_kernel_m<1, false>(c);
   return damp ? replay_kernel_m<3, true>(c) : replay_kernel_m<3, false>(c);
 }
@@ -707,7 +714,7 @@ int rsf_forward_batch(rsf_ctx *c, int64_t n, const double *dc, const double *a, 
   if ((rc = stage_out(c, 5, acc_out, nb * (size_t)c->nout, &dacc))) return rc;
   const Consts K = make_consts(c, (const double *)ddata);
   const dim3 grid(grid_for(c, n)), block(c->block);
-  const bool damp = c->m.flags & RSF_FLAG_RADIATION_DAMPING;
+  const bool damp = damped(c, mode_of(c));
 #define RSF_LAUNCH_FWD_M(DAMP, SSQ, ACC, MODE)                                                              \
   hipLaunchKernelGGL((forward_kernel<DAMP, SSQ, ACC, MODE>), grid, block, c->lds_bytes, c->stream, K, n,      \
                      (const double *)ddc, (const double *)da, (const double *)db, (double *)dssq, (double *)dacc)
@@ -799,6 +806,7 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
   // the init kernels run one lane per TRAJECTORY: 1 + d adjacent lanes per chain (rsf_kernels.h, InitGroup)
   const dim3 igrid((unsigned)((C * (d + 1) + c->block - 1) / c->block));
   const bool damp = c->m.flags & RSF_FLAG_RADIATION_DAMPING;
+  const bool damp_rk4 = damped(c, RK4_F64);  // init_kernel: the float64 RK4 solve, in the float32 mode as well
   if (c->m.flags & RSF_FLAG_DOP853) {
     if (d == 1) {
       if (damp) hipLaunchKernelGGL((init_dp_kernel<1, true>), igrid, block, c->lds_bytes, c->stream, K, A);
@@ -808,10 +816,10 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
       else hipLaunchKernelGGL((init_dp_kernel<3, false>), igrid, block, c->lds_bytes, c->stream, K, A);
     }
   } else if (d == 1) {
-    if (damp) hipLaunchKernelGGL((init_kernel<1, true>), igrid, block, c->lds_bytes, c->stream, K, A);
+    if (damp_rk4) hipLaunchKernelGGL((init_kernel<1, true>), igrid, block, c->lds_bytes, c->stream, K, A);
     else hipLaunchKernelGGL((init_kernel<1, false>), igrid, block, c->lds_bytes, c->stream, K, A);
   } else {
-    if (damp) hipLaunchKernelGGL((init_kernel<3, true>), igrid, block, c->lds_bytes, c->stream, K, A);
+    if (damp_rk4) hipLaunchKernelGGL((init_kernel<3, true>), igrid, block, c->lds_bytes, c->stream, K, A);
     else hipLaunchKernelGGL((init_kernel<3, false>), igrid, block, c->lds_bytes, c->stream, K, A);
   }
   if (c->m.flags & RSF_FLAG_FP32_SOLVE) {

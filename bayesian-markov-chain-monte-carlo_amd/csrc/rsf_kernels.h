@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) init_kernel(Consts K, I
   const bool active = grp.chain < A.C;
   double pq[3], inv_den;
   grp.parameters(K, A, active, pq, inv_den);
-  const rsf::Lane L = rsf::make_lane(pq[0], pq[1], pq[2], K);
+  const rsf::Lane L = rsf::make_lane<DAMP>(pq[0], pq[1], pq[2], K);
   rsf::State st = rsf::initial_state(pq[0], L, K);
   double dsum = 0.0;
   if (active) { const double d0 = K.data[0]; grp.ssq = d0 * d0; }
@@ -250,9 +250,9 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) init_kernel(Consts K, I
       rsf::set_tier<T>(Lt);
       const rsf::State save = st;
       double dv[NUT];
-      rsf::tier_enter<T>(st, Lt);
+      rsf::tier_enter<DAMP, T>(st, Lt);
       const bool bad = rsf::trip_fast<DAMP, T, NUT>(v, Lt, K, st, dv);
-      rsf::tier_leave<T>(st, Lt);
+      rsf::tier_leave<DAMP, T>(st, Lt);
       const bool any_bad = rsf::ballot(bad) != 0;
       if (__builtin_expect(any_bad, 0)) {
         if (bad) {  // back to the trip's start (the plain state: saved before tier_enter) and through it with full evaluations
