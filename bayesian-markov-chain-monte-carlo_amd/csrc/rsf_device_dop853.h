@@ -8,7 +8,7 @@
 // length delta_t, so lanes stay convergent.  That steady state is the fast path of call(): the RHS is evaluated in full
 // at the step's end point and incrementally from its start point at the eleven inner stages (friction_incr); every other
 // step goes through the general loop with full evaluations.  This mode is for fidelity to the reference's numbers
-// (agreement ~1e-12 with its trajectories), the fixed-step RK4 path is the fast one.
+// (the same distance from the exact map as a float64 restatement: DESIGN.md Tier 0), the fixed-step RK4 path is the fast one.
 // Tableau: include/rsf_dop853_tableau.h (generated from SciPy's table).
 //
 // What is NOT carried per stage: the third component.  V never feeds back into the RHS (RateStateModel.py:336-353), so
