@@ -34,12 +34,22 @@ else:  # flat layout: this directory on sys.path, the reference's own import sty
 class PosteriorPool:
     """Result of sample_batched: kept draws of every chain, iteration-major."""
 
-    def __init__(self, samples, std2, accept_rate, stats, nburn):
+    def __init__(self, samples, std2, accept_rate, stats, nburn, superchain_size=None):
         self.samples = samples          # (n_keep, C, d)
         self.std2 = std2                # (n_keep, C)
         self.accept_rate = accept_rate  # accepted / proposals over all chains
         self.stats = stats
         self.nburn = nburn
+        self.superchain_size = superchain_size  # chains [k*S, (k+1)*S) started from one point (sample_batched)
+
+    def diagnostics(self, superchain_size=None, engine=None, **kw):
+        """Split R-hat, nested R-hat and multi-chain ESS of the kept draws, computed on the GPU (Engine.diagnostics) → one dict
+        per parameter.  Nested R-hat uses superchains of `superchain_size` chains, by default the sampler's own."""
+        S = self.superchain_size if superchain_size is None else superchain_size
+        if engine is not None:
+            return engine.diagnostics(self.samples, superchain_size=S, **kw)
+        with Engine(mem="host") as eng:
+            return eng.diagnostics(self.samples, superchain_size=S, **kw)
 
     def pooled(self):
         """(d, n_keep*C): every kept draw of every chain, the reference's (d, n) layout."""
@@ -331,15 +341,20 @@ class MCMC:
         return qparams[:, self.nburn:]
 
     def sample_batched(self, n_chains, seed=0, q0=None, jitter=None, n_iters=None, iters_per_launch=None,
-                       adapt_mode=None, mem="device", device=-1, chain_offset=0, keep="post_burn", thin=1):
+                       adapt_mode=None, mem="device", device=-1, chain_offset=0, keep="post_burn", thin=1, superchain_size=None):
         """Throughput path (additive): n_chains independent chains, Philox variates on device.
 
         q0: (C,) / (C, d) start points; default qstart for every chain, optionally jittered
         uniformly in `jitter=(lo, hi)` with a NumPy generator seeded by `seed` and keyed by
         global chain id.  Returns a PosteriorPool of the post-burn-in draws; `thin=k` keeps every k-th kept draw
-        (the pool of a long multi-GPU run need not hold, or all-gather, every iteration: SURVEY §8e)."""
+        (the pool of a long multi-GPU run need not hold, or all-gather, every iteration: SURVEY §8e).
+        superchain_size=S: the jitter generator is keyed by global chain id // S instead, so that each block of S consecutive
+        chains shares a start point — the superchains of nested R-hat (PosteriorPool.diagnostics)."""
         if int(thin) < 1:
             raise ValueError("thin must be >= 1")
+        S = None if superchain_size is None else int(superchain_size)
+        if S is not None and (S < 1 or n_chains % S or chain_offset % S):
+            raise ValueError(f"superchain_size={superchain_size} must divide n_chains={n_chains} and chain_offset={chain_offset}")
         thin = int(thin)
         n_iters = self.nsamples if n_iters is None else n_iters
         nburn = int(n_iters / 2) if keep == "post_burn" else 0
@@ -350,7 +365,7 @@ class MCMC:
             if jitter is not None:  # (lo, hi) for Dc, or one (lo, hi) per parameter: start points spread over that box
                 jit = np.broadcast_to(np.asarray(jitter, dtype=np.float64).reshape(-1, 2), (d, 2)) if np.ndim(jitter) > 1 else None
                 for r, g in enumerate(gids):
-                    rng = np.random.default_rng([seed, int(g)])
+                    rng = np.random.default_rng([seed, int(g) if S is None else int(g) // S])
                     if jit is None:
                         q0[r, 0] = rng.uniform(*jitter)
                     else:
@@ -382,7 +397,7 @@ class MCMC:
         finally:
             eng.close()
         rate = stats["accepted"] / max(1, n_iters * n_chains)
-        return PosteriorPool(samples, std2, rate, stats, nburn)
+        return PosteriorPool(samples, std2, rate, stats, nburn, superchain_size=S)
 
     # ---- visualisation (off the hot path; degrades gracefully) --------------------------
     def _animate(self, qparams):

@@ -123,6 +123,17 @@ PROTOTYPES = {
 }
 
 
+# include/rsf_diag.h: exported by librsf_hip.so only (the CPU checker implements rsf_abi.h alone), bound by load()
+DIAG_PROTOTYPES = {
+    "rsf_diag_partials": (c_int, [c_void_p, c_int64, c_int64, c_int32, _P, c_int64, POINTER(c_double), c_int64, c_int64,
+                                  POINTER(c_double)]),
+    "rsf_diag_finish": (c_int, [c_int64, c_int32, c_int64, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_double)]),
+}
+DIAG_HEAD = 9  # RSF_DIAG_HEAD: fields of the partials before the lag sums
+# rsf_diag_finish out[p][RSF_DIAG_OUT], in index order
+DIAG_OUT = ("mean", "var_plus", "W", "B_over_N", "split_rhat", "nested_rhat", "K", "ess", "tau", "mcse_mean", "lags_complete")
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -166,6 +177,9 @@ def load():
                                "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
+        for name, (restype, argtypes) in DIAG_PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if lib.rsf_version() != ABI_VERSION:
             raise RsfError(-1, f"ABI version mismatch: library {lib.rsf_version()}, binding {ABI_VERSION}")
         _lib = lib

@@ -18,7 +18,9 @@
 #include <vector>
 
 #include "../../include/rsf_abi.h"
+#include "../../include/rsf_diag.h"
 #include "rsf_kernels.h"
+#include "rsf_diag.h"
 
 using rsf::Consts;
 using namespace rsfk;
@@ -105,6 +107,7 @@ struct rsf_ctx {
   int32_t world = 0, rank = 0;  // world 0: rsf_comm_init not called
   ncclComm_t comm = nullptr;
   DevBuf pool;  // workspace of the posterior post-processing kernels
+  DevBuf diag;  // workspace of the convergence diagnostics (rsf_diag_partials)
 };
 
 namespace {
@@ -598,6 +601,7 @@ int rsf_destroy(rsf_ctx *c) {
     release(c->vl);
     for (auto &s : c->stage) release(s);
     release(c->pool);
+    release(c->diag);
     release_replay_graph(c);
     if (c->comm) { const Rccl *R = rccl(); if (R) (void)R->comm_destroy(c->comm); }
     for (auto &e : c->ev_done) if (e) (void)hipEventDestroy(e);
@@ -1083,6 +1087,134 @@ int rsf_pool_histogram(rsf_ctx *c, int64_t n, const double *x, int64_t stride, i
                      (const unsigned long long *)ws.p, (double *)dout);
   if ((rc = copy_back(c, 2, counts, (size_t)nb * sizeof(double)))) return rc;
   return finish(c);
+}
+
+// ---- convergence diagnostics (include/rsf_diag.h) ----------------------------------------------
+int rsf_diag_partials(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double *trace, int64_t S, const double *center,
+                      int64_t lag_begin, int64_t lag_end, double *partials) {
+  if (!c || !trace || !center || !partials) return fail(RSF_ERR_INVALID, "rsf_diag_partials: NULL argument");
+  if (n < 4 || C < 1 || d < 1 || d > RSF_MAX_PARAMS)
+    return fail(RSF_ERR_INVALID, "rsf_diag_partials: need n_iters >= 4, n_chains >= 1, 1 <= n_params <= %d", RSF_MAX_PARAMS);
+  if (S < 0 || (S > 0 && C % S)) return fail(RSF_ERR_INVALID, "rsf_diag_partials: chains_per_superchain %lld does not divide %lld chains",
+                                             (long long)S, (long long)C);
+  const int64_t N = n / 2;
+  if (lag_begin < 0 || lag_end <= lag_begin || lag_end > N)
+    return fail(RSF_ERR_INVALID, "rsf_diag_partials: lags [%lld, %lld) are not a non-empty range within [0, %lld)", (long long)lag_begin,
+                (long long)lag_end, (long long)N);
+  if (n > INT64_MAX / 8 / C / d) return fail(RSF_ERR_INVALID, "rsf_diag_partials: trace too large");
+  const int64_t L = lag_end - lag_begin, nbc = (C + kDiagBlock - 1) / kDiagBlock, ntiles = (L + kLagTile - 1) / kLagTile;
+  if (nbc * d * ntiles > INT32_MAX) return fail(RSF_ERR_INVALID, "rsf_diag_partials: too many lags for one call; ask for fewer");
+  rsfk::DiagCenter cen{{0.0, 0.0, 0.0}};
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(center[p])) return fail(RSF_ERR_INVALID, "rsf_diag_partials: center[%d] is not finite", p);
+    cen.v[p] = center[p];
+  }
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_partials: cannot select device %d", c->device);
+  const void *dx;
+  int rc;
+  if ((rc = stage_in(c, 0, trace, (size_t)(n * C * d) * sizeof(double), &dx))) return rc;
+  const int64_t K = S ? C / S : 0, nbs = S ? std::min<int64_t>(kDiagSuperBlocks, (K + kDiagBlock / 64 - 1) / (kDiagBlock / 64)) : 0;
+  // workspace, doubles: mh[2][d][C] | fm[d][C] | fv[d][C] | chain partials[nbc][d][3] | superchain partials[nbs][d][4] |
+  // lag partials[nbc][d][L] | sums[d*3 + d*4 + d*L]
+  const int64_t nf1 = d * kDiagChainFields, nf2 = d * kDiagSuperFields, nf3 = d * L;
+  const int64_t o_fm = 2 * d * C, o_fv = o_fm + d * C, o_p1 = o_fv + d * C, o_p2 = o_p1 + nbc * nf1, o_p3 = o_p2 + nbs * nf2,
+                o_sum = o_p3 + nbc * nf3, total = o_sum + nf1 + nf2 + nf3;
+  if ((rc = ensure(c->diag, (size_t)total * sizeof(double)))) return rc;
+  double *w = (double *)c->diag.p;
+  const rsfk::DiagShape sh{n, C, d, N, n - N};
+  const double *x = (const double *)dx;
+  switch (d) {
+    case 1: hipLaunchKernelGGL(diag_chain_kernel<1>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
+    case 2: hipLaunchKernelGGL(diag_chain_kernel<2>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
+    default: hipLaunchKernelGGL(diag_chain_kernel<3>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
+  }
+  if (S) hipLaunchKernelGGL(diag_super_kernel, dim3((unsigned)nbs), dim3(kDiagBlock), 0, c->stream, C, (int)d, S, cen, (const double *)(w + o_fm),
+                            (const double *)(w + o_fv), w + o_p2);
+  hipLaunchKernelGGL(diag_lag_kernel, dim3((unsigned)(nbc * d * ntiles)), dim3(kDiagBlock), 0, c->stream, sh, x, (const double *)w, lag_begin,
+                     lag_end, w + o_p3);
+  const int64_t sum_blocks = (std::max<int64_t>(nf1, std::max(nf2, nf3)) + kDiagBlock - 1) / kDiagBlock;
+  hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbc, nf1, (const double *)(w + o_p1), w + o_sum);
+  if (S) hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbs, nf2, (const double *)(w + o_p2),
+                            w + o_sum + nf1);
+  hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbc, nf3, (const double *)(w + o_p3),
+                     w + o_sum + nf1 + nf2);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> h((size_t)(nf1 + nf2 + nf3), 0.0);
+  HIP_TRY(hipMemcpyAsync(h.data(), w + o_sum, sizeof(double) * (size_t)(nf1 + (S ? nf2 : 0)), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h.data() + nf1 + nf2, w + o_sum + nf1 + nf2, sizeof(double) * (size_t)nf3, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int p = 0; p < d; ++p) {
+    double *o = partials + (int64_t)p * (RSF_DIAG_HEAD + L);
+    const double *h1 = h.data() + p * kDiagChainFields, *h2 = h.data() + nf1 + p * kDiagSuperFields, *h3 = h.data() + nf1 + nf2 + p * L;
+    o[0] = 2.0 * (double)C;
+    o[1] = h1[0]; o[2] = h1[1]; o[3] = h1[2];
+    o[4] = (double)K;
+    for (int f = 0; f < kDiagSuperFields; ++f) o[5 + f] = S ? h2[f] : 0.0;
+    for (int64_t j = 0; j < L; ++j) o[RSF_DIAG_HEAD + j] = h3[j];
+  }
+  return RSF_OK;
+}
+
+int rsf_diag_finish(int64_t n, int32_t d, int64_t S, const double *center, const double *partials, int64_t n_lags, double *out) {
+  if (!center || !partials || !out) return fail(RSF_ERR_INVALID, "rsf_diag_finish: NULL argument");
+  if (n < 4 || d < 1 || d > RSF_MAX_PARAMS || S < 0)
+    return fail(RSF_ERR_INVALID, "rsf_diag_finish: need n_iters >= 4, 1 <= n_params <= %d, chains_per_superchain >= 0", RSF_MAX_PARAMS);
+  const int64_t N = n / 2;
+  if (n_lags < 2 || n_lags > N) return fail(RSF_ERR_INVALID, "rsf_diag_finish: n_lags %lld outside [2, %lld]", (long long)n_lags, (long long)N);
+  const double Nd = (double)N;
+  std::vector<double> r((size_t)n_lags);
+  for (int p = 0; p < d; ++p) {
+    const double *q = partials + (int64_t)p * (RSF_DIAG_HEAD + n_lags);
+    double *o = out + (int64_t)p * RSF_DIAG_OUT;
+    for (int f = 0; f < RSF_DIAG_OUT; ++f) o[f] = NAN;
+    o[RSF_DIAG_K] = q[4];
+    o[RSF_DIAG_LAGS_COMPLETE] = 1.0;
+    bool finite = std::isfinite(center[p]);
+    for (int64_t f = 0; f < RSF_DIAG_HEAD + n_lags; ++f) finite = finite && std::isfinite(q[f]);
+    if (!finite) continue;  // a non-finite draw: every statistic of this parameter is NaN
+    const double Mp = q[0], ybar = q[1] / Mp, W = q[3] / Mp;
+    const double BN = (q[2] - q[1] * ybar) / (Mp - 1.0);
+    const double var_plus = (Nd - 1.0) / Nd * W + BN;
+    o[RSF_DIAG_MEAN] = center[p] + ybar;
+    o[RSF_DIAG_VAR_PLUS] = var_plus;
+    o[RSF_DIAG_W] = W;
+    o[RSF_DIAG_B_OVER_N] = BN;
+    const double K = q[4];
+    if (S > 0 && K > 1.0) {
+      const double B_nu = (q[6] - q[5] * q[5] / K) / (K - 1.0), W_nu = (q[7] + q[8]) / K;
+      if (W_nu > 0.0) o[RSF_DIAG_NESTED_RHAT] = std::sqrt(1.0 + B_nu / W_nu);
+    }
+    if (!(W > 0.0)) continue;  // every split chain constant
+    o[RSF_DIAG_SPLIT_RHAT] = std::sqrt(var_plus / W);
+    // ArviZ's _ess on the split chains, step by step (tests/diagnostics_reference.py), with the sequence cut at n_lags
+    auto rho = [&](int64_t t) { return 1.0 - (W - q[RSF_DIAG_HEAD + t] / Mp) / var_plus; };
+    std::fill(r.begin(), r.end(), 0.0);
+    double ev = 1.0, od = rho(1);
+    r[0] = ev; r[1] = od;
+    int64_t t = 1;
+    const int64_t lim = std::min(N - 3, n_lags - 2);  // the pair (t+1, t+2) needs lag t+2 < n_lags
+    while (t < lim && ev + od > 0.0) {  // Geyer's initial positive sequence
+      ev = rho(t + 1);
+      od = rho(t + 2);
+      if (ev + od >= 0.0) { r[t + 1] = ev; r[t + 2] = od; }
+      t += 2;
+    }
+    o[RSF_DIAG_LAGS_COMPLETE] = (ev + od > 0.0 && t < N - 3) ? 0.0 : 1.0;
+    const int64_t max_t = t - 2;
+    if (ev > 0.0) r[max_t + 1] = ev;
+    for (int64_t u = 1; u <= max_t - 2; u += 2)  // Geyer's initial monotone sequence
+      if (r[u + 1] + r[u + 2] > r[u - 1] + r[u]) { r[u + 1] = 0.5 * (r[u - 1] + r[u]); r[u + 2] = r[u + 1]; }
+    double tau = 0.0;
+    for (int64_t u = 0; u <= max_t; ++u) tau += r[u];
+    tau = -1.0 + 2.0 * tau + r[max_t + 1];
+    const double MN = Mp * Nd;
+    tau = std::max(tau, 1.0 / std::log10(MN));
+    o[RSF_DIAG_TAU] = tau;
+    o[RSF_DIAG_ESS] = MN / tau;
+    o[RSF_DIAG_MCSE_MEAN] = std::sqrt(var_plus / o[RSF_DIAG_ESS]);
+  }
+  return RSF_OK;
 }
 
 int rsf_comm_unique_id(uint8_t id[RSF_COMM_ID_BYTES]) {

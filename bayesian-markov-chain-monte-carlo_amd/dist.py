@@ -107,6 +107,20 @@ def allreduce_histogram(counts, group=None, device=None):
     return t
 
 
+def allreduce_diag_partials(partials, group=None, device=None):
+    """Per-rank `Engine.diag_partials` (every rank's contiguous block of global chain ids, the same centre and lags, no
+    superchain across two ranks) → the partials of all ranks' chains: one all-reduce SUM of d * (DIAG_HEAD + L) doubles.
+    Feed the result to `Engine.diag_finish`."""
+    import torch
+    import torch.distributed as dist
+
+    t = partials.clone() if isinstance(partials, torch.Tensor) else torch.as_tensor(np.array(partials, dtype=np.float64))
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
+
+
 def pool_to_chain_major(pool):
     """(G, n_keep, C_local, d) → (n_keep, G*C_local, d): global chain id = g*C_local + c."""
     G, n, C, d = pool.shape

@@ -320,6 +320,77 @@ class Engine:
                                                          self._ptr(counts)))
         return counts
 
+    # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
+    def _diag_trace(self, trace):
+        x = self._in(trace)
+        if x.ndim == 2:
+            x = x.reshape(int(x.shape[0]), int(x.shape[1]), 1)
+        if x.ndim != 3:
+            raise ValueError("a trace is (n_iters, n_chains) or (n_iters, n_chains, n_params)")
+        return x, int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+
+    @staticmethod
+    def _diag_center(x, d, center):
+        if center is None:  # the trace's first draw of chain 0
+            first = x[0, 0]
+            return np.ascontiguousarray(np.asarray(first.cpu() if hasattr(first, "cpu") else first, dtype=np.float64).reshape(d))
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), (d,)))
+
+    def diag_partials(self, trace, superchain_size=None, center=None, lag_begin=0, lag_end=None):
+        """rsf_diag_partials: the additive partials of the trace (n, C[, d]) about `center` (default: the first draw of chain 0)
+        for the lags [lag_begin, lag_end) (default: every lag, N = n // 2) → (d, DIAG_HEAD + L) float64 on the host.  Partials of
+        disjoint sets of chains taken about the same centre add (dist.allreduce_diag_partials); a superchain must not straddle
+        two sets."""
+        x, n, C, d = self._diag_trace(trace)
+        c = self._diag_center(x, d, center)
+        lag_end = n // 2 if lag_end is None else int(lag_end)
+        out = np.empty((d, _abi.DIAG_HEAD + max(lag_end - int(lag_begin), 0)))
+        dbl = ctypes.POINTER(ctypes.c_double)
+        _abi.check(self.lib, self.lib.rsf_diag_partials(self._ctx, n, C, d, self._ptr(x), int(superchain_size or 0), c.ctypes.data_as(dbl),
+                                                        int(lag_begin), lag_end, out.ctypes.data_as(dbl)))
+        return out
+
+    def diag_finish(self, n_iters, partials, center, superchain_size=None, n_lags=None):
+        """rsf_diag_finish (host only): the statistics of summed partials whose lags are [0, n_lags) → one dict per parameter
+        (split_rhat, nested_rhat, ess, tau, mcse_mean, mean, var_plus, W, B_over_N, K, lags_complete)."""
+        part = np.ascontiguousarray(np.asarray(partials.cpu() if hasattr(partials, "cpu") else partials, dtype=np.float64))
+        part = part.reshape(-1, part.shape[-1])
+        d = int(part.shape[0])
+        n_lags = int(part.shape[1]) - _abi.DIAG_HEAD if n_lags is None else int(n_lags)
+        if part.shape[1] != _abi.DIAG_HEAD + n_lags:
+            raise ValueError(f"partials have {part.shape[1] - _abi.DIAG_HEAD} lags, not n_lags = {n_lags}")
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), (d,)))
+        out = np.empty((d, len(_abi.DIAG_OUT)))
+        dbl = ctypes.POINTER(ctypes.c_double)
+        _abi.check(self.lib, self.lib.rsf_diag_finish(int(n_iters), d, int(superchain_size or 0), c.ctypes.data_as(dbl),
+                                                      part.ctypes.data_as(dbl), n_lags, out.ctypes.data_as(dbl)))
+        res = []
+        for row in out:
+            r = dict(zip(_abi.DIAG_OUT, (float(v) for v in row)))
+            r["K"], r["lags_complete"], r["n_lags"] = int(r["K"]), bool(r["lags_complete"]), n_lags
+            res.append(r)
+        return res
+
+    def diagnostics(self, trace, superchain_size=None, center=None, n_lags=None, lag_block=64):
+        """Split R-hat, nested R-hat (superchains of `superchain_size` consecutive chains) and the multi-chain ESS of a trace
+        (n, C[, d]) → one dict per parameter (see diag_finish; `n_lags` = the lags used).  Without `n_lags` the lags are computed
+        `lag_block` at a time until Geyer's truncation is reached for every parameter; with it, exactly [0, n_lags) and
+        `lags_complete` says whether that was enough."""
+        x, n, _, d = self._diag_trace(trace)
+        c = self._diag_center(x, d, center)
+        if n_lags is not None:
+            return self.diag_finish(n, self.diag_partials(x, superchain_size, c, 0, n_lags), c, superchain_size)
+        if int(lag_block) < 2:
+            raise ValueError("lag_block must be >= 2")
+        N, end, part = n // 2, 0, None
+        while True:
+            new = self.diag_partials(x, superchain_size, c, end, min(N, end + int(lag_block)))
+            part = new if part is None else np.concatenate([part, new[:, _abi.DIAG_HEAD:]], axis=1)
+            end = part.shape[1] - _abi.DIAG_HEAD
+            res = self.diag_finish(n, part, c, superchain_size)
+            if end >= N or all(r["lags_complete"] for r in res):
+                return res
+
     # -- multi-GPU posterior pool through the C ABI (RCCL bound inside the library; SURVEY §8e) -----
     def comm_unique_id(self):
         """Rank 0: the 128-byte id every rank passes to comm_init (send it over any channel)."""
