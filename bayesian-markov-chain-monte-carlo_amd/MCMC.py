@@ -51,6 +51,14 @@ class PosteriorPool:
         with Engine(mem="host") as eng:
             return eng.diagnostics(self.samples, superchain_size=S, **kw)
 
+    def rank_diagnostics(self, engine=None, **kw):
+        """Rank-normalised R-hat, bulk and tail ESS, median, quantiles and HDI of the kept draws, computed on the GPU
+        (Engine.rank_diagnostics) → one dict per parameter.  Ranks are global: a multi-rank pool is gathered first."""
+        if engine is not None:
+            return engine.rank_diagnostics(self.samples, **kw)
+        with Engine(mem="host") as eng:
+            return eng.rank_diagnostics(self.samples, **kw)
+
     def pooled(self):
         """(d, n_keep*C): every kept draw of every chain, the reference's (d, n) layout."""
         n, C, d = self.samples.shape

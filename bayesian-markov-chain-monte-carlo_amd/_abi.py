@@ -128,10 +128,20 @@ DIAG_PROTOTYPES = {
     "rsf_diag_partials": (c_int, [c_void_p, c_int64, c_int64, c_int32, _P, c_int64, POINTER(c_double), c_int64, c_int64,
                                   POINTER(c_double)]),
     "rsf_diag_finish": (c_int, [c_int64, c_int32, c_int64, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_double)]),
+    "rsf_diag_rank_prepare": (c_int, [c_void_p, c_int64, c_int64, c_int32, _P, c_int32, POINTER(c_double), c_double,
+                                      POINTER(c_double), _P]),
+    "rsf_diag_rank_partials": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_double)]),
+    "rsf_diag_rank_finish": (c_int, [c_int64, c_int32, POINTER(c_double), c_int32, POINTER(c_double), c_int64, POINTER(c_double)]),
+    "rsf_diag_rank_release": (c_int, [c_void_p]),
 }
 DIAG_HEAD = 9  # RSF_DIAG_HEAD: fields of the partials before the lag sums
 # rsf_diag_finish out[p][RSF_DIAG_OUT], in index order
 DIAG_OUT = ("mean", "var_plus", "W", "B_over_N", "split_rhat", "nested_rhat", "K", "ess", "tau", "mcse_mean", "lags_complete")
+# rank-normalised diagnostics (rsf_diag_rank_*): the four derived series, prepare's stats[p][DIAG_RANK_STATS + n_probs] in index order
+# (then the n_probs quantiles) and rsf_diag_rank_finish out[p][RSF_DIAG_RANK_OUT] in index order
+DIAG_RANK_SERIES = ("bulk", "folded", "q05", "q95")
+DIAG_RANK_STATS = ("median", "q05", "q95", "hdi_lo", "hdi_hi", "nonfinite", "const_bulk", "const_folded", "const_q05", "const_q95")
+DIAG_RANK_OUT = ("rhat", "rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail", "ess_q05", "ess_q95", "lags_complete")
 
 
 def bind(lib):

@@ -21,6 +21,7 @@
 #include "../../include/rsf_diag.h"
 #include "rsf_kernels.h"
 #include "rsf_diag.h"
+#include "rsf_diag_rank.h"
 
 using rsf::Consts;
 using namespace rsfk;
@@ -108,6 +109,9 @@ struct rsf_ctx {
   ncclComm_t comm = nullptr;
   DevBuf pool;  // workspace of the posterior post-processing kernels
   DevBuf diag;  // workspace of the convergence diagnostics (rsf_diag_partials)
+  DevBuf rankws;  // rank workspace (rsf_diag_rank_prepare): the four derived series, then the sort buffers
+  int64_t rank_n = 0, rank_C = 0;  // shape of the prepared trace; rank_d 0 = nothing prepared
+  int32_t rank_d = 0;
 };
 
 namespace {
@@ -602,6 +606,7 @@ int rsf_destroy(rsf_ctx *c) {
     for (auto &s : c->stage) release(s);
     release(c->pool);
     release(c->diag);
+    release(c->rankws);
     release_replay_graph(c);
     if (c->comm) { const Rccl *R = rccl(); if (R) (void)R->comm_destroy(c->comm); }
     for (auto &e : c->ev_done) if (e) (void)hipEventDestroy(e);
@@ -1090,40 +1095,22 @@ int rsf_pool_histogram(rsf_ctx *c, int64_t n, const double *x, int64_t stride, i
 }
 
 // ---- convergence diagnostics (include/rsf_diag.h) ----------------------------------------------
-int rsf_diag_partials(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double *trace, int64_t S, const double *center,
+namespace {
+// rsf_diag_partials after its checks, on a trace x already in device memory
+int diag_partials_dev(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double *x, int64_t S, const rsfk::DiagCenter &cen,
                       int64_t lag_begin, int64_t lag_end, double *partials) {
-  if (!c || !trace || !center || !partials) return fail(RSF_ERR_INVALID, "rsf_diag_partials: NULL argument");
-  if (n < 4 || C < 1 || d < 1 || d > RSF_MAX_PARAMS)
-    return fail(RSF_ERR_INVALID, "rsf_diag_partials: need n_iters >= 4, n_chains >= 1, 1 <= n_params <= %d", RSF_MAX_PARAMS);
-  if (S < 0 || (S > 0 && C % S)) return fail(RSF_ERR_INVALID, "rsf_diag_partials: chains_per_superchain %lld does not divide %lld chains",
-                                             (long long)S, (long long)C);
   const int64_t N = n / 2;
-  if (lag_begin < 0 || lag_end <= lag_begin || lag_end > N)
-    return fail(RSF_ERR_INVALID, "rsf_diag_partials: lags [%lld, %lld) are not a non-empty range within [0, %lld)", (long long)lag_begin,
-                (long long)lag_end, (long long)N);
-  if (n > INT64_MAX / 8 / C / d) return fail(RSF_ERR_INVALID, "rsf_diag_partials: trace too large");
   const int64_t L = lag_end - lag_begin, nbc = (C + kDiagBlock - 1) / kDiagBlock, ntiles = (L + kLagTile - 1) / kLagTile;
-  if (nbc * d * ntiles > INT32_MAX) return fail(RSF_ERR_INVALID, "rsf_diag_partials: too many lags for one call; ask for fewer");
-  rsfk::DiagCenter cen{{0.0, 0.0, 0.0}};
-  for (int p = 0; p < d; ++p) {
-    if (!std::isfinite(center[p])) return fail(RSF_ERR_INVALID, "rsf_diag_partials: center[%d] is not finite", p);
-    cen.v[p] = center[p];
-  }
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_partials: cannot select device %d", c->device);
-  const void *dx;
-  int rc;
-  if ((rc = stage_in(c, 0, trace, (size_t)(n * C * d) * sizeof(double), &dx))) return rc;
   const int64_t K = S ? C / S : 0, nbs = S ? std::min<int64_t>(kDiagSuperBlocks, (K + kDiagBlock / 64 - 1) / (kDiagBlock / 64)) : 0;
   // workspace, doubles: mh[2][d][C] | fm[d][C] | fv[d][C] | chain partials[nbc][d][3] | superchain partials[nbs][d][4] |
   // lag partials[nbc][d][L] | sums[d*3 + d*4 + d*L]
   const int64_t nf1 = d * kDiagChainFields, nf2 = d * kDiagSuperFields, nf3 = d * L;
   const int64_t o_fm = 2 * d * C, o_fv = o_fm + d * C, o_p1 = o_fv + d * C, o_p2 = o_p1 + nbc * nf1, o_p3 = o_p2 + nbs * nf2,
                 o_sum = o_p3 + nbc * nf3, total = o_sum + nf1 + nf2 + nf3;
+  int rc;
   if ((rc = ensure(c->diag, (size_t)total * sizeof(double)))) return rc;
   double *w = (double *)c->diag.p;
   const rsfk::DiagShape sh{n, C, d, N, n - N};
-  const double *x = (const double *)dx;
   switch (d) {
     case 1: hipLaunchKernelGGL(diag_chain_kernel<1>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
     case 2: hipLaunchKernelGGL(diag_chain_kernel<2>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
@@ -1154,6 +1141,34 @@ int rsf_diag_partials(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double 
     for (int64_t j = 0; j < L; ++j) o[RSF_DIAG_HEAD + j] = h3[j];
   }
   return RSF_OK;
+}
+}  // namespace
+
+int rsf_diag_partials(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double *trace, int64_t S, const double *center,
+                      int64_t lag_begin, int64_t lag_end, double *partials) {
+  if (!c || !trace || !center || !partials) return fail(RSF_ERR_INVALID, "rsf_diag_partials: NULL argument");
+  if (n < 4 || C < 1 || d < 1 || d > RSF_MAX_PARAMS)
+    return fail(RSF_ERR_INVALID, "rsf_diag_partials: need n_iters >= 4, n_chains >= 1, 1 <= n_params <= %d", RSF_MAX_PARAMS);
+  if (S < 0 || (S > 0 && C % S)) return fail(RSF_ERR_INVALID, "rsf_diag_partials: chains_per_superchain %lld does not divide %lld chains",
+                                             (long long)S, (long long)C);
+  const int64_t N = n / 2;
+  if (lag_begin < 0 || lag_end <= lag_begin || lag_end > N)
+    return fail(RSF_ERR_INVALID, "rsf_diag_partials: lags [%lld, %lld) are not a non-empty range within [0, %lld)", (long long)lag_begin,
+                (long long)lag_end, (long long)N);
+  if (n > INT64_MAX / 8 / C / d) return fail(RSF_ERR_INVALID, "rsf_diag_partials: trace too large");
+  const int64_t L = lag_end - lag_begin, nbc = (C + kDiagBlock - 1) / kDiagBlock, ntiles = (L + kLagTile - 1) / kLagTile;
+  if (nbc * d * ntiles > INT32_MAX) return fail(RSF_ERR_INVALID, "rsf_diag_partials: too many lags for one call; ask for fewer");
+  rsfk::DiagCenter cen{{0.0, 0.0, 0.0}};
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(center[p])) return fail(RSF_ERR_INVALID, "rsf_diag_partials: center[%d] is not finite", p);
+    cen.v[p] = center[p];
+  }
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_partials: cannot select device %d", c->device);
+  const void *dx;
+  int rc;
+  if ((rc = stage_in(c, 0, trace, (size_t)(n * C * d) * sizeof(double), &dx))) return rc;
+  return diag_partials_dev(c, n, C, d, (const double *)dx, S, cen, lag_begin, lag_end, partials);
 }
 
 int rsf_diag_finish(int64_t n, int32_t d, int64_t S, const double *center, const double *partials, int64_t n_lags, double *out) {
@@ -1214,6 +1229,241 @@ int rsf_diag_finish(int64_t n, int32_t d, int64_t S, const double *center, const
     o[RSF_DIAG_ESS] = MN / tau;
     o[RSF_DIAG_MCSE_MEAN] = std::sqrt(var_plus / o[RSF_DIAG_ESS]);
   }
+  return RSF_OK;
+}
+
+// ---- rank-normalised diagnostics and order statistics (include/rsf_diag.h, rsf_diag_rank_*) ------------------
+namespace {
+constexpr int64_t kRankMaxDraws = INT64_C(1) << 32;  // 32-bit sort indices
+
+// the rank workspace, carved from c->rank (byte offsets rounded to 256)
+struct RankWs {
+  double *series;            // [4][A][d]
+  uint64_t *keys[2];         // [A]
+  uint32_t *idx[2];          // [A + 1] (the spare one holds P during the ranks)
+  uint32_t *th;              // [256][ntiles]: tile histograms, then offsets
+  uint32_t *tm, *tlast, *tfirst;  // [ntiles]
+  uint32_t *hist;            // [8][256] + the non-finite count
+  uint32_t *hpart;           // [kRankKeyBlocks][kRankHist]: per-workgroup histograms of rank_key_kernel
+  void *part;                // [kRankReduceBlocks] RankArg or 2 doubles
+  double *probs, *stats;     // [n_probs], [d][RSF_DIAG_RANK_STATS + n_probs]
+};
+
+size_t rank_ws_layout(int64_t A, int d, int np, char *base, RankWs *w) {
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return base ? base + at : nullptr; };  // base NULL: size only
+  const int64_t ntiles = (A + kRankTile - 1) / kRankTile;
+  w->series = (double *)take((size_t)(4 * A * d) * sizeof(double));
+  for (int b = 0; b < 2; ++b) w->keys[b] = (uint64_t *)take((size_t)A * sizeof(uint64_t));
+  for (int b = 0; b < 2; ++b) w->idx[b] = (uint32_t *)take((size_t)(A + 1) * sizeof(uint32_t));
+  w->th = (uint32_t *)take((size_t)(256 * ntiles) * sizeof(uint32_t));
+  w->tm = (uint32_t *)take((size_t)ntiles * sizeof(uint32_t));
+  w->tlast = (uint32_t *)take((size_t)ntiles * sizeof(uint32_t));
+  w->tfirst = (uint32_t *)take((size_t)ntiles * sizeof(uint32_t));
+  w->hist = (uint32_t *)take(kRankHist * sizeof(uint32_t));
+  w->hpart = (uint32_t *)take((size_t)kRankKeyBlocks * kRankHist * sizeof(uint32_t));
+  w->part = take(kRankReduceBlocks * sizeof(RankArg));
+  w->probs = (double *)take((size_t)(np > 0 ? np : 1) * sizeof(double));
+  w->stats = (double *)take((size_t)(d * (RSF_DIAG_RANK_STATS + np)) * sizeof(double));
+  return o;
+}
+
+// Sorts parameter p's keys (of x, or of |x - median| when folded) into keys[*cur] / idx[*cur]; *bad = a non-finite draw
+int rank_sort(rsf_ctx *c, RankWs &w, int64_t A, int d, int p, const double *x, bool folded, const double *st, int *cur, bool *bad) {
+  const int64_t ntiles = (A + kRankTile - 1) / kRankTile;
+  const int nkb = (int)std::min<int64_t>(kRankKeyBlocks, ntiles);
+  hipLaunchKernelGGL(rank_key_kernel, dim3((unsigned)nkb), dim3(kRankThreads), 0, c->stream, A, d, p, x, folded, st, w.keys[0], w.idx[0], w.hpart);
+  hipLaunchKernelGGL(rank_hist_kernel, dim3((kRankHist + kRankThreads - 1) / kRankThreads), dim3(kRankThreads), 0, c->stream, nkb,
+                     (const uint32_t *)w.hpart, w.hist);
+  HIP_TRY(hipGetLastError());
+  std::vector<uint32_t> h(kRankHist);
+  HIP_TRY(hipMemcpyAsync(h.data(), w.hist, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *bad = h[kRankDigits * 256] != 0;
+  *cur = 0;
+  if (*bad) return RSF_OK;
+  for (int g = 0; g < kRankDigits; ++g) {
+    bool one = false;  // one bucket holds every key: the pass would not move anything
+    for (int b = 0; b < 256; ++b) one = one || (int64_t)h[g * 256 + b] == A;
+    if (one) continue;
+    const int s = *cur;
+    hipLaunchKernelGGL(rank_upsweep_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, A, 8 * g, (const uint64_t *)w.keys[s],
+                       w.th, ntiles);
+    hipLaunchKernelGGL(rank_offsets_kernel, dim3(256), dim3(kRankThreads), 0, c->stream, (const uint32_t *)(w.hist + g * 256), w.th, ntiles);
+    hipLaunchKernelGGL(rank_scatter_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, A, 8 * g, (const uint64_t *)w.keys[s],
+                       (const uint32_t *)w.idx[s], w.keys[1 - s], w.idx[1 - s], (const uint32_t *)w.th, ntiles);
+    *cur = 1 - s;
+  }
+  HIP_TRY(hipGetLastError());
+  return RSF_OK;
+}
+
+// the normal scores of the sorted pairs keys[s] / idx[s] into out (+ p, stride d); idx[1 - s] holds P
+int rank_scores(rsf_ctx *c, RankWs &w, const RankShape &rs, int s, double *out) {
+  const int64_t ntiles = (rs.A + kRankTile - 1) / kRankTile;
+  const uint64_t *k = w.keys[s];
+  const uint32_t *ix = w.idx[s];
+  uint32_t *P = w.idx[1 - s];
+  hipLaunchKernelGGL(rank_tile_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, rs, k, ix, w.tm, w.tlast, w.tfirst);
+  hipLaunchKernelGGL(rank_carry_kernel, dim3(1), dim3(kRankThreads), 0, c->stream, ntiles, (uint32_t)rs.A, w.tm, w.tlast, w.tfirst);
+  hipLaunchKernelGGL(rank_prefix_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, rs, k, ix, (const uint32_t *)w.tm, P);
+  hipLaunchKernelGGL(rank_z_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, rs, k, ix, (const uint32_t *)w.tlast,
+                     (const uint32_t *)w.tfirst, (const uint32_t *)P, out);
+  HIP_TRY(hipGetLastError());
+  return RSF_OK;
+}
+
+int rank_grid(int64_t work, int64_t cap) { return (int)std::max<int64_t>(1, std::min<int64_t>(cap, (work + kRankThreads - 1) / kRankThreads)); }
+}  // namespace
+
+int rsf_diag_rank_prepare(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double *trace, int32_t n_probs, const double *probs,
+                          double hdi_prob, double *stats, double *series) {
+  if (!c || !trace || !stats || (n_probs > 0 && !probs)) return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: NULL argument");
+  if (n < 4 || C < 1 || d < 1 || d > RSF_MAX_PARAMS || n_probs < 0)
+    return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: need n_iters >= 4, n_chains >= 1, 1 <= n_params <= %d, n_probs >= 0", RSF_MAX_PARAMS);
+  if (n >= kRankMaxDraws || C >= kRankMaxDraws || n * C >= kRankMaxDraws)
+    return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: n_iters * n_chains must be below 2^32");
+  for (int i = 0; i < n_probs; ++i)
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: probs[%d] outside [0, 1]", i);
+  const int64_t A = n * C;
+  if (!(hdi_prob > 0.0 && hdi_prob < 1.0)) return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: hdi_prob outside (0, 1)");
+  const double kd = std::floor(hdi_prob * (double)A);  // ArviZ: int(floor(hdi_prob * n))
+  if (kd < 1.0 || kd >= (double)A)
+    return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: the HDI of %g of %lld draws spans %g of them; need 1 <= k < n*C", hdi_prob,
+                (long long)A, kd);
+  const int64_t khdi = (int64_t)kd;
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_rank_prepare: cannot select device %d", c->device);
+  c->rank_d = 0;
+  const void *dx;
+  int rc;
+  if ((rc = stage_in(c, 0, trace, (size_t)(A * d) * sizeof(double), &dx))) return rc;
+  const double *x = (const double *)dx;
+  RankWs w;
+  const size_t bytes = rank_ws_layout(A, d, n_probs, nullptr, &w);
+  if ((rc = ensure(c->rankws, bytes))) return rc;
+  rank_ws_layout(A, d, n_probs, (char *)c->rankws.p, &w);
+  const int ns = RSF_DIAG_RANK_STATS + n_probs;
+  HIP_TRY(hipMemsetAsync(w.stats, 0, (size_t)(d * ns) * sizeof(double), c->stream));
+  if (n_probs) HIP_TRY(hipMemcpyAsync(w.probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  const int64_t N = n / 2, stride = A * d;
+  std::vector<char> bad((size_t)d, 0);
+  for (int p = 0; p < d; ++p) {
+    const RankShape rs{A, (n % 2) ? N * C : 0, (n % 2) ? N * C + C : 0, d, p, 2.0 * (double)C * (double)N};
+    double *st = w.stats + (int64_t)p * ns;
+    int cur;
+    bool nonfinite;
+    if ((rc = rank_sort(c, w, A, d, p, x, false, st, &cur, &nonfinite))) return rc;
+    if (nonfinite) {  // every output of this parameter is NaN
+      bad[(size_t)p] = 1;
+      hipLaunchKernelGGL(rank_fill_kernel, dim3((unsigned)rank_grid(A, 4096)), dim3(kRankThreads), 0, c->stream, rs, w.series, stride, (double)NAN);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    const uint64_t *sorted = w.keys[cur];
+    hipLaunchKernelGGL(rank_order_kernel, dim3(1), dim3(kRankThreads), 0, c->stream, sorted, A, (int)n_probs, (const double *)w.probs, st);
+    const int nh = rank_grid(A - khdi, kRankReduceBlocks);
+    hipLaunchKernelGGL(rank_hdi_kernel, dim3((unsigned)nh), dim3(kRankThreads), 0, c->stream, sorted, A, khdi, (RankArg *)w.part);
+    hipLaunchKernelGGL(rank_hdi_final_kernel, dim3(1), dim3(kRankThreads), 0, c->stream, sorted, A, khdi, nh, (const RankArg *)w.part, st);
+    if ((rc = rank_scores(c, w, rs, cur, w.series))) return rc;                        // bulk: z(x)
+    if ((rc = rank_sort(c, w, A, d, p, x, true, st, &cur, &nonfinite))) return rc;    // folded: z(|x - median|)
+    if ((rc = rank_scores(c, w, rs, cur, w.series + stride))) return rc;
+    hipLaunchKernelGGL(rank_indicator_kernel, dim3((unsigned)rank_grid(A, 4096)), dim3(kRankThreads), 0, c->stream, rs, x, (const double *)st,
+                       w.series + 2 * stride, w.series + 3 * stride);
+    const int nr = rank_grid(A, kRankReduceBlocks);
+    for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
+      hipLaunchKernelGGL(rank_range_kernel, dim3((unsigned)nr), dim3(kRankThreads), 0, c->stream, rs, (const double *)(w.series + q * stride),
+                         (double *)w.part);
+      hipLaunchKernelGGL(rank_range_final_kernel, dim3(1), dim3(64), 0, c->stream, nr, (const double *)w.part, st + kStConst + q);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<double> h((size_t)(d * ns));
+  HIP_TRY(hipMemcpyAsync(h.data(), w.stats, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (series)
+    HIP_TRY(hipMemcpyAsync(series, w.series, (size_t)(4 * stride) * sizeof(double), host_mem(c) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                           c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int p = 0; p < d; ++p) {
+    double *o = stats + (int64_t)p * ns;
+    for (int f = 0; f < ns; ++f) o[f] = bad[(size_t)p] ? NAN : h[(size_t)(p * ns + f)];
+    o[kStNonFinite] = bad[(size_t)p] ? 1.0 : 0.0;
+    if (bad[(size_t)p])
+      for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) o[kStConst + q] = 0.0;
+  }
+  c->rank_n = n; c->rank_C = C; c->rank_d = d;
+  return RSF_OK;
+}
+
+int rsf_diag_rank_partials(rsf_ctx *c, int64_t lag_begin, int64_t lag_end, double *partials) {
+  if (!c || !partials) return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: NULL argument");
+  if (!c->rank_d || !c->rankws.p) return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: no prepared trace (call rsf_diag_rank_prepare first)");
+  const int64_t n = c->rank_n, C = c->rank_C, N = n / 2;
+  const int32_t d = c->rank_d;
+  if (lag_begin < 0 || lag_end <= lag_begin || lag_end > N)
+    return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: lags [%lld, %lld) are not a non-empty range within [0, %lld)", (long long)lag_begin,
+                (long long)lag_end, (long long)N);
+  const int64_t L = lag_end - lag_begin, nbc = (C + kDiagBlock - 1) / kDiagBlock, ntiles = (L + kLagTile - 1) / kLagTile;
+  if (nbc * d * ntiles > INT32_MAX) return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: too many lags for one call; ask for fewer");
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_rank_partials: cannot select device %d", c->device);
+  const rsfk::DiagCenter zero{{0.0, 0.0, 0.0}};
+  const double *series = (const double *)c->rankws.p;  // the workspace starts with the series
+  for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
+    const int rc = diag_partials_dev(c, n, C, d, series + q * n * C * d, 0, zero, lag_begin, lag_end,
+                                     partials + (int64_t)q * d * (RSF_DIAG_HEAD + L));
+    if (rc) return rc;
+  }
+  return RSF_OK;
+}
+
+int rsf_diag_rank_finish(int64_t n, int32_t d, const double *stats, int32_t n_probs, const double *partials, int64_t n_lags, double *out) {
+  if (!stats || !partials || !out) return fail(RSF_ERR_INVALID, "rsf_diag_rank_finish: NULL argument");
+  if (n < 4 || d < 1 || d > RSF_MAX_PARAMS || n_probs < 0)
+    return fail(RSF_ERR_INVALID, "rsf_diag_rank_finish: need n_iters >= 4, 1 <= n_params <= %d, n_probs >= 0", RSF_MAX_PARAMS);
+  const int64_t N = n / 2;
+  if (n_lags < 2 || n_lags > N) return fail(RSF_ERR_INVALID, "rsf_diag_rank_finish: n_lags %lld outside [2, %lld]", (long long)n_lags, (long long)N);
+  const double zero[RSF_MAX_PARAMS] = {0.0, 0.0, 0.0};
+  std::vector<double> o((size_t)(RSF_DIAG_RANK_SERIES * d * RSF_DIAG_OUT));
+  for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
+    const int rc = rsf_diag_finish(n, d, 0, zero, partials + (int64_t)q * d * (RSF_DIAG_HEAD + n_lags), n_lags, o.data() + q * d * RSF_DIAG_OUT);
+    if (rc) return rc;
+  }
+  const int ns = RSF_DIAG_RANK_STATS + n_probs;
+  for (int p = 0; p < d; ++p) {
+    const double *st = stats + (int64_t)p * ns;
+    double *r = out + (int64_t)p * RSF_DIAG_RANK_OUT;
+    double ess[RSF_DIAG_RANK_SERIES], rh[RSF_DIAG_RANK_SERIES];
+    bool complete = true;
+    for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
+      const double *f = o.data() + (q * d + p) * RSF_DIAG_OUT;
+      const double T = partials[((int64_t)q * d + p) * (RSF_DIAG_HEAD + n_lags)] * (double)N;  // M' N
+      ess[q] = st[kStConst + q] != 0.0 ? T : f[RSF_DIAG_ESS];  // ArviZ _ess: a constant series has ess = M'N (tau = 1)
+      rh[q] = f[RSF_DIAG_SPLIT_RHAT];
+      complete = complete && f[RSF_DIAG_LAGS_COMPLETE] != 0.0;
+    }
+    for (int f = 0; f < RSF_DIAG_RANK_OUT; ++f) r[f] = NAN;
+    r[RSF_DIAG_RANK_LAGS_COMPLETE] = complete ? 1.0 : 0.0;
+    if (st[kStNonFinite] != 0.0) continue;
+    auto nanmax = [](double a, double b) { return std::isnan(a) || std::isnan(b) ? NAN : std::max(a, b); };
+    auto nanmin = [](double a, double b) { return std::isnan(a) || std::isnan(b) ? NAN : std::min(a, b); };
+    r[RSF_DIAG_RANK_RHAT_BULK] = rh[0];
+    r[RSF_DIAG_RANK_RHAT_TAIL] = rh[1];
+    r[RSF_DIAG_RANK_RHAT] = nanmax(rh[0], rh[1]);
+    r[RSF_DIAG_RANK_ESS_BULK] = ess[0];
+    r[RSF_DIAG_RANK_ESS_Q05] = ess[2];
+    r[RSF_DIAG_RANK_ESS_Q95] = ess[3];
+    r[RSF_DIAG_RANK_ESS_TAIL] = nanmin(ess[2], ess[3]);
+  }
+  return RSF_OK;
+}
+
+int rsf_diag_rank_release(rsf_ctx *c) {
+  if (!c) return fail(RSF_ERR_INVALID, "rsf_diag_rank_release: NULL argument");
+  DeviceGuard guard(c->device);
+  if (c->rankws.p) HIP_TRY(hipStreamSynchronize(c->stream));
+  release(c->rankws);
+  c->rank_d = 0;
   return RSF_OK;
 }
 

@@ -391,6 +391,88 @@ class Engine:
             if end >= N or all(r["lags_complete"] for r in res):
                 return res
 
+    # -- rank-normalised diagnostics and order statistics (include/rsf_diag.h, rsf_diag_rank_*) -----------
+    def rank_prepare(self, trace, probs=(), hdi_prob=0.94, series=False):
+        """rsf_diag_rank_prepare: sort every parameter's draws on the device and keep the four derived series (zb, zf, I_lo, I_hi) in
+        this engine's rank workspace → stats (d, len(DIAG_RANK_STATS) + len(probs)) on the host, and with series=True also a copy of
+        the series (4, n, C, d) in this engine's memory space.  rank_partials then reads the workspace; rank_release frees it."""
+        x, n, C, d = self._diag_trace(trace)
+        pr = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+        stats = np.empty((d, len(_abi.DIAG_RANK_STATS) + pr.size))
+        out = self._empty((4, n, C, d)) if series else None
+        dbl = ctypes.POINTER(ctypes.c_double)
+        _abi.check(self.lib, self.lib.rsf_diag_rank_prepare(self._ctx, n, C, d, self._ptr(x), int(pr.size), pr.ctypes.data_as(dbl),
+                                                            float(hdi_prob), stats.ctypes.data_as(dbl), self._ptr(out)))
+        self._rank_d = d
+        return (stats, out) if series else stats
+
+    def rank_partials(self, lag_begin, lag_end):
+        """rsf_diag_rank_partials: the diagnostics partials of the four prepared series → (4, d, DIAG_HEAD + L) on the host."""
+        d = getattr(self, "_rank_d", None)
+        if d is None:
+            raise ValueError("rank_partials before rank_prepare")
+        out = np.empty((4, d, _abi.DIAG_HEAD + max(int(lag_end) - int(lag_begin), 0)))
+        _abi.check(self.lib, self.lib.rsf_diag_rank_partials(self._ctx, int(lag_begin), int(lag_end),
+                                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
+    def rank_finish(self, n_iters, stats, partials, n_lags=None):
+        """rsf_diag_rank_finish (host only) → (d, len(DIAG_RANK_OUT)) float64."""
+        st = np.ascontiguousarray(np.asarray(stats, dtype=np.float64))
+        part = np.ascontiguousarray(np.asarray(partials, dtype=np.float64))
+        d = int(st.shape[0])
+        n_lags = int(part.shape[-1]) - _abi.DIAG_HEAD if n_lags is None else int(n_lags)
+        if part.shape != (4, d, _abi.DIAG_HEAD + n_lags):
+            raise ValueError(f"partials must be (4, {d}, DIAG_HEAD + n_lags), not {part.shape}")
+        out = np.empty((d, len(_abi.DIAG_RANK_OUT)))
+        dbl = ctypes.POINTER(ctypes.c_double)
+        _abi.check(self.lib, self.lib.rsf_diag_rank_finish(int(n_iters), d, st.ctypes.data_as(dbl), int(st.shape[1]) - len(_abi.DIAG_RANK_STATS),
+                                                           part.ctypes.data_as(dbl), n_lags, out.ctypes.data_as(dbl)))
+        return out
+
+    def rank_release(self):
+        self._rank_d = None
+        _abi.check(self.lib, self.lib.rsf_diag_rank_release(self._ctx))
+
+    def rank_diagnostics(self, trace, probs=(0.025, 0.5, 0.975), hdi_prob=0.94, n_lags=None, lag_block=64):
+        """Rank-normalised R-hat (max of bulk and folded-tail split R-hat), bulk and tail ESS, median, quantiles and the HDI of a
+        trace (n, C[, d]), as ArviZ reports them (include/rsf_diag.h) → one dict per parameter: rhat, rhat_bulk, rhat_tail,
+        ess_bulk, ess_tail, ess_q05, ess_q95, median, quantiles {prob: value}, hdi (lo, hi), n_lags, lags_complete.  The trace
+        is sorted once; the lags of the four derived series are then computed `lag_block` at a time until Geyer's truncation is
+        reached for all of them (or exactly [0, n_lags)).  The rank workspace is freed before returning."""
+        x, n, _, d = self._diag_trace(trace)
+        probs = tuple(float(p) for p in probs)
+        if n_lags is None and int(lag_block) < 2:
+            raise ValueError("lag_block must be >= 2")
+        stats = self.rank_prepare(x, probs, hdi_prob)
+        try:
+            N = n // 2
+            if n_lags is not None:
+                part = self.rank_partials(0, int(n_lags))
+                out = self.rank_finish(n, stats, part)
+            else:
+                part = None
+                while True:
+                    end = 0 if part is None else part.shape[-1] - _abi.DIAG_HEAD
+                    new = self.rank_partials(end, min(N, end + int(lag_block)))
+                    part = new if part is None else np.concatenate([part, new[:, :, _abi.DIAG_HEAD:]], axis=2)
+                    out = self.rank_finish(n, stats, part)
+                    if part.shape[-1] - _abi.DIAG_HEAD >= N or np.all(out[:, -1] != 0):
+                        break
+        finally:
+            self.rank_release()
+        L = part.shape[-1] - _abi.DIAG_HEAD
+        res = []
+        for p in range(d):
+            r = dict(zip(_abi.DIAG_RANK_OUT, (float(v) for v in out[p])))
+            st = dict(zip(_abi.DIAG_RANK_STATS, (float(v) for v in stats[p])))
+            r["lags_complete"], r["n_lags"] = bool(r["lags_complete"]), L
+            r["median"] = st["median"]
+            r["quantiles"] = {pr: float(v) for pr, v in zip(probs, stats[p, len(_abi.DIAG_RANK_STATS):])}
+            r["hdi"] = (st["hdi_lo"], st["hdi_hi"])
+            res.append(r)
+        return res
+
     # -- multi-GPU posterior pool through the C ABI (RCCL bound inside the library; SURVEY §8e) -----
     def comm_unique_id(self):
         """Rank 0: the 128-byte id every rank passes to comm_init (send it over any channel)."""

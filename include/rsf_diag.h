@@ -70,6 +70,70 @@ int rsf_diag_partials(rsf_ctx *ctx, int64_t n_iters, int64_t n_chains, int32_t n
 int rsf_diag_finish(int64_t n_iters, int32_t n_params, int64_t chains_per_superchain, const double *center,
                     const double *partials, int64_t n_lags, double *out);
 
+/*
+ * Rank-normalised diagnostics and order statistics (Vehtari et al. 2021, as ArviZ reports them; the specification is
+ * tests/rank_diagnostics_reference.py).  Per parameter p, with A = n*C draws (the full set), N = floor(n/2) and the split set =
+ * rows [0, N) and [n-N, n), T = 2CN draws (an odd n leaves out the middle row):
+ *   order statistics  of the full set sorted ascending, s[0..A-1], -0.0 == +0.0: median (np.median); quantile(prob) with
+ *                     h = (A-1) prob, lo = floor(h), g = h - lo, a = s[lo], b = s[min(lo+1, A-1)]: a + (b-a) g if g < 0.5,
+ *                     else b - (b-a)(1-g) (np.quantile "linear"); HDI(prob): k = floor(prob A), the first i of the smallest
+ *                     s[i+k] - s[i], i < A-k, gives (s[i], s[i+k]) (ArviZ, not circular).
+ *   normal scores     r(v) = L + (E+1)/2 with L, E = split draws < v, == v (average ranks); z(v) = ndtri((r - 3/8) / (T + 1/4)).
+ *   series            zb = z(x); zf = the normal scores of |x - median| among the split set's |x - median|; I_lo = [x <= q05];
+ *                     I_hi = [x <= q95] (q05, q95: quantile(0.05), quantile(0.95)).  Each has the trace's shape; the middle row
+ *                     holds 0 and is never read.
+ *   statistics        each series through rsf_diag_partials (centre 0, no superchains) and rsf_diag_finish: rhat_bulk = split R-hat
+ *                     of zb, rhat_tail = that of zf, rhat = max of the two (NaN if either is); ess_bulk = ESS of zb, ess_q05 / ess_q95
+ *                     = ESS of I_lo / I_hi, ess_tail = their minimum.  A series whose split draws span less than 1e-15 (constant)
+ *                     has ESS = T instead of NaN; its R-hat stays NaN.
+ *   non-finite        a non-finite draw of p makes every output of p NaN (lags_complete excepted); other parameters are unaffected.
+ * Ranks are global: the statistics of shards do not add.  Gather a multi-rank pool first.
+ */
+#define RSF_DIAG_RANK_SERIES 4 /* zb, zf, I_lo, I_hi: series-major [4][n][C][d] */
+
+/* rsf_diag_rank_prepare stats[p][RSF_DIAG_RANK_STATS + n_probs] */
+#define RSF_DIAG_RANK_MEDIAN 0
+#define RSF_DIAG_RANK_Q05 1
+#define RSF_DIAG_RANK_Q95 2
+#define RSF_DIAG_RANK_HDI_LO 3
+#define RSF_DIAG_RANK_HDI_HI 4
+#define RSF_DIAG_RANK_NONFINITE 5  /* 1 when p has a non-finite draw (every other field NaN, constant flags 0) */
+#define RSF_DIAG_RANK_CONST 6      /* 6..9: 1 when series zb, zf, I_lo, I_hi is constant over the split set */
+#define RSF_DIAG_RANK_STATS 10     /* then quantile(probs[i]) for i < n_probs */
+
+/* rsf_diag_rank_finish out[p][RSF_DIAG_RANK_OUT] */
+#define RSF_DIAG_RANK_RHAT 0
+#define RSF_DIAG_RANK_RHAT_BULK 1
+#define RSF_DIAG_RANK_RHAT_TAIL 2
+#define RSF_DIAG_RANK_ESS_BULK 3
+#define RSF_DIAG_RANK_ESS_TAIL 4
+#define RSF_DIAG_RANK_ESS_Q05 5
+#define RSF_DIAG_RANK_ESS_Q95 6
+#define RSF_DIAG_RANK_LAGS_COMPLETE 7 /* 1 when all four series reached Geyer's truncation within the lags given */
+#define RSF_DIAG_RANK_OUT 8
+
+/* Sorts every parameter's draws on the device once and keeps the four series in a ctx workspace (about 4x the trace plus
+ * 24 B per draw; rsf_diag_rank_release or rsf_destroy frees it).  trace, series: ctx memory space; probs, stats: host.  series
+ * (optional, NULL = device only) receives a copy of [4][n][C][d].  Deterministic: the same trace gives the same bits, host or
+ * device memory alike.  RSF_ERR_INVALID (checked before the device is touched): n_iters < 4, n_chains < 1, n_params outside
+ * 1..3, n_iters * n_chains >= 2^32, n_probs < 0, a probability outside [0, 1], hdi_prob outside (0, 1) or k = floor(hdi_prob*A)
+ * outside [1, A), a NULL pointer (probs may be NULL when n_probs = 0). */
+int rsf_diag_rank_prepare(rsf_ctx *ctx, int64_t n_iters, int64_t n_chains, int32_t n_params, const double *trace, int32_t n_probs,
+                          const double *probs, double hdi_prob, double *stats, double *series);
+
+/* rsf_diag_partials of each prepared series with centre 0 and no superchains: partials[4][d][RSF_DIAG_HEAD + L] (host).  Call it
+ * for lag blocks until rsf_diag_rank_finish reports lags_complete.  RSF_ERR_INVALID: nothing prepared, the lag range as in
+ * rsf_diag_partials, a NULL pointer. */
+int rsf_diag_rank_partials(rsf_ctx *ctx, int64_t lag_begin, int64_t lag_end, double *partials);
+
+/* Host-only: the statistics from prepare's stats and the four series' partials with lags [0, n_lags), out[d][RSF_DIAG_RANK_OUT].
+ * RSF_ERR_INVALID: as rsf_diag_finish, n_probs < 0. */
+int rsf_diag_rank_finish(int64_t n_iters, int32_t n_params, const double *stats, int32_t n_probs, const double *partials,
+                         int64_t n_lags, double *out);
+
+/* Frees the rank workspace; rsf_diag_rank_partials is invalid until the next prepare. */
+int rsf_diag_rank_release(rsf_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
