@@ -199,8 +199,6 @@ bool damped(const rsf_ctx *c, int mode) {
 // chains a lane of the sampler kernel carries: two in the float32 mode (mcmc_f32x2_kernel), else one
 int chains_per_lane(const rsf_ctx *c) { return mode_of(c) == RK4_F32 ? 2 : 1; }
 
-// LDS of a sampler launch: the table chunk, and behind it the per-lane Cholesky factors of a three-parameter chain
-// (six doubles per lane, mcmc_kernel)
 // the table chunk as the sampler kernel stages it: doubles, or floats in the float32 sampler — with a chunk length of its own
 // (kc32, rsf_set_model): nsteps 4000 is ONE chunk of 48 KB there, resident for the whole launch, where the shared length kc
 // (sized for doubles) made it two, staged — with two workgroup barriers each — for every proposal
@@ -217,20 +215,42 @@ Consts make_sampler_consts(const rsf_ctx *c, const double *data) {
   return K;
 }
 
-size_t mcmc_lds_bytes(const rsf_ctx *c) {
-  // per lane behind the table chunk: the float64 RK4 sampler parks the chain's point, sigma^2, SSq and log u there across
-  // the forward solve (kParkSlots: 4 doubles for one parameter; 12 for three, whose first six hold the chain's Cholesky
-  // factor); the other samplers keep only the factor of a three-parameter chain (two chains per lane in float32)
-  const int d = c->mc.n_params;
-  size_t slots = d == 3 ? (mode_of(c) == RK4_F32 ? 12 : 6) : 0;
-  if (mode_of(c) == RK4_F64) slots = d == 3 ? kParkSlots<3> : kParkSlots<1>;
-  return mcmc_table_bytes(c) + slots * sizeof(double) * (size_t)c->block;
+// The sampler kernel of a launch, and its grid and LDS: the table chunk (mcmc_table_bytes), and behind it per-lane slots
+// (rsf_kernels.h: the float64 RK4 sampler parks the chain state there; the others keep only a three-parameter chain's
+// Cholesky factor, one per chain of the lane).  INJECT (rsf_mcmc_replay_ssq, any mode): the chain logic alone on supplied
+// sums of squares — no tables, one chain per lane, its slots at the base of LDS.
+struct SamplerLaunch {
+  const void *fn;
+  unsigned grid;
+  size_t lds;
+  int32_t lc_off;  // McmcArgs::lc_off: the slots' offset in doubles
+};
+
+template <int D, bool DAMP>
+const void *sampler_kernel(int mode, bool replay, bool inject) {
+  if (inject) return (const void *)mcmc_kernel<D, false, true, RK4_F64, true>;
+  switch (mode) {
+    case RK4_F32: return replay ? (const void *)mcmc_f32x2_kernel<D, DAMP, true> : (const void *)mcmc_f32x2_kernel<D, DAMP, false>;
+    case DOP853: return replay ? (const void *)mcmc_kernel<D, DAMP, true, DOP853> : (const void *)mcmc_kernel<D, DAMP, false, DOP853>;
+    default: return replay ? (const void *)mcmc_kernel<D, DAMP, true, RK4_F64> : (const void *)mcmc_kernel<D, DAMP, false, RK4_F64>;
+  }
 }
 
-// workgroups of a sampler launch over n chains
-unsigned mcmc_grid(const rsf_ctx *c, int64_t n) {
-  const int64_t per = (int64_t)c->block * chains_per_lane(c);
-  return (unsigned)((n + per - 1) / per);
+SamplerLaunch sampler_launch(const rsf_ctx *c, bool replay, bool inject) {
+  const int d = c->mc.n_params, mode = inject ? RK4_F64 : mode_of(c), nc = inject ? 1 : chains_per_lane(c);
+  const bool damp = damped(c, mode_of(c));
+  const void *fn = d == 1 ? (damp ? sampler_kernel<1, true>(mode, replay, inject) : sampler_kernel<1, false>(mode, replay, inject))
+                          : (damp ? sampler_kernel<3, true>(mode, replay, inject) : sampler_kernel<3, false>(mode, replay, inject));
+  const size_t table = inject ? 0 : mcmc_table_bytes(c);
+  const size_t slots = mode == RK4_F64 ? park_slots(d) : factor_slots(d) * nc;
+  const int64_t per = (int64_t)c->block * nc;
+  return {fn, (unsigned)((c->mc.n_chains + per - 1) / per), table + slots * sizeof(double) * (size_t)c->block, (int32_t)(table / sizeof(double))};
+}
+
+int launch_sampler(rsf_ctx *c, const SamplerLaunch &L, Consts K, McmcArgs A) {
+  void *args[2] = {&K, &A};
+  HIP_TRY(hipLaunchKernel(L.fn, dim3(L.grid), dim3(c->block), args, L.lds, c->stream));
+  return RSF_OK;
 }
 
 // [n][d] (the C ABI's layout) <-> [d][n] (the kernels' structure of arrays); both device pointers, on the ctx stream
@@ -243,37 +263,6 @@ int transpose(rsf_ctx *c, int64_t n, int d, const double *src, double *dst, bool
   return RSF_OK;
 }
 
-template <int D, bool DAMP, int MODE>
-int launch_mcmc(rsf_ctx *c, const Consts &K, const McmcArgs &A, bool replay) {
-  const dim3 grid(mcmc_grid(c, A.C)), block(c->block);
-  if constexpr (MODE == RK4_F32) {
-    if (replay)
-      hipLaunchKernelGGL((mcmc_f32x2_kernel<D, DAMP, true>), grid, block, mcmc_lds_bytes(c), c->stream, K, A);
-    else
-      hipLaunchKernelGGL((mcmc_f32x2_kernel<D, DAMP, false>), grid, block, mcmc_lds_bytes(c), c->stream, K, A);
-  } else {
-    if (replay)
-      hipLaunchKernelGGL((mcmc_kernel<D, DAMP, true, MODE>), grid, block, mcmc_lds_bytes(c), c->stream, K, A);
-    else
-      hipLaunchKernelGGL((mcmc_kernel<D, DAMP, false, MODE>), grid, block, mcmc_lds_bytes(c), c->stream, K, A);
-  }
-  return RSF_OK;
-}
-
-template <int D, bool DAMP>
-int launch_mcmc_m(rsf_ctx *c, const Consts &K, const McmcArgs &A, bool replay) {
-  switch (mode_of(c)) {
-    case RK4_F32: return launch_mcmc<D, DAMP, RK4_F32>(c, K, A, replay);
-    case DOP853: return launch_mcmc<D, DAMP, DOP853>(c, K, A, replay);
-    default: return launch_mcmc<D, DAMP, RK4_F64>(c, K, A, replay);
-  }
-}
-
-template <int D>
-int launch_mcmc_d(rsf_ctx *c, const Consts &K, const McmcArgs &A, bool replay) {
-  return damped(c, mode_of(c)) ? launch_mcmc_m<D, true>(c, K, A, replay) : launch_mcmc_m<D, false>(c, K, A, replay);
-}
-
 // RSF_MEM_HOST callers with a long run: launches of `per` iterations write their trace rows into one of two device
 // staging sets; while launch k+1 computes, the rows of launch k go to the caller's arrays on a second stream.  The
 // chain is the same as with one launch (the kernel continues from iter_base; tests: continuation == single launch).
@@ -284,7 +273,7 @@ size_t drain_bytes() {
   return v > 0 ? (size_t)v : (size_t)32 << 20;
 }
 
-int run_mcmc_drained(rsf_ctx *c, const Consts &K, McmcArgs A, int64_t per, double *tq, double *ts, uint8_t *ta) {
+int run_mcmc_drained(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcArgs A, int64_t per, double *tq, double *ts, uint8_t *ta) {
   const int d = c->mc.n_params;
   const size_t C = (size_t)A.C;
   const int64_t n_iters = A.n_iters;
@@ -317,8 +306,7 @@ int run_mcmc_drained(rsf_ctx *c, const Consts &K, McmcArgs A, int64_t per, doubl
     A.tq = tq ? (double *)c->stage[slot_q[b]].p : nullptr;
     A.ts = ts ? (double *)c->stage[slot_s[b]].p : nullptr;
     A.ta = ta ? (uint8_t *)c->stage[slot_a[b]].p : nullptr;
-    rc = d == 1 ? launch_mcmc_d<1>(c, K, A, false) : launch_mcmc_d<3>(c, K, A, false);
-    if (rc) return rc;
+    if ((rc = launch_sampler(c, L, K, A))) return rc;
     HIP_TRY(hipEventRecord(c->ev_done[b], c->stream));
     if (prev_n && (rc = drain(b ^ 1, prev_first, prev_n))) return rc;
     prev_first = done; prev_n = n;
@@ -331,21 +319,6 @@ int run_mcmc_drained(rsf_ctx *c, const Consts &K, McmcArgs A, int64_t per, doubl
 }
 
 constexpr int64_t kReplayGraphMaxChains = 4096;  // beyond this the copies dominate and the plain path is as good
-
-template <int D, bool DAMP>
-const void *replay_kernel_m(const rsf_ctx *c) {
-  switch (mode_of(c)) {
-    case RK4_F32: return (const void *)mcmc_f32x2_kernel<D, DAMP, true>;
-    case DOP853: return (const void *)mcmc_kernel<D, DAMP, true, DOP853>;
-    default: return (const void *)mcmc_kernel<D, DAMP, true, RK4_F64>;
-  }
-}
-
-const void *replay_kernel(const rsf_ctx *c) {
-  const bool damp = damped(c, mode_of(c));
-  if (c->mc.n_params == 1) return damp ? replay_kernel_m<1, true>(c) : replay_kernel_m<1, false>(c);
-  return damp ? replay_kernel_m<3, true>(c) : replay_kernel_m<3, false>(c);
-}
 
 void release_replay_graph(rsf_ctx *c) {
   auto &g = c->rg;
@@ -360,16 +333,15 @@ void release_replay_graph(rsf_ctx *c) {
 // otherwise being three small H2D copies, a 0.1 ms kernel, three D2H copies and a synchronise.  The sequence is a
 // three-node hipGraph (H2D of one pinned input block, the kernel, D2H of one pinned output block) instantiated once per
 // (chains, parameters, kernel) and relaunched with fresh kernel arguments: one runtime call per proposal instead of seven.
-int run_replay_graph(rsf_ctx *c, const Consts &K, McmcArgs A, const double *z, const double *u, const double *g, double *tq,
+int run_replay_graph(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcArgs A, const double *z, const double *u, const double *g, double *tq,
                      double *ts, uint8_t *ta) {
   auto &G = c->rg;
   const int d = c->mc.n_params;
   const size_t C = (size_t)A.C;
   const size_t in_bytes = (C * d + 2 * C) * sizeof(double), out_bytes = (C * d + C) * sizeof(double) + C;
   const size_t out_off = (in_bytes + 255) & ~(size_t)255, total = out_off + ((out_bytes + 255) & ~(size_t)255);
-  const void *fn = replay_kernel(c);
   char *hb = (char *)G.host, *db = (char *)G.dev;
-  const bool rebuild = !G.exec || G.C != A.C || G.d != d || G.fn != fn || G.lds != mcmc_lds_bytes(c) || G.block != c->block;
+  const bool rebuild = !G.exec || G.C != A.C || G.d != d || G.fn != L.fn || G.lds != L.lds || G.block != c->block;
   if (rebuild) {
     release_replay_graph(c);
     HIP_TRY(hipHostMalloc(&G.host, total, hipHostMallocDefault));
@@ -383,9 +355,9 @@ int run_replay_graph(rsf_ctx *c, const Consts &K, McmcArgs A, const double *z, c
   Consts Kc = K;
   void *params[2] = {&Kc, &A};
   hipKernelNodeParams kp{};
-  kp.func = const_cast<void *>(fn);
-  kp.gridDim = dim3(mcmc_grid(c, A.C)); kp.blockDim = dim3(c->block);
-  kp.sharedMemBytes = (unsigned)mcmc_lds_bytes(c);
+  kp.func = const_cast<void *>(L.fn);
+  kp.gridDim = dim3(L.grid); kp.blockDim = dim3(c->block);
+  kp.sharedMemBytes = (unsigned)L.lds;
   kp.kernelParams = params;
   kp.extra = nullptr;
   if (rebuild) {
@@ -395,7 +367,7 @@ int run_replay_graph(rsf_ctx *c, const Consts &K, McmcArgs A, const double *z, c
     HIP_TRY(hipGraphAddKernelNode(&G.kernel, G.graph, &h2d, 1, &kp));
     HIP_TRY(hipGraphAddMemcpyNode1D(&d2h, G.graph, &G.kernel, 1, hb + out_off, db + out_off, out_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0));
-    G.C = A.C; G.d = d; G.fn = fn; G.lds = mcmc_lds_bytes(c); G.block = c->block;
+    G.C = A.C; G.d = d; G.fn = L.fn; G.lds = L.lds; G.block = c->block;
   } else {
     HIP_TRY(hipGraphExecKernelNodeSetParams(G.exec, G.kernel, &kp));
   }
@@ -410,15 +382,6 @@ int run_replay_graph(rsf_ctx *c, const Consts &K, McmcArgs A, const double *z, c
   if (ts) std::memcpy(ts, ho + C * d, C * sizeof(double));
   if (ta) std::memcpy(ta, (const uint8_t *)(ho + C * d + C), C);
   c->iters_done += 1;
-  return RSF_OK;
-}
-
-// the chain logic alone on caller-supplied sums of squares (rsf_mcmc_replay_ssq): no tables, no solve, one chain per lane
-template <int D>
-int launch_mcmc_inject(rsf_ctx *c, const Consts &K, McmcArgs A) {
-  A.lc_off = 0;  // nothing is staged: the per-lane slots of a three-parameter chain start at the base of LDS
-  const size_t lds = kParkSlots<D> * sizeof(double) * (size_t)c->block;
-  hipLaunchKernelGGL((mcmc_kernel<D, false, true, RK4_F64, true>), dim3(grid_for(c, A.C)), dim3(c->block), lds, c->stream, K, A);
   return RSF_OK;
 }
 
@@ -446,16 +409,17 @@ int run_mcmc(rsf_ctx *c, int64_t n_iters, const double *z, const double *u, cons
   }
   A.adapt_mode = c->mc.adapt_mode; A.adapt_interval = c->mc.adapt_interval > 0 ? c->mc.adapt_interval : 1;
   A.dict_scale = 2.38 * 2.38 / (double)(c->mc.prior_len > 0 ? c->mc.prior_len : 2);
-  A.lc_off = (int32_t)(mcmc_table_bytes(c) / sizeof(double));
   A.q = (double *)c->q.p; A.ssq = (double *)c->ssq.p; A.std2 = (double *)c->std2.p; A.V = (double *)c->V.p;
   A.wref = (double *)c->wref.p; A.wsum = (double *)c->wsum.p; A.wsq = (double *)c->wsq.p; A.wn = (int32_t *)c->wn.p;
   A.wbuf = (double *)c->wbuf.p;
   A.stats = (unsigned long long *)c->stats.p;
+  const SamplerLaunch L = sampler_launch(c, replay, ssq_new != nullptr);
+  A.lc_off = L.lc_off;
   int rc;
   if (replay && !ssq_new && host_mem(c) && n_iters == 1 && C <= kReplayGraphMaxChains) {
     Consts Kg = make_sampler_consts(c, (const double *)c->data.p);
     Kg.group_chains = c->group_chains;
-    return run_replay_graph(c, Kg, A, z, u, g, tq, ts, ta);
+    return run_replay_graph(c, L, Kg, A, z, u, g, tq, ts, ta);
   }
   const void *dz = nullptr, *du = nullptr, *dg = nullptr;
   void *dtq = nullptr, *dts = nullptr, *dta = nullptr;
@@ -471,15 +435,13 @@ int run_mcmc(rsf_ctx *c, int64_t n_iters, const double *z, const double *u, cons
   if (host_mem(c) && !replay) {
     const size_t row_bytes = (size_t)C * ((tq ? d * sizeof(double) : 0) + (ts ? sizeof(double) : 0) + (ta ? 1 : 0));
     const int64_t per = row_bytes ? std::max<int64_t>(1, (int64_t)(drain_bytes() / row_bytes)) : n_iters;
-    if (per < n_iters) return run_mcmc_drained(c, K, A, per, tq, ts, ta);
+    if (per < n_iters) return run_mcmc_drained(c, L, K, A, per, tq, ts, ta);
   }
   if ((rc = stage_out(c, 3, tq, rows * d * sizeof(double), &dtq))) return rc;
   if ((rc = stage_out(c, 4, ts, rows * sizeof(double), &dts))) return rc;
   if ((rc = stage_out(c, 5, ta, rows, &dta))) return rc;
   A.tq = (double *)dtq; A.ts = (double *)dts; A.ta = (uint8_t *)dta;
-  if (ssq_new) rc = d == 1 ? launch_mcmc_inject<1>(c, K, A) : launch_mcmc_inject<3>(c, K, A);
-  else rc = d == 1 ? launch_mcmc_d<1>(c, K, A, replay) : launch_mcmc_d<3>(c, K, A, replay);
-  if (rc) return rc;
+  if ((rc = launch_sampler(c, L, K, A))) return rc;
   if ((rc = copy_back(c, 3, tq, rows * d * sizeof(double)))) return rc;
   if ((rc = copy_back(c, 4, ts, rows * sizeof(double)))) return rc;
   if ((rc = copy_back(c, 5, ta, rows))) return rc;
@@ -752,30 +714,25 @@ int rsf_forward_batch(rsf_ctx *c, int64_t n, const double *dc, const double *a, 
   return finish(c);
 }
 
-int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, const double *data) {
-  if (!c || !cfg || !q0 || !data) return fail(RSF_ERR_INVALID, "rsf_mcmc_init: NULL argument");
-  if (!c->have_model) return fail(RSF_ERR_STATE, "rsf_mcmc_init: call rsf_set_model first");
-  if (cfg->size != sizeof(rsf_mcmc_config)) return fail(RSF_ERR_INVALID, "rsf_mcmc_init: struct size mismatch");
-  if (cfg->n_params != 1 && cfg->n_params != 3) return fail(RSF_ERR_UNSUPPORTED, "rsf_mcmc_init: n_params must be 1 or 3");
-  if (cfg->n_chains < 1) return fail(RSF_ERR_INVALID, "rsf_mcmc_init: n_chains < 1");
+// What rsf_mcmc_init and rsf_mcmc_init_state share: the config checks (fn: the entry point the messages name), the
+// chain-state arrays (structure of arrays, rsf_kernels.h) with the adaptation window and counters, and a fresh window about
+// the chains' points once q is set.
+int check_mcmc_config(const rsf_mcmc_config *cfg, const char *fn) {
+  if (cfg->size != sizeof(rsf_mcmc_config)) return fail(RSF_ERR_INVALID, "%s: struct size mismatch", fn);
+  if (cfg->n_params != 1 && cfg->n_params != 3) return fail(RSF_ERR_UNSUPPORTED, "%s: n_params must be 1 or 3", fn);
+  if (cfg->n_chains < 1) return fail(RSF_ERR_INVALID, "%s: n_chains < 1", fn);
   if (cfg->adapt_mode == RSF_ADAPT_REFERENCE_DICT && cfg->n_params != 1)
-    return fail(RSF_ERR_UNSUPPORTED, "rsf_mcmc_init: reference_dict adaptation is defined for 1 parameter only");
+    return fail(RSF_ERR_UNSUPPORTED, "%s: reference_dict adaptation is defined for 1 parameter only", fn);
   if (cfg->adapt_mode < 0 || cfg->adapt_mode > RSF_ADAPT_AM || (cfg->adapt_mode && cfg->adapt_interval < 2))
-    return fail(RSF_ERR_INVALID, "rsf_mcmc_init: bad adapt_mode / adapt_interval");
-  const int G = cfg->n_groups > 1 ? cfg->n_groups : 1;
-  // a workgroup's chains share one observation series: a group must be whole workgroups' worth of chains
-  const int wg_chains = c->block * chains_per_lane(c);
-  if (cfg->n_groups < 0 || cfg->n_chains % G || (G > 1 && (cfg->n_chains / G) % wg_chains))
-    return fail(RSF_ERR_INVALID, "rsf_mcmc_init: n_chains/n_groups must be a whole multiple of a workgroup's chains (%d%s)", wg_chains,
-                chains_per_lane(c) == 2 ? ": the float32 sampler carries two chains per lane" : "");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_mcmc_init: cannot select device %d", c->device);
+    return fail(RSF_ERR_INVALID, "%s: bad adapt_mode / adapt_interval", fn);
+  return RSF_OK;
+}
+
+int alloc_chains(rsf_ctx *c, const rsf_mcmc_config *cfg) {
   const int d = cfg->n_params;
   const int64_t C = cfg->n_chains;
   const size_t cb = (size_t)C * sizeof(double);
-  const size_t data_bytes = (size_t)G * (size_t)c->nout * sizeof(double);
   int rc;
-  if ((rc = ensure(c->data, data_bytes))) return rc;
   if ((rc = ensure(c->q, cb * d))) return rc;
   if ((rc = ensure(c->ssq, cb))) return rc;
   if ((rc = ensure(c->std2, cb))) return rc;
@@ -791,16 +748,46 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
     HIP_TRY(hipMemsetAsync(c->wbuf.p, 0, cb * (size_t)cfg->adapt_interval, c->stream));
   }
   if ((rc = ensure(c->stats, RSF_CNT_COUNT * sizeof(unsigned long long)))) return rc;
-  const hipMemcpyKind kind = host_mem(c) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  HIP_TRY(hipMemcpyAsync(c->data.p, data, data_bytes, kind, c->stream));
-  const void *dq0;
-  if ((rc = stage_in(c, 0, q0, cb * d, &dq0))) return rc;
-  if ((rc = transpose(c, C, d, (const double *)dq0, (double *)c->q.p, true))) return rc;
+  return RSF_OK;
+}
+
+int reset_window(rsf_ctx *c, const rsf_mcmc_config *cfg) {
+  const int d = cfg->n_params;
+  const int64_t C = cfg->n_chains;
+  const size_t cb = (size_t)C * sizeof(double);
   HIP_TRY(hipMemcpyAsync(c->wref.p, c->q.p, cb * d, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(c->wsum.p, 0, cb * d, c->stream));
   HIP_TRY(hipMemsetAsync(c->wsq.p, 0, cb * d * d, c->stream));
   HIP_TRY(hipMemsetAsync(c->wn.p, 0, (size_t)C * sizeof(int32_t), c->stream));
   HIP_TRY(hipMemsetAsync(c->stats.p, 0, RSF_CNT_COUNT * sizeof(unsigned long long), c->stream));
+  return RSF_OK;
+}
+
+int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, const double *data) {
+  int rc;
+  if (!c || !cfg || !q0 || !data) return fail(RSF_ERR_INVALID, "rsf_mcmc_init: NULL argument");
+  if (!c->have_model) return fail(RSF_ERR_STATE, "rsf_mcmc_init: call rsf_set_model first");
+  if ((rc = check_mcmc_config(cfg, "rsf_mcmc_init"))) return rc;
+  const int G = cfg->n_groups > 1 ? cfg->n_groups : 1;
+  // a workgroup's chains share one observation series: a group must be whole workgroups' worth of chains
+  const int wg_chains = c->block * chains_per_lane(c);
+  if (cfg->n_groups < 0 || cfg->n_chains % G || (G > 1 && (cfg->n_chains / G) % wg_chains))
+    return fail(RSF_ERR_INVALID, "rsf_mcmc_init: n_chains/n_groups must be a whole multiple of a workgroup's chains (%d%s)", wg_chains,
+                chains_per_lane(c) == 2 ? ": the float32 sampler carries two chains per lane" : "");
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_mcmc_init: cannot select device %d", c->device);
+  const int d = cfg->n_params;
+  const int64_t C = cfg->n_chains;
+  const size_t cb = (size_t)C * sizeof(double);
+  const size_t data_bytes = (size_t)G * (size_t)c->nout * sizeof(double);
+  if ((rc = ensure(c->data, data_bytes))) return rc;
+  if ((rc = alloc_chains(c, cfg))) return rc;
+  const hipMemcpyKind kind = host_mem(c) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  HIP_TRY(hipMemcpyAsync(c->data.p, data, data_bytes, kind, c->stream));
+  const void *dq0;
+  if ((rc = stage_in(c, 0, q0, cb * d, &dq0))) return rc;
+  if ((rc = transpose(c, C, d, (const double *)dq0, (double *)c->q.p, true))) return rc;
+  if ((rc = reset_window(c, cfg))) return rc;
   InitArgs A{};
   A.C = C;
   A.fd = cfg->fd_rel_step;
@@ -906,35 +893,15 @@ int rsf_mcmc_replay_ssq(rsf_ctx *c, int64_t n_iters, const double *z, const doub
 }
 
 int rsf_mcmc_init_state(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q, const double *ssq, const double *std2, const double *V) {
+  int rc;
   if (!c || !cfg || !q || !ssq || !std2 || !V) return fail(RSF_ERR_INVALID, "rsf_mcmc_init_state: NULL argument");
-  if (cfg->size != sizeof(rsf_mcmc_config)) return fail(RSF_ERR_INVALID, "rsf_mcmc_init_state: struct size mismatch");
-  if (cfg->n_params != 1 && cfg->n_params != 3) return fail(RSF_ERR_UNSUPPORTED, "rsf_mcmc_init_state: n_params must be 1 or 3");
-  if (cfg->n_chains < 1) return fail(RSF_ERR_INVALID, "rsf_mcmc_init_state: n_chains < 1");
-  if (cfg->adapt_mode == RSF_ADAPT_REFERENCE_DICT && cfg->n_params != 1)
-    return fail(RSF_ERR_UNSUPPORTED, "rsf_mcmc_init_state: reference_dict adaptation is defined for 1 parameter only");
-  if (cfg->adapt_mode < 0 || cfg->adapt_mode > RSF_ADAPT_AM || (cfg->adapt_mode && cfg->adapt_interval < 2))
-    return fail(RSF_ERR_INVALID, "rsf_mcmc_init_state: bad adapt_mode / adapt_interval");
+  if ((rc = check_mcmc_config(cfg, "rsf_mcmc_init_state"))) return rc;
   DeviceGuard guard(c->device);
   if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_mcmc_init_state: cannot select device %d", c->device);
   const int d = cfg->n_params;
   const int64_t C = cfg->n_chains;
   const size_t cb = (size_t)C * sizeof(double);
-  int rc;
-  if ((rc = ensure(c->q, cb * d))) return rc;
-  if ((rc = ensure(c->ssq, cb))) return rc;
-  if ((rc = ensure(c->std2, cb))) return rc;
-  if ((rc = ensure(c->V, cb * d * d))) return rc;
-  if ((rc = ensure(c->wref, cb * d))) return rc;
-  if ((rc = ensure(c->wsum, cb * d))) return rc;
-  if ((rc = ensure(c->wsq, cb * d * d))) return rc;
-  if ((rc = ensure(c->wn, (size_t)C * sizeof(int32_t)))) return rc;
-  if (cfg->adapt_mode == RSF_ADAPT_REFERENCE_DICT) {  // the window's samples themselves: np.cov's own arithmetic needs them
-    if (cfg->adapt_interval > RSF_DICT_MAX_INTERVAL)
-      return fail(RSF_ERR_UNSUPPORTED, "reference_dict adaptation keeps at most %d samples per window", RSF_DICT_MAX_INTERVAL);
-    if ((rc = ensure(c->wbuf, cb * (size_t)cfg->adapt_interval))) return rc;
-    HIP_TRY(hipMemsetAsync(c->wbuf.p, 0, cb * (size_t)cfg->adapt_interval, c->stream));
-  }
-  if ((rc = ensure(c->stats, RSF_CNT_COUNT * sizeof(unsigned long long)))) return rc;
+  if ((rc = alloc_chains(c, cfg))) return rc;
   const hipMemcpyKind kind = host_mem(c) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   const void *dq, *dV;
   if ((rc = stage_in(c, 0, q, cb * d, &dq))) return rc;
@@ -943,11 +910,7 @@ int rsf_mcmc_init_state(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q,
   if ((rc = transpose(c, C, d * d, (const double *)dV, (double *)c->V.p, true))) return rc;
   HIP_TRY(hipMemcpyAsync(c->ssq.p, ssq, cb, kind, c->stream));
   HIP_TRY(hipMemcpyAsync(c->std2.p, std2, cb, kind, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->wref.p, c->q.p, cb * d, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->wsum.p, 0, cb * d, c->stream));
-  HIP_TRY(hipMemsetAsync(c->wsq.p, 0, cb * d * d, c->stream));
-  HIP_TRY(hipMemsetAsync(c->wn.p, 0, (size_t)C * sizeof(int32_t), c->stream));
-  HIP_TRY(hipMemsetAsync(c->stats.p, 0, RSF_CNT_COUNT * sizeof(unsigned long long), c->stream));
+  if ((rc = reset_window(c, cfg))) return rc;
   c->mc = *cfg;
   c->group_chains = 0;
   c->iters_done = 0;

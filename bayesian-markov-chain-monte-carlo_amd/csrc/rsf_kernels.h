@@ -46,10 +46,10 @@ constexpr int kD3Trip = 2;
 // kc is sized for tables of doubles (rsf_set_model); the float32 SAMPLER, whose tables are floats, has its own (kc32: nsteps
 // 4000 is one resident chunk of 48 KB there), the other float32 kernels share kc with the float64 init kernel of that mode.
 constexpr size_t kLdsBudget = 56 * 1024;
-// per-lane LDS slots (doubles) of the float64 RK4 sampler behind the table chunk: D = 3: the Cholesky factor's six; then the
-// chain's point, sigma^2, SSq and log u parked across the forward solve (mcmc_kernel)
-template <int D>
-constexpr int kParkSlots = (D == 3 ? 6 : 0) + D + 3;
+// LDS slots (doubles) of a sampler launch behind the table chunk, per lane: d = 3: the Cholesky factor's six per chain; the
+// float64 RK4 sampler adds the chain's point, sigma^2, SSq and log u parked across the forward solve (mcmc_kernel)
+constexpr int factor_slots(int d) { return d == 3 ? 6 : 0; }
+constexpr int park_slots(int d) { return factor_slots(d) + d + 3; }
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -342,7 +342,7 @@ __device__ __forceinline__ bool accept_test(double ratio, double log_u) {
 
 // The proposal of MCMC.py:497 from the chain's point, the lower Cholesky factor of its proposal covariance (row-major
 // lower triangle, D (D + 1) / 2 entries) and D standard normals — one definition, so that rsf_mcmc_propose announces
-// exactly the point the sampler kernel will evaluate.
+// exactly the point the sampler kernels will evaluate.
 template <int D, typename F>
 __device__ __forceinline__ void propose(const double (&q)[D], F factor, const double *z, double (&qn)[D]) {
   int e = 0;
@@ -411,7 +411,28 @@ struct McmcArgs {
   uint8_t *ta;
 };
 
-// INJECT (rsf_mcmc_replay_ssq): the proposals' sums of squares come from the caller — the chain logic alone, no tables, no solve.
+
+// Parts of the iteration shared by mcmc_kernel and mcmc_f32x2_kernel (with propose and accept_test above).  A replayed
+// variate is element row0 + lane of its [n][C] array: mcmc_kernel passes its lane's own row and lane 0.
+
+// accept / reject, MCMC.py:327-333
+template <bool REPLAY>
+__device__ __forceinline__ bool metropolis(double ssq, double ssqn, double std2, double lu) {
+  return accept_test(REPLAY ? 0.5 * (ssq - ssqn) / std2 : (0.5 * (ssq - ssqn)) * rsf::fm::rcp(std2), lu);
+}
+
+// sigma^2 Gibbs update with the post-accept SSq, MCMC.py:158-160
+template <bool REPLAY>
+__device__ __forceinline__ double gibbs_std2(const McmcArgs &A, uint64_t gid, uint32_t it, int64_t row0, unsigned lane, double std2,
+                                             double ssq) {
+  const double bval = 0.5 * (A.n0 * std2 + ssq);
+  const double g = REPLAY ? (A.g + row0)[lane] : rsf::gamma_draw(A.seed, gid, it, A.gd, A.gc);
+  return REPLAY ? bval / g : bval * rsf::fm::rcp(g);
+}
+
+// The float64 sampler.  INJECT (rsf_mcmc_replay_ssq): the proposals' sums of squares come from the caller — the chain logic
+// alone, no tables, no solve.  Only here: the run-ahead over out-of-bounds proposals (kProposalTries), the uniform drawn before
+// the solve for the early-rejection bound thr, the chain state parked in LDS across the solve (kPark), WaveCounters.
 template <int D, bool DAMP, bool REPLAY, int MODE, bool INJECT = false>
 __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, McmcArgs A) {
   static_assert(MODE == RK4_F64 || MODE == DOP853, "the float32 sampler is mcmc_f32x2_kernel (two chains per lane)");
@@ -441,7 +462,6 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
   // registers for the launch: seven of them held across every solve, also when nothing adapts — the BASELINE case — and
   // with them the kernel spilled loop-invariant values whose reload, at the top of every solve, waited for the trace row
   // just stored: vector stores and scratch loads share one counter.)
-  constexpr bool kWinRegs = false;
   double *lcs = lds + A.lc_off + t;  // D = 3: element e of this lane's factor at lcs[e * blockDim.x]
   double V1 = 0.0;                             // D = 1: the proposal variance
   double wr[D], ws[D], wq[D * D];
@@ -482,7 +502,6 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
     for (int e = 0; e < D * D; ++e) at(A.wsq, e)[t] = wq[e];
     at(A.wn, 0)[t] = wn;
   };
-  if (kWinRegs && A.adapt_mode != RSF_ADAPT_NONE && valid) load_window(t);
   // statistics (rsf_mcmc_counters): wave-uniform popcounts and step counts — scalar registers, nothing per lane — added to
   // the ctx totals by one lane every kFlushEvery proposals (32-bit accumulators cannot overflow in between)
   WaveCounters cnt;
@@ -497,8 +516,8 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
   // (per-lane slots behind the table chunk; D = 3: behind the Cholesky factor's six) instead of in registers the
   // integrator needs — the spills per proposal these kernels had otherwise.
   constexpr bool kPark = MODE == RK4_F64;  // (the DOP853 kernel allocates worse with it: measured, tools/one_kernel.sh)
-  constexpr int kSlotQ = D == 3 ? 6 : 0, kSlotStd2 = kSlotQ + D, kSlotSsq = kSlotStd2 + 1, kSlotLu = kSlotSsq + 1;
-  static_assert(kSlotLu + 1 == kParkSlots<D>, "rsf_hip.hip sizes the launch's LDS with kParkSlots");
+  constexpr int kSlotQ = factor_slots(D), kSlotStd2 = kSlotQ + D, kSlotSsq = kSlotStd2 + 1, kSlotLu = kSlotSsq + 1;
+  static_assert(kSlotLu + 1 == park_slots(D), "rsf_hip.hip sizes the launch's LDS with park_slots");
 
   // Every lane walks its OWN chain through iterations 0 .. n_iters-1 (nl: the lane's next one).  A round of the loop below
   // gives every lane that has no proposal in hand its next one; a proposal outside the prior box is a finished iteration
@@ -634,7 +653,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
     // accept / reject, MCMC.py:327-333
     bool accept = false;
     if (solved) {
-      accept = accept_test(REPLAY ? 0.5 * (ssq - ssqn) / std2 : (0.5 * (ssq - ssqn)) * rsf::fm::rcp(std2), lu);
+      accept = metropolis<REPLAY>(ssq, ssqn, std2, lu);
       if (accept) {
         ssq = ssqn;
 #pragma unroll
@@ -646,9 +665,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
     cnt.oob += (uint32_t)__builtin_popcountll(rsf::ballot(oob));
     if (solved || oob) {
       // sigma^2 Gibbs update with the post-accept SSq, MCMC.py:158-160
-      const double bval = 0.5 * (A.n0 * std2 + ssq);
-      const double g = REPLAY ? A.g[row] : rsf::gamma_draw(A.seed, gid, it, A.gd, A.gc);
-      std2 = REPLAY ? bval / g : bval * rsf::fm::rcp(g);
+      std2 = gibbs_std2<REPLAY>(A, gid, it, row, 0, std2, ssq);
       if (A.tq) {
 #pragma unroll
         for (int p = 0; p < D; ++p) A.tq[row * D + p] = q[p];
@@ -657,7 +674,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
       if (A.ta) A.ta[row] = accept ? 1 : 0;
       // adaptation, MCMC.py:200-204, 523-527
       if (A.adapt_mode != RSF_ADAPT_NONE) {
-        if (!kWinRegs) load_window(tl);
+        load_window(tl);
 #pragma unroll
         for (int p = 0; p < D; ++p) {
           ws[p] += q[p] - wr[p];
@@ -689,7 +706,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
           }
           // (am keeps its sums: the covariance of the whole history.  reference_dict forms its window from wbuf and ignores them.)
         }
-        if (!kWinRegs) store_window(tl);
+        store_window(tl);
       }
       ++nl;
       have = false;
@@ -703,7 +720,6 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
     if constexpr (D == 1) at(A.V, 0)[t] = V1;
     at(A.ssq, 0)[t] = ssq;
     at(A.std2, 0)[t] = std2;
-    if (kWinRegs && A.adapt_mode != RSF_ADAPT_NONE) store_window(t);
   }
   cnt.flush(A.stats);
 }
@@ -744,7 +760,11 @@ __global__ void __launch_bounds__(kMaxBlock) propose_kernel(ProposeArgs A) {
 // solve advances two chains per packed instruction (rsf_device_f32.h, solve32x2).  Chain slot s of lane t of workgroup w
 // is chain w * 2 * blockDim + s * blockDim + t, so that both slots read and write coalesced runs.  (A second kernel
 // rather than a chains-per-lane parameter of mcmc_kernel: written that way, the float64 kernels — which sit at 252-256
-// registers — came out with 12-44 B of scratch per lane.)  The sampler logic itself stays float64.
+// registers — came out with 12-44 B of scratch per lane.)  The sampler logic itself stays float64, with mcmc_kernel's
+// propose, metropolis and gibbs_std2.  Only here: the uniform is drawn after the solve, the one-parameter window stays in
+// registers, counters are reduced once (rsf::wave_sum).  The draws, box test, trace row and adaptation are still written
+// out in both kernels: as helpers they grew this kernel's spills (d = 3: 512 -> 528-1008 B, the adaptation's partly inside
+// the trip loop) or mcmc_kernel's SGPR spills in its solve loops (HISTORY.md: one definition of the chain logic).
 // Per-chain sampler state of one slot:
 template <int D>
 struct Chain {
@@ -865,16 +885,9 @@ mcmc_f32x2_kernel(Consts K, McmcArgs A) {  // (the registers above that count: t
       if constexpr (D == 1) {
         double Lc;
         rsf::chol_lower<1>(&c.V1, &Lc);  // sqrt(V), or 0 where V is not positive
-        qn[s][0] = c.q[0] + Lc * z[0];
+        propose<1>(c.q, [&](int) { return Lc; }, z, qn[s]);
       } else {
-        int e = 0;
-#pragma unroll
-        for (int p = 0; p < D; ++p) {
-          double acc = c.q[p];
-#pragma unroll
-          for (int r = 0; r <= p; ++r) acc += lcs[((e++) * NC + s) * blockDim.x] * z[r];
-          qn[s][p] = acc;
-        }
+        propose<D>(c.q, [&](int e) { return lcs[(e * NC + s) * blockDim.x]; }, z, qn[s]);
       }
       inb[s] = c.valid;
 #pragma unroll
@@ -906,10 +919,8 @@ mcmc_f32x2_kernel(Consts K, McmcArgs A) {  // (the registers above that count: t
           rsf::draw_words(A.seed, c.gid, it, rsf::SLOT_U, w);
           u = rsf::u53(w[0], w[1]);
         }
-        // (replaying recorded variates follows the reference's arithmetic to the last bit: IEEE division, libm-grade log;
-        //  the sampler proper uses the kernel's own reciprocal and log — the same value to ~1 ulp)
-        accept = accept_test(REPLAY ? 0.5 * (c.ssq - ssqn[s]) / c.std2 : (0.5 * (c.ssq - ssqn[s])) * rsf::fm::rcp(c.std2),
-                             REPLAY ? log(u) : rsf::rng_log(u));
+        // (log u as in mcmc_kernel)
+        accept = metropolis<REPLAY>(c.ssq, ssqn[s], c.std2, REPLAY ? log(u) : rsf::rng_log(u));
         ++n_eval;
         if (!isfinite(ssqn[s])) ++n_nonfinite;
         if (accept) {
@@ -921,9 +932,7 @@ mcmc_f32x2_kernel(Consts K, McmcArgs A) {  // (the registers above that count: t
       }
       // ---- sigma^2 Gibbs update with the post-accept SSq, MCMC.py:158-160 ----
       if (c.valid) {
-        const double bval = 0.5 * (A.n0 * c.std2 + c.ssq);
-        const double g = REPLAY ? (A.g + row0)[tl] : rsf::gamma_draw(A.seed, c.gid, it, A.gd, A.gc);
-        c.std2 = REPLAY ? bval / g : bval * rsf::fm::rcp(g);
+        c.std2 = gibbs_std2<REPLAY>(A, c.gid, it, row0, tl, c.std2, c.ssq);
         if (A.tq) {
 #pragma unroll
           for (int p = 0; p < D; ++p) (A.tq + row0 * D)[tl * D + p] = c.q[p];

@@ -184,10 +184,15 @@ def test_generated_trip_is_current():
 def test_float32_trip_owns_its_private_register_file():
     """The float32 sampler's assembly trip keeps constants, tables and temporaries in the registers above RSF_F32_TRIP_COMPILER_VGPRS (v[154:255]) across statements.  That is
     sound only while compiled code never touches those registers, the kernel uses no AGPR, nothing spills inside the trip loop
-    and the trip's 8-byte instruction stream starts on an 8-byte boundary: tools/check_private_file.py compiles one
-    instantiation (no GPU) and checks all four in the ISA."""
+    and the trip's 8-byte instruction stream starts on an 8-byte boundary: tools/check_private_file.py compiles an
+    instantiation (no GPU) and checks all four in the ISA — here every instantiation the library builds, since register
+    allocation, and with it where spills land, differs between them."""
     import subprocess
     import sys
 
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_private_file.py")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr[-2000:]
+    insts = [f"mcmc_f32x2_kernel<{d}, {damp}, {replay}>" for d in (1, 3) for damp in ("false", "true") for replay in ("false", "true")]
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "check_private_file.py"), inst], stdout=subprocess.PIPE,
+                              stderr=subprocess.PIPE, text=True) for inst in insts]
+    for inst, p in zip(insts, procs):
+        stdout, stderr = p.communicate(timeout=600)
+        assert p.returncode == 0 and stdout.strip().endswith("ok"), inst + ": " + stdout + stderr[-2000:]

@@ -29,7 +29,7 @@ def main():
         if (a, i) in seen:
             continue
         seen.add((a, i))
-        ins = [x.split()[0] for x in body[a:i + 1] if x.startswith("\t") and not x.strip().startswith((";", "."))]
+        ins = [x.split()[0] for x in body[a:i + 1] if x.startswith("\t") and x.strip() and not x.strip().startswith((";", "."))]
         c = collections.Counter(ins)
         valu = sum(v for k, v in c.items() if k.startswith("v_"))
         if lo <= valu <= hi:
