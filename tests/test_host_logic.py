@@ -238,6 +238,43 @@ def test_sample_batched_host_logic(pkg, model, golden, monkeypatch):
         mc.sample_batched(8, seed=4, mem="host", thin=0)
 
 
+def test_sample_batched_freezes_the_adaptive_proposal_after_burn_in(pkg, model, golden, monkeypatch):
+    """d = 3 under "am": the proposal adapts during burn-in and is frozen from there on (oracle engine injected): the launch
+    boundaries do not matter, the post-burn chains are the non-adaptive sampler continued from the burn-in's last state with
+    its adapted covariance, and the statistics cover both phases."""
+    import sys
+
+    mcmc_mod = sys.modules[pkg.MCMC.__module__]
+    g = golden.npz("ssq")
+    lib = model._engine.lib
+    engines = []
+
+    def make(mem="host", device=-1, **k):
+        engines.append(pkg.Engine(lib=lib))
+        return engines[-1]
+
+    monkeypatch.setattr(mcmc_mod, "Engine", make)
+    box = [["Uniform", 0.0, 1e4], ["Uniform", 0.005, 0.02], ["Uniform", 0.005, 0.03]]
+    mc = pkg.MCMC(model, g["data"], 1000.0, box, [1600.0, 0.008, 0.022], nsamples=40, lstm_model=None)
+    one = mc.sample_batched(8, seed=4, mem="host")
+    many = mc.sample_batched(8, seed=4, mem="host", iters_per_launch=7)
+    np.testing.assert_array_equal(one.samples, many.samples)
+    assert one.stats["iters_done"] == 40 and one.stats["evaluated"] <= 40 * 8
+    # the same by hand: 20 adaptive iterations, then the fixed proposal it ended with
+    with pkg.Engine(lib=lib) as e:
+        model.engine = lambda: e
+        e.set_model(model, 1)
+        mc._init_chains(e, np.tile([1600.0, 0.008, 0.022], (8, 1)), seed=4)
+        tq, _, _ = e.mcmc_run(20)
+        state = e.get_state()
+        mc._init_chains(e, state[0], seed=(4 * 0x9E3779B97F4A7C15 + 1) % 2 ** 64, adapt_mode="none")
+        e.set_state(*state)
+        tq2, _, _ = e.mcmc_run(20)
+        assert np.array_equal(e.get_state()[3], state[3])  # frozen: the burn-in's covariance, unchanged by the second phase
+    del model.engine
+    np.testing.assert_array_equal(one.samples, np.concatenate([tq[19:], tq2]))
+
+
 def test_flat_module_imports_like_the_reference(tmp_path):
     """The reference imports its modules flat (main.py:44-46, RSF.py:1-4, MCMC.py:1).  With the package directory first on
     sys.path the very same statements must work (fresh interpreter: nothing of the package pre-imported), and the objects
