@@ -15,6 +15,7 @@
 #include <cstring>
 #include <functional>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rsf_abi.h"
@@ -54,12 +55,34 @@ struct DevBuf {
 
 struct DeviceGuard {  // run on the ctx device, restore the caller's current device afterwards
   int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-    if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
+  DeviceGuard() = default;
+  explicit DeviceGuard(int dev) { (void)select(dev); }  // unchecked: rsf_destroy, rsf_comm_destroy (free what can be freed), later loops of *_all
+  bool select(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) return false;
+    return prev == dev || hipSetDevice(dev) == hipSuccess;
   }
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// Staging slots of RSF_MEM_HOST callers (rsf_ctx::stage), named by what each holds in the call that uses it.  The rule that
+// makes sharing them safe: within one ABI call every array the call stages has a slot of its own (the names of one line
+// below are distinct slots); a slot is reused only ACROSS calls, and every RSF_MEM_HOST call ends in finish()'s synchronise,
+// so no copy of an earlier call is in flight when the next one writes the slot.
+enum Slot : int {
+  // rsf_mcmc_run / _replay / _replay_ssq: supplied variates and sums of squares in, trace rows out
+  SLOT_Z, SLOT_U, SLOT_G, SLOT_TQ, SLOT_TS, SLOT_TA, SLOT_SSQ_NEW, SLOT_COUNT,
+  // the drained run's second trace set lies in the replay inputs' slots: a drained run stages none (run_mcmc_drained checks it)
+  SLOT_TQ_B = SLOT_Z, SLOT_TS_B = SLOT_U, SLOT_TA_B = SLOT_G,
+  // rsf_mcmc_propose: z in SLOT_Z
+  SLOT_Q_NEW = SLOT_TQ, SLOT_IN_BOUNDS = SLOT_TA,
+  // rsf_forward_batch
+  SLOT_DC = SLOT_Z, SLOT_A = SLOT_U, SLOT_B = SLOT_G, SLOT_DATA = SLOT_TQ, SLOT_SSQ_OUT = SLOT_TS, SLOT_ACC_OUT = SLOT_TA,
+  // rsf_mcmc_init (q0 in SLOT_Q), rsf_mcmc_get_state / _set_state / _init_state
+  SLOT_Q = SLOT_Z, SLOT_V = SLOT_U,
+  // rsf_pool_summary / _kde / _histogram, rsf_diag_partials, rsf_diag_rank_prepare: the samples or the trace in SLOT_X
+  SLOT_X = SLOT_Z, SLOT_GRID = SLOT_U, SLOT_POOL_OUT = SLOT_G,
+  // rsf_pool_allgather[_all] / _allreduce_sum[_all] (the reduction is in place in SLOT_SEND)
+  SLOT_SEND = SLOT_Z, SLOT_RECV = SLOT_U,
 };
 
 }  // namespace
@@ -86,7 +109,7 @@ struct rsf_ctx {
   int64_t group_chains = 0;  // chains per observation group (0: one series)
   int64_t iters_done = 0;
   // staging for RSF_MEM_HOST callers
-  DevBuf stage[8];
+  DevBuf stage[SLOT_COUNT];
   // drain pipeline of rsf_mcmc_run for RSF_MEM_HOST callers: the trace of launch k is copied out on its own stream
   // while launch k+1 computes
   hipStream_t copy_stream = nullptr;
@@ -107,7 +130,8 @@ struct rsf_ctx {
   // posterior-pool communicator (one process per GPU)
   int32_t world = 0, rank = 0;  // world 0: rsf_comm_init not called
   ncclComm_t comm = nullptr;
-  DevBuf pool;  // workspace of the posterior post-processing kernels
+  DevBuf pool;    // workspace of the posterior post-processing kernels: the moments' partials
+  DevBuf poolws;  // ... and the KDE's per-workgroup densities or the histogram's integer counts
   DevBuf diag;  // workspace of the convergence diagnostics (rsf_diag_partials)
   DevBuf rankws;  // rank workspace (rsf_diag_rank_prepare): the four derived series, then the sort buffers
   int64_t rank_n = 0, rank_C = 0;  // shape of the prepared trace; rank_d 0 = nothing prepared
@@ -134,27 +158,27 @@ void release(DevBuf &b) {
 bool host_mem(const rsf_ctx *c) { return c->cfg.mem_space == RSF_MEM_HOST; }
 
 // input array: device pointer the kernels may read (staged copy for host callers)
-int stage_in(rsf_ctx *c, int slot, const void *src, size_t bytes, const void **dev) {
+template <class T> int stage_in(rsf_ctx *c, Slot slot, const T *src, size_t bytes, const T **dev) {
   if (!src) { *dev = nullptr; return RSF_OK; }
   if (!host_mem(c)) { *dev = src; return RSF_OK; }
   int rc = ensure(c->stage[slot], bytes);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(c->stage[slot].p, src, bytes, hipMemcpyHostToDevice, c->stream));
-  *dev = c->stage[slot].p;
+  *dev = (const T *)c->stage[slot].p;
   return RSF_OK;
 }
 
 // output array: device pointer the kernels may write
-int stage_out(rsf_ctx *c, int slot, void *dst, size_t bytes, void **dev) {
+template <class T> int stage_out(rsf_ctx *c, Slot slot, T *dst, size_t bytes, T **dev) {
   if (!dst) { *dev = nullptr; return RSF_OK; }
   if (!host_mem(c)) { *dev = dst; return RSF_OK; }
   int rc = ensure(c->stage[slot], bytes);
   if (rc) return rc;
-  *dev = c->stage[slot].p;
+  *dev = (T *)c->stage[slot].p;
   return RSF_OK;
 }
 
-int copy_back(rsf_ctx *c, int slot, void *dst, size_t bytes) {
+int copy_back(rsf_ctx *c, Slot slot, void *dst, size_t bytes) {
   if (!dst || !host_mem(c)) return RSF_OK;
   HIP_TRY(hipMemcpyAsync(dst, c->stage[slot].p, bytes, hipMemcpyDeviceToHost, c->stream));
   return RSF_OK;
@@ -166,7 +190,26 @@ int finish(rsf_ctx *c) {  // host callers get synchronous semantics
   return RSF_OK;
 }
 
-Consts make_consts(const rsf_ctx *c, const double *data) {
+// What an entry point that touches the device begins with: its arguments (a NULL ctx, and whatever else the caller folds
+// into args_ok and names in `what`), the state it needs, and the ctx's device selected for as long as the caller's guard
+// lives.  fn: the entry point the messages name.
+enum Need { NEED_NOTHING, NEED_MODEL, NEED_CHAINS, NEED_COMM };
+
+int enter(DeviceGuard &guard, rsf_ctx *c, const char *fn, Need need, bool args_ok = true, const char *what = "NULL ctx") {
+  static const char *const first[] = {nullptr, "rsf_set_model", "rsf_mcmc_init", "rsf_comm_init"};
+  if (!c || !args_ok) return fail(RSF_ERR_INVALID, "%s: %s", fn, what);
+  const bool have[] = {true, c->have_model, c->have_chains, c->world != 0};
+  if (!have[need]) return fail(RSF_ERR_STATE, "%s: call %s first", fn, first[need]);
+  if (!guard.select(c->device)) return fail(RSF_ERR_DEVICE, "%s: cannot select device %d", fn, c->device);
+  return RSF_OK;
+}
+
+// ... as the first statement of the entry point itself, which it names; `guard` lives to the end of the enclosing block
+#define RSF_ENTER(c, ...)                                            \
+  DeviceGuard guard;                                                 \
+  if (int rc_ = enter(guard, c, __func__, __VA_ARGS__)) return rc_
+
+Consts make_consts(const rsf_ctx *c, const double *data, int64_t group_chains = 0) {
   Consts K{};
   K.mu_ref = c->m.mu_ref; K.V_ref = c->m.V_ref; K.k1 = c->m.k1; K.mu0 = c->m.mu_t_zero;
   K.a_def = c->m.a; K.b_def = c->m.b;
@@ -179,7 +222,7 @@ Consts make_consts(const rsf_ctx *c, const double *data) {
   K.vl = (const double *)c->vl.p;
   K.data = data;
   K.nout = c->nout; K.S = c->m.substeps; K.kc = c->kc; K.nchunks = c->nchunks;
-  K.group_chains = 0;
+  K.group_chains = group_chains;
   return K;
 }
 
@@ -208,11 +251,75 @@ size_t mcmc_table_bytes(const rsf_ctx *c) {
   return (floats * sizeof(float) + 15) & ~(size_t)15;
 }
 
-// the sampler's kernel constants: make_consts with the chunking the sampler kernel of this mode uses
-Consts make_sampler_consts(const rsf_ctx *c, const double *data) {
-  Consts K = make_consts(c, data);
+// the sampler's kernel constants: the chains' observations and groups, and the chunking the sampler kernel of this mode uses
+Consts make_sampler_consts(const rsf_ctx *c) {
+  Consts K = make_consts(c, (const double *)c->data.p, c->group_chains);
   if (mode_of(c) == RK4_F32) { K.kc = c->kc32; K.nchunks = c->nchunks32; }
   return K;
+}
+
+// ---- kernel selection -----------------------------------------------------------------------------------------------
+// A runtime selector becomes a template argument: with<V0, V1, ...>(v, f) hands f the one of the listed values that equals
+// v (the last if none does) as a std::integral_constant.  Every *_fn below returns the TYPED pointer of one instantiation
+// (the same address on every call: the replay graph compares it), and asks damped() itself with the integrator its kernel
+// runs.  Only combinations that are launched are named: naming one instantiates it.
+template <auto V0, auto... Vs, class F> auto with(int v, F f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<decltype(V0), V0>{});
+  else return v == (int)V0 ? f(std::integral_constant<decltype(V0), V0>{}) : with<Vs...>(v, f);
+}
+
+using ForwardFn = void (*)(Consts, int64_t, const double *, const double *, const double *, double *, double *);
+using SamplerFn = void (*)(Consts, McmcArgs);
+
+ForwardFn forward_fn(const rsf_ctx *c, bool want_ssq, bool want_acc) {  // NULL: nothing requested, nothing to launch
+  return with<RK4_F32, DOP853, RK4_F64>(mode_of(c), [&](auto MODE) {
+    return with<true, false>(damped(c, MODE), [&](auto DAMP) -> ForwardFn {
+      if (want_ssq && want_acc) return forward_kernel<DAMP, true, true, MODE>;
+      if (want_ssq) return forward_kernel<DAMP, true, false, MODE>;
+      return want_acc ? forward_kernel<DAMP, false, true, MODE> : nullptr;
+    });
+  });
+}
+
+// rsf_mcmc_init's solve with its sensitivities, void (*)(Consts, InitArgs): DOP853, or the float64 RK4 — in the float32 mode as well
+auto init_fn(const rsf_ctx *c, int d) {
+  const bool dop = mode_of(c) == DOP853;
+  return with<1, 3>(d, [&](auto D) {
+    return with<true, false>(damped(c, dop ? DOP853 : RK4_F64), [&](auto DAMP) { return dop ? init_dp_kernel<D, DAMP> : init_kernel<D, DAMP>; });
+  });
+}
+
+auto ssq32_fn(const rsf_ctx *c, int d) {  // void (*)(Consts, int64_t C, const double *q, double *ssq)
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F32), [&](auto DAMP) { return ssq32_kernel<D, DAMP>; }); });
+}
+
+// INJECT (rsf_mcmc_replay_ssq, any mode): the chain logic alone, which has no solve to damp
+SamplerFn sampler_fn(const rsf_ctx *c, bool replay, bool inject) {
+  return with<1, 3>(c->mc.n_params, [&](auto D) -> SamplerFn {
+    if (inject) return mcmc_kernel<D, false, true, RK4_F64, true>;
+    return with<RK4_F32, DOP853, RK4_F64>(mode_of(c), [&](auto MODE) {
+      return with<true, false>(damped(c, MODE), [&](auto DAMP) {
+        return with<true, false>(replay, [&](auto REPLAY) -> SamplerFn {
+          if constexpr (MODE == RK4_F32) return mcmc_f32x2_kernel<D, DAMP, REPLAY>;
+          else return mcmc_kernel<D, DAMP, REPLAY, MODE>;
+        });
+      });
+    });
+  });
+}
+
+auto propose_fn(int d) { return with<1, 3>(d, [](auto D) { return propose_kernel<D>; }); }        // void (*)(ProposeArgs)
+auto diag_chain_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return diag_chain_kernel<D>; }); }  // 1 <= d <= RSF_MAX_PARAMS
+
+// One launch on the ctx stream.  The parameter types come from the kernel's pointer alone, and the call's arguments are
+// converted to them before their addresses are taken: a wrong count, order or type does not compile.
+template <class T> struct as_declared { using type = T; };
+
+template <class... P>
+int launch(rsf_ctx *c, void (*fn)(P...), unsigned grid, unsigned block, size_t lds, typename as_declared<P>::type... a) {
+  void *args[] = {(void *)&a...};
+  HIP_TRY(hipLaunchKernel((const void *)fn, dim3(grid), dim3(block), args, lds, c->stream));
+  return RSF_OK;
 }
 
 // The sampler kernel of a launch, and its grid and LDS: the table chunk (mcmc_table_bytes), and behind it per-lane slots
@@ -220,37 +327,19 @@ Consts make_sampler_consts(const rsf_ctx *c, const double *data) {
 // Cholesky factor, one per chain of the lane).  INJECT (rsf_mcmc_replay_ssq, any mode): the chain logic alone on supplied
 // sums of squares — no tables, one chain per lane, its slots at the base of LDS.
 struct SamplerLaunch {
-  const void *fn;
+  SamplerFn fn;
   unsigned grid;
   size_t lds;
   int32_t lc_off;  // McmcArgs::lc_off: the slots' offset in doubles
 };
 
-template <int D, bool DAMP>
-const void *sampler_kernel(int mode, bool replay, bool inject) {
-  if (inject) return (const void *)mcmc_kernel<D, false, true, RK4_F64, true>;
-  switch (mode) {
-    case RK4_F32: return replay ? (const void *)mcmc_f32x2_kernel<D, DAMP, true> : (const void *)mcmc_f32x2_kernel<D, DAMP, false>;
-    case DOP853: return replay ? (const void *)mcmc_kernel<D, DAMP, true, DOP853> : (const void *)mcmc_kernel<D, DAMP, false, DOP853>;
-    default: return replay ? (const void *)mcmc_kernel<D, DAMP, true, RK4_F64> : (const void *)mcmc_kernel<D, DAMP, false, RK4_F64>;
-  }
-}
-
 SamplerLaunch sampler_launch(const rsf_ctx *c, bool replay, bool inject) {
   const int d = c->mc.n_params, mode = inject ? RK4_F64 : mode_of(c), nc = inject ? 1 : chains_per_lane(c);
-  const bool damp = damped(c, mode_of(c));
-  const void *fn = d == 1 ? (damp ? sampler_kernel<1, true>(mode, replay, inject) : sampler_kernel<1, false>(mode, replay, inject))
-                          : (damp ? sampler_kernel<3, true>(mode, replay, inject) : sampler_kernel<3, false>(mode, replay, inject));
   const size_t table = inject ? 0 : mcmc_table_bytes(c);
   const size_t slots = mode == RK4_F64 ? park_slots(d) : factor_slots(d) * nc;
   const int64_t per = (int64_t)c->block * nc;
-  return {fn, (unsigned)((c->mc.n_chains + per - 1) / per), table + slots * sizeof(double) * (size_t)c->block, (int32_t)(table / sizeof(double))};
-}
-
-int launch_sampler(rsf_ctx *c, const SamplerLaunch &L, Consts K, McmcArgs A) {
-  void *args[2] = {&K, &A};
-  HIP_TRY(hipLaunchKernel(L.fn, dim3(L.grid), dim3(c->block), args, L.lds, c->stream));
-  return RSF_OK;
+  return {sampler_fn(c, replay, inject), (unsigned)((c->mc.n_chains + per - 1) / per), table + slots * sizeof(double) * (size_t)c->block,
+          (int32_t)(table / sizeof(double))};
 }
 
 // [n][d] (the C ABI's layout) <-> [d][n] (the kernels' structure of arrays); both device pointers, on the ctx stream
@@ -260,6 +349,18 @@ int transpose(rsf_ctx *c, int64_t n, int d, const double *src, double *dst, bool
     return RSF_OK;
   }
   hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((n + kMaxBlock - 1) / kMaxBlock)), dim3(kMaxBlock), 0, c->stream, n, d, src, dst, to_soa);
+  return RSF_OK;
+}
+
+// the caller's q [C][d] and V [C][d*d] into the chain state; a NULL one stays as it is
+int put_q_V(rsf_ctx *c, int64_t C, int d, const double *q, const double *V) {
+  const size_t cb = (size_t)C * sizeof(double);
+  const double *dq, *dV;
+  int rc;
+  if ((rc = stage_in(c, SLOT_Q, q, cb * d, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_V, V, cb * d * d, &dV))) return rc;
+  if (q && (rc = transpose(c, C, d, dq, (double *)c->q.p, true))) return rc;
+  if (V && (rc = transpose(c, C, d * d, dV, (double *)c->V.p, true))) return rc;
   return RSF_OK;
 }
 
@@ -281,19 +382,23 @@ int run_mcmc_drained(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcAr
     HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     for (auto &e : c->ev_done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  const int slot_q[2] = {3, 0}, slot_s[2] = {4, 1}, slot_a[2] = {5, 2};
+  if (A.z || A.u || A.g || A.ssq_new)  // set 1 lies in their slots (Slot)
+    return fail(RSF_ERR_STATE, "rsf_mcmc_run: a drained run cannot take supplied variates or sums of squares");
+  const Slot slot_q[2] = {SLOT_TQ, SLOT_TQ_B}, slot_s[2] = {SLOT_TS, SLOT_TS_B}, slot_a[2] = {SLOT_TA, SLOT_TA_B};
+  double *dq[2], *ds[2];
+  uint8_t *da[2];
   int rc;
   for (int b = 0; b < 2; ++b) {
-    if (tq && (rc = ensure(c->stage[slot_q[b]], (size_t)per * C * d * sizeof(double)))) return rc;
-    if (ts && (rc = ensure(c->stage[slot_s[b]], (size_t)per * C * sizeof(double)))) return rc;
-    if (ta && (rc = ensure(c->stage[slot_a[b]], (size_t)per * C))) return rc;
+    if ((rc = stage_out(c, slot_q[b], tq, (size_t)per * C * d * sizeof(double), &dq[b]))) return rc;
+    if ((rc = stage_out(c, slot_s[b], ts, (size_t)per * C * sizeof(double), &ds[b]))) return rc;
+    if ((rc = stage_out(c, slot_a[b], ta, (size_t)per * C, &da[b]))) return rc;
   }
   auto drain = [&](int b, int64_t first, int64_t n) -> int {
     const size_t r0 = (size_t)first * C, rn = (size_t)n * C;
     HIP_TRY(hipStreamWaitEvent(c->copy_stream, c->ev_done[b], 0));
-    if (tq) HIP_TRY(hipMemcpyAsync(tq + r0 * d, c->stage[slot_q[b]].p, rn * d * sizeof(double), hipMemcpyDeviceToHost, c->copy_stream));
-    if (ts) HIP_TRY(hipMemcpyAsync(ts + r0, c->stage[slot_s[b]].p, rn * sizeof(double), hipMemcpyDeviceToHost, c->copy_stream));
-    if (ta) HIP_TRY(hipMemcpyAsync(ta + r0, c->stage[slot_a[b]].p, rn, hipMemcpyDeviceToHost, c->copy_stream));
+    if (tq) HIP_TRY(hipMemcpyAsync(tq + r0 * d, dq[b], rn * d * sizeof(double), hipMemcpyDeviceToHost, c->copy_stream));
+    if (ts) HIP_TRY(hipMemcpyAsync(ts + r0, ds[b], rn * sizeof(double), hipMemcpyDeviceToHost, c->copy_stream));
+    if (ta) HIP_TRY(hipMemcpyAsync(ta + r0, da[b], rn, hipMemcpyDeviceToHost, c->copy_stream));
     HIP_TRY(hipStreamSynchronize(c->copy_stream));  // the staging set is free again, the rows are in the caller's arrays
     return RSF_OK;
   };
@@ -303,10 +408,8 @@ int run_mcmc_drained(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcAr
   while (done < n_iters) {
     const int64_t n = std::min(per, n_iters - done);
     A.n_iters = n; A.iter_base = base + done;
-    A.tq = tq ? (double *)c->stage[slot_q[b]].p : nullptr;
-    A.ts = ts ? (double *)c->stage[slot_s[b]].p : nullptr;
-    A.ta = ta ? (uint8_t *)c->stage[slot_a[b]].p : nullptr;
-    if ((rc = launch_sampler(c, L, K, A))) return rc;
+    A.tq = dq[b]; A.ts = ds[b]; A.ta = da[b];
+    if ((rc = launch(c, L.fn, L.grid, c->block, L.lds, K, A))) return rc;
     HIP_TRY(hipEventRecord(c->ev_done[b], c->stream));
     if (prev_n && (rc = drain(b ^ 1, prev_first, prev_n))) return rc;
     prev_first = done; prev_n = n;
@@ -341,7 +444,7 @@ int run_replay_graph(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcAr
   const size_t in_bytes = (C * d + 2 * C) * sizeof(double), out_bytes = (C * d + C) * sizeof(double) + C;
   const size_t out_off = (in_bytes + 255) & ~(size_t)255, total = out_off + ((out_bytes + 255) & ~(size_t)255);
   char *hb = (char *)G.host, *db = (char *)G.dev;
-  const bool rebuild = !G.exec || G.C != A.C || G.d != d || G.fn != L.fn || G.lds != L.lds || G.block != c->block;
+  const bool rebuild = !G.exec || G.C != A.C || G.d != d || G.fn != (const void *)L.fn || G.lds != L.lds || G.block != c->block;
   if (rebuild) {
     release_replay_graph(c);
     HIP_TRY(hipHostMalloc(&G.host, total, hipHostMallocDefault));
@@ -355,7 +458,7 @@ int run_replay_graph(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcAr
   Consts Kc = K;
   void *params[2] = {&Kc, &A};
   hipKernelNodeParams kp{};
-  kp.func = const_cast<void *>(L.fn);
+  kp.func = (void *)L.fn;
   kp.gridDim = dim3(L.grid); kp.blockDim = dim3(c->block);
   kp.sharedMemBytes = (unsigned)L.lds;
   kp.kernelParams = params;
@@ -367,7 +470,7 @@ int run_replay_graph(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcAr
     HIP_TRY(hipGraphAddKernelNode(&G.kernel, G.graph, &h2d, 1, &kp));
     HIP_TRY(hipGraphAddMemcpyNode1D(&d2h, G.graph, &G.kernel, 1, hb + out_off, db + out_off, out_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0));
-    G.C = A.C; G.d = d; G.fn = L.fn; G.lds = L.lds; G.block = c->block;
+    G.C = A.C; G.d = d; G.fn = (const void *)L.fn; G.lds = L.lds; G.block = c->block;
   } else {
     HIP_TRY(hipGraphExecKernelNodeSetParams(G.exec, G.kernel, &kp));
   }
@@ -385,21 +488,10 @@ int run_replay_graph(rsf_ctx *c, const SamplerLaunch &L, const Consts &K, McmcAr
   return RSF_OK;
 }
 
-int run_mcmc(rsf_ctx *c, int64_t n_iters, const double *z, const double *u, const double *g, const double *ssq_new, double *tq,
-             double *ts, uint8_t *ta, bool replay) {
-  if (!c || n_iters < 0) return fail(RSF_ERR_INVALID, "rsf_mcmc_run: bad argument");
-  if (!c->have_chains) return fail(RSF_ERR_STATE, "rsf_mcmc_run: call rsf_mcmc_init first");
-  if (c->external_chains && !ssq_new)
-    return fail(RSF_ERR_STATE, "chains made by rsf_mcmc_init_state have no observation: advance them with rsf_mcmc_replay_ssq");
-  if (n_iters > INT32_MAX) return fail(RSF_ERR_INVALID, "at most 2^31 - 1 iterations per call (every lane counts its own)");
-  if (n_iters == 0) return RSF_OK;
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_mcmc_run: cannot select device %d", c->device);
-  const int d = c->mc.n_params;
-  const int64_t C = c->mc.n_chains;
-  const size_t rows = (size_t)n_iters * (size_t)C;
+// the sampler's arguments that the ctx alone decides: chain state, limits, adaptation, and the iteration the launch begins at
+McmcArgs mcmc_args(const rsf_ctx *c, int64_t n_iters) {
   McmcArgs A{};
-  A.C = C; A.chain_offset = c->mc.chain_offset; A.n_iters = n_iters; A.iter_base = c->iters_done;
+  A.C = c->mc.n_chains; A.chain_offset = c->mc.chain_offset; A.n_iters = n_iters; A.iter_base = c->iters_done;
   A.seed = c->mc.seed; A.n0 = c->mc.n0; A.shape = 0.5 * (c->mc.n0 + (double)c->nout);  // MCMC.py:158
   A.gd = A.shape - 1.0 / 3.0; A.gc = 1.0 / std::sqrt(9.0 * A.gd);
   for (int p = 0; p < RSF_MAX_PARAMS; ++p) {
@@ -413,38 +505,43 @@ int run_mcmc(rsf_ctx *c, int64_t n_iters, const double *z, const double *u, cons
   A.wref = (double *)c->wref.p; A.wsum = (double *)c->wsum.p; A.wsq = (double *)c->wsq.p; A.wn = (int32_t *)c->wn.p;
   A.wbuf = (double *)c->wbuf.p;
   A.stats = (unsigned long long *)c->stats.p;
-  const SamplerLaunch L = sampler_launch(c, replay, ssq_new != nullptr);
-  A.lc_off = L.lc_off;
+  return A;
+}
+
+// rsf_mcmc_run, _replay (z, u, g) and _replay_ssq (ssq_new as well): all three report as rsf_mcmc_run
+int run_mcmc(rsf_ctx *c, int64_t n_iters, const double *z, const double *u, const double *g, const double *ssq_new, double *tq,
+             double *ts, uint8_t *ta, bool replay) {
+  DeviceGuard guard;
   int rc;
-  if (replay && !ssq_new && host_mem(c) && n_iters == 1 && C <= kReplayGraphMaxChains) {
-    Consts Kg = make_sampler_consts(c, (const double *)c->data.p);
-    Kg.group_chains = c->group_chains;
-    return run_replay_graph(c, L, Kg, A, z, u, g, tq, ts, ta);
-  }
-  const void *dz = nullptr, *du = nullptr, *dg = nullptr;
-  void *dtq = nullptr, *dts = nullptr, *dta = nullptr;
-  if ((rc = stage_in(c, 0, z, rows * d * sizeof(double), &dz))) return rc;
-  if ((rc = stage_in(c, 1, u, rows * sizeof(double), &du))) return rc;
-  if ((rc = stage_in(c, 2, g, rows * sizeof(double), &dg))) return rc;
-  A.z = (const double *)dz; A.u = (const double *)du; A.g = (const double *)dg;
-  const void *dsn = nullptr;
-  if ((rc = stage_in(c, 6, ssq_new, rows * sizeof(double), &dsn))) return rc;
-  A.ssq_new = (const double *)dsn;
-  Consts K = make_sampler_consts(c, (const double *)c->data.p);
-  K.group_chains = c->group_chains;
+  if ((rc = enter(guard, c, "rsf_mcmc_run", NEED_CHAINS, n_iters >= 0, "bad argument"))) return rc;
+  if (c->external_chains && !ssq_new)
+    return fail(RSF_ERR_STATE, "chains made by rsf_mcmc_init_state have no observation: advance them with rsf_mcmc_replay_ssq");
+  if (n_iters > INT32_MAX) return fail(RSF_ERR_INVALID, "at most 2^31 - 1 iterations per call (every lane counts its own)");
+  if (n_iters == 0) return RSF_OK;
+  const int d = c->mc.n_params;
+  const int64_t C = c->mc.n_chains;
+  const size_t rows = (size_t)n_iters * (size_t)C;
+  const SamplerLaunch L = sampler_launch(c, replay, ssq_new != nullptr);
+  const Consts K = make_sampler_consts(c);
+  McmcArgs A = mcmc_args(c, n_iters);
+  A.lc_off = L.lc_off;
+  if (replay && !ssq_new && host_mem(c) && n_iters == 1 && C <= kReplayGraphMaxChains) return run_replay_graph(c, L, K, A, z, u, g, tq, ts, ta);
+  if ((rc = stage_in(c, SLOT_Z, z, rows * d * sizeof(double), &A.z))) return rc;
+  if ((rc = stage_in(c, SLOT_U, u, rows * sizeof(double), &A.u))) return rc;
+  if ((rc = stage_in(c, SLOT_G, g, rows * sizeof(double), &A.g))) return rc;
+  if ((rc = stage_in(c, SLOT_SSQ_NEW, ssq_new, rows * sizeof(double), &A.ssq_new))) return rc;
   if (host_mem(c) && !replay) {
     const size_t row_bytes = (size_t)C * ((tq ? d * sizeof(double) : 0) + (ts ? sizeof(double) : 0) + (ta ? 1 : 0));
     const int64_t per = row_bytes ? std::max<int64_t>(1, (int64_t)(drain_bytes() / row_bytes)) : n_iters;
     if (per < n_iters) return run_mcmc_drained(c, L, K, A, per, tq, ts, ta);
   }
-  if ((rc = stage_out(c, 3, tq, rows * d * sizeof(double), &dtq))) return rc;
-  if ((rc = stage_out(c, 4, ts, rows * sizeof(double), &dts))) return rc;
-  if ((rc = stage_out(c, 5, ta, rows, &dta))) return rc;
-  A.tq = (double *)dtq; A.ts = (double *)dts; A.ta = (uint8_t *)dta;
-  if ((rc = launch_sampler(c, L, K, A))) return rc;
-  if ((rc = copy_back(c, 3, tq, rows * d * sizeof(double)))) return rc;
-  if ((rc = copy_back(c, 4, ts, rows * sizeof(double)))) return rc;
-  if ((rc = copy_back(c, 5, ta, rows))) return rc;
+  if ((rc = stage_out(c, SLOT_TQ, tq, rows * d * sizeof(double), &A.tq))) return rc;
+  if ((rc = stage_out(c, SLOT_TS, ts, rows * sizeof(double), &A.ts))) return rc;
+  if ((rc = stage_out(c, SLOT_TA, ta, rows, &A.ta))) return rc;
+  if ((rc = launch(c, L.fn, L.grid, c->block, L.lds, K, A))) return rc;
+  if ((rc = copy_back(c, SLOT_TQ, tq, rows * d * sizeof(double)))) return rc;
+  if ((rc = copy_back(c, SLOT_TS, ts, rows * sizeof(double)))) return rc;
+  if ((rc = copy_back(c, SLOT_TA, ta, rows))) return rc;
   c->iters_done += n_iters;
   return finish(c);
 }
@@ -511,6 +608,16 @@ void free_chains(rsf_ctx *c) {
   c->external_chains = false;
 }
 
+// RK4 table chunk: the output intervals kc whose (2*S*kc + 1) loading values + kc observations + the observation's sample
+// 0 fit `entries`, at most all nout - 1 of them (0: not even one fits).  float32 solve (group8): residuals are summed in
+// float32 over groups of eight samples (k = 1..8, 9..16, ...; rsf_device_f32.h, Out32) and its assembly trip covers one
+// group: chunks begin on a group boundary.
+int64_t rk4_chunk_len(int64_t entries, int S, int32_t nout, bool group8) {
+  int64_t kc = std::min<int64_t>((entries - 2) / (2 * (int64_t)S + 1), nout - 1);
+  if (group8 && kc < nout - 1 && kc >= 8) kc &= ~(int64_t)7;
+  return kc;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -567,6 +674,7 @@ int rsf_destroy(rsf_ctx *c) {
     release(c->vl);
     for (auto &s : c->stage) release(s);
     release(c->pool);
+    release(c->poolws);
     release(c->diag);
     release(c->rankws);
     release_replay_graph(c);
@@ -579,21 +687,19 @@ int rsf_destroy(rsf_ctx *c) {
 }
 
 int rsf_sync(rsf_ctx *c) {
-  if (!c) return fail(RSF_ERR_INVALID, "rsf_sync: NULL ctx");
-  DeviceGuard guard(c->device);
+  RSF_ENTER(c, NEED_NOTHING);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RSF_OK;
 }
 
 int rsf_set_model(rsf_ctx *c, const rsf_model *m) {
-  if (!c || !m) return fail(RSF_ERR_INVALID, "rsf_set_model: NULL argument");
+  RSF_ENTER(c, NEED_NOTHING, m != nullptr, "NULL argument");
+  int rc;
   if (m->size != sizeof(rsf_model)) return fail(RSF_ERR_INVALID, "rsf_set_model: struct size mismatch");
   if (m->nsteps < 2 || m->substeps < 1 || !(m->t_final > m->t_start))
     return fail(RSF_ERR_INVALID, "rsf_set_model: need nsteps >= 2, substeps >= 1, t_final > t_start");
   if ((m->flags & RSF_FLAG_DOP853) && (m->flags & RSF_FLAG_FP32_SOLVE))
     return fail(RSF_ERR_INVALID, "rsf_set_model: the dop853 integrator is float64 only");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_set_model: cannot select device %d", c->device);
   const double delta_t = (m->t_final - m->t_start) / m->nsteps;                  // RateStateModel.py:176
   const int32_t nout = (int32_t)std::floor((m->t_final - m->t_start) / delta_t); // RateStateModel.py:358
   if (nout < 2) return fail(RSF_ERR_INVALID, "rsf_set_model: fewer than 2 output samples");
@@ -620,13 +726,8 @@ int rsf_set_model(rsf_ctx *c, const rsf_model *m) {
       x = x + hk;
     }
   } else {
-    // LDS chunking: kc output intervals need (2*S*kc + 1) loading values + kc observations + the observation's sample 0
-    kc = ((int64_t)words - 2) / (2 * (int64_t)S + 1);
+    kc = rk4_chunk_len((int64_t)words, S, nout, m->flags & RSF_FLAG_FP32_SOLVE);
     if (kc < 1) return fail(RSF_ERR_UNSUPPORTED, "rsf_set_model: substeps=%d does not fit the LDS staging budget", S);
-    if (kc > nout - 1) kc = nout - 1;
-    // float32 solve: residuals are summed in float32 over groups of eight samples (k = 1..8, 9..16, ...; rsf_device_f32.h,
-    // Out32) and its assembly trip covers one group: chunks begin on a group boundary
-    if ((m->flags & RSF_FLAG_FP32_SOLVE) && kc < nout - 1 && kc >= 8) kc &= ~(int64_t)7;
     // chain-independent loading velocity at every RK4 stage time, RateStateModel.py:327-329
     vl.resize(2 * (size_t)S * (size_t)(nout - 1) + 1);
     for (size_t j = 0; j < vl.size(); ++j) {
@@ -635,8 +736,7 @@ int rsf_set_model(rsf_ctx *c, const rsf_model *m) {
     }
   }
   const size_t nvl = vl.size();
-  int rc = ensure(c->vl, nvl * sizeof(double));
-  if (rc) return rc;
+  if ((rc = ensure(c->vl, nvl * sizeof(double)))) return rc;
   HIP_TRY(hipMemcpyAsync(c->vl.p, vl.data(), nvl * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // vl (host vector) goes out of scope
   if (c->have_chains) free_chains(c);  // chain state (SSq, sigma^2, covariance) belongs to the previous model
@@ -646,10 +746,8 @@ int rsf_set_model(rsf_ctx *c, const rsf_model *m) {
   c->nchunks = (int32_t)((nout - 1 + kc - 1) / kc);
   c->kc32 = c->kc; c->nchunks32 = c->nchunks;
   if ((m->flags & RSF_FLAG_FP32_SOLVE) && !dop) {
-    // the float32 sampler stages floats: the same budget in bytes holds twice the entries (chunks on a group boundary, as above)
-    int64_t k32 = ((int64_t)(kLdsBudget / sizeof(float)) - 2) / (2 * (int64_t)S + 1);
-    if (k32 > nout - 1) k32 = nout - 1;
-    if (k32 < nout - 1 && k32 >= 8) k32 &= ~(int64_t)7;
+    // the float32 sampler stages floats: the same budget in bytes holds twice the entries
+    const int64_t k32 = rk4_chunk_len((int64_t)(kLdsBudget / sizeof(float)), S, nout, true);
     c->kc32 = (int32_t)k32;
     c->nchunks32 = (int32_t)((nout - 1 + k32 - 1) / k32);
   }
@@ -667,50 +765,23 @@ int rsf_model_nout(rsf_ctx *c, int32_t *nout) {
 
 int rsf_forward_batch(rsf_ctx *c, int64_t n, const double *dc, const double *a, const double *b,
                       const double *data, double *ssq_out, double *acc_out) {
-  if (!c || !dc || n < 0) return fail(RSF_ERR_INVALID, "rsf_forward_batch: bad argument");
-  if (!c->have_model) return fail(RSF_ERR_STATE, "rsf_forward_batch: call rsf_set_model first");
+  RSF_ENTER(c, NEED_MODEL, dc && n >= 0, "bad argument");
+  int rc;
   if (ssq_out && !data) return fail(RSF_ERR_INVALID, "rsf_forward_batch: ssq_out needs data");
   if (n == 0) return RSF_OK;
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_forward_batch: cannot select device %d", c->device);
   const size_t nb = (size_t)n * sizeof(double);
-  const void *ddc, *da, *db, *ddata;
-  void *dssq, *dacc;
-  int rc;
-  if ((rc = stage_in(c, 0, dc, nb, &ddc))) return rc;
-  if ((rc = stage_in(c, 1, a, nb, &da))) return rc;
-  if ((rc = stage_in(c, 2, b, nb, &db))) return rc;
-  if ((rc = stage_in(c, 3, ssq_out ? data : nullptr, (size_t)c->nout * sizeof(double), &ddata))) return rc;
-  if ((rc = stage_out(c, 4, ssq_out, nb, &dssq))) return rc;
-  if ((rc = stage_out(c, 5, acc_out, nb * (size_t)c->nout, &dacc))) return rc;
-  const Consts K = make_consts(c, (const double *)ddata);
-  const dim3 grid(grid_for(c, n)), block(c->block);
-  const bool damp = damped(c, mode_of(c));
-#define RSF_LAUNCH_FWD_M(DAMP, SSQ, ACC, MODE)                                                              \
-  hipLaunchKernelGGL((forward_kernel<DAMP, SSQ, ACC, MODE>), grid, block, c->lds_bytes, c->stream, K, n,      \
-                     (const double *)ddc, (const double *)da, (const double *)db, (double *)dssq, (double *)dacc)
-#define RSF_LAUNCH_FWD(DAMP, SSQ, ACC)                                                                      \
-  do {                                                                                                      \
-    switch (mode_of(c)) {                                                                                   \
-      case RK4_F32: RSF_LAUNCH_FWD_M(DAMP, SSQ, ACC, RK4_F32); break;                                       \
-      case DOP853: RSF_LAUNCH_FWD_M(DAMP, SSQ, ACC, DOP853); break;                                         \
-      default: RSF_LAUNCH_FWD_M(DAMP, SSQ, ACC, RK4_F64); break;                                            \
-    }                                                                                                       \
-  } while (0)
-  const int sel = (damp ? 4 : 0) | (ssq_out ? 2 : 0) | (acc_out ? 1 : 0);
-  switch (sel) {
-    case 0: case 4: break;  // nothing requested
-    case 1: RSF_LAUNCH_FWD(false, false, true); break;
-    case 2: RSF_LAUNCH_FWD(false, true, false); break;
-    case 3: RSF_LAUNCH_FWD(false, true, true); break;
-    case 5: RSF_LAUNCH_FWD(true, false, true); break;
-    case 6: RSF_LAUNCH_FWD(true, true, false); break;
-    case 7: RSF_LAUNCH_FWD(true, true, true); break;
-  }
-#undef RSF_LAUNCH_FWD
-#undef RSF_LAUNCH_FWD_M
-  if ((rc = copy_back(c, 4, ssq_out, nb))) return rc;
-  if ((rc = copy_back(c, 5, acc_out, nb * (size_t)c->nout))) return rc;
+  const double *ddc, *da, *db, *ddata;
+  double *dssq, *dacc;
+  if ((rc = stage_in(c, SLOT_DC, dc, nb, &ddc))) return rc;
+  if ((rc = stage_in(c, SLOT_A, a, nb, &da))) return rc;
+  if ((rc = stage_in(c, SLOT_B, b, nb, &db))) return rc;
+  if ((rc = stage_in(c, SLOT_DATA, ssq_out ? data : nullptr, (size_t)c->nout * sizeof(double), &ddata))) return rc;
+  if ((rc = stage_out(c, SLOT_SSQ_OUT, ssq_out, nb, &dssq))) return rc;
+  if ((rc = stage_out(c, SLOT_ACC_OUT, acc_out, nb * (size_t)c->nout, &dacc))) return rc;
+  if (const ForwardFn fn = forward_fn(c, ssq_out != nullptr, acc_out != nullptr))
+    if ((rc = launch(c, fn, grid_for(c, n), c->block, c->lds_bytes, make_consts(c, ddata), n, ddc, da, db, dssq, dacc))) return rc;
+  if ((rc = copy_back(c, SLOT_SSQ_OUT, ssq_out, nb))) return rc;
+  if ((rc = copy_back(c, SLOT_ACC_OUT, acc_out, nb * (size_t)c->nout))) return rc;
   return finish(c);
 }
 
@@ -764,9 +835,8 @@ int reset_window(rsf_ctx *c, const rsf_mcmc_config *cfg) {
 }
 
 int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, const double *data) {
+  RSF_ENTER(c, NEED_MODEL, cfg && q0 && data, "NULL argument");
   int rc;
-  if (!c || !cfg || !q0 || !data) return fail(RSF_ERR_INVALID, "rsf_mcmc_init: NULL argument");
-  if (!c->have_model) return fail(RSF_ERR_STATE, "rsf_mcmc_init: call rsf_set_model first");
   if ((rc = check_mcmc_config(cfg, "rsf_mcmc_init"))) return rc;
   const int G = cfg->n_groups > 1 ? cfg->n_groups : 1;
   // a workgroup's chains share one observation series: a group must be whole workgroups' worth of chains
@@ -774,8 +844,6 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
   if (cfg->n_groups < 0 || cfg->n_chains % G || (G > 1 && (cfg->n_chains / G) % wg_chains))
     return fail(RSF_ERR_INVALID, "rsf_mcmc_init: n_chains/n_groups must be a whole multiple of a workgroup's chains (%d%s)", wg_chains,
                 chains_per_lane(c) == 2 ? ": the float32 sampler carries two chains per lane" : "");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_mcmc_init: cannot select device %d", c->device);
   const int d = cfg->n_params;
   const int64_t C = cfg->n_chains;
   const size_t cb = (size_t)C * sizeof(double);
@@ -784,9 +852,9 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
   if ((rc = alloc_chains(c, cfg))) return rc;
   const hipMemcpyKind kind = host_mem(c) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   HIP_TRY(hipMemcpyAsync(c->data.p, data, data_bytes, kind, c->stream));
-  const void *dq0;
-  if ((rc = stage_in(c, 0, q0, cb * d, &dq0))) return rc;
-  if ((rc = transpose(c, C, d, (const double *)dq0, (double *)c->q.p, true))) return rc;
+  const double *dq0;
+  if ((rc = stage_in(c, SLOT_Q, q0, cb * d, &dq0))) return rc;
+  if ((rc = transpose(c, C, d, dq0, (double *)c->q.p, true))) return rc;
   if ((rc = reset_window(c, cfg))) return rc;
   InitArgs A{};
   A.C = C;
@@ -796,37 +864,11 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
   A.q0 = (const double *)c->q.p;
   A.ssq = (double *)c->ssq.p; A.std2 = (double *)c->std2.p; A.V = (double *)c->V.p;
   c->group_chains = G > 1 ? C / G : 0;
-  Consts K = make_consts(c, (const double *)c->data.p);
-  K.group_chains = c->group_chains;
-  const dim3 grid(grid_for(c, C)), block(c->block);
+  // both kernels take the shared chunking (c->kc, c->lds_bytes): only the float32 SAMPLER has its own (rsf_kernels.h, kLdsBudget)
+  const Consts K = make_consts(c, (const double *)c->data.p, c->group_chains);
   // the init kernels run one lane per TRAJECTORY: 1 + d adjacent lanes per chain (rsf_kernels.h, InitGroup)
-  const dim3 igrid((unsigned)((C * (d + 1) + c->block - 1) / c->block));
-  const bool damp = c->m.flags & RSF_FLAG_RADIATION_DAMPING;
-  const bool damp_rk4 = damped(c, RK4_F64);  // init_kernel: the float64 RK4 solve, in the float32 mode as well
-  if (c->m.flags & RSF_FLAG_DOP853) {
-    if (d == 1) {
-      if (damp) hipLaunchKernelGGL((init_dp_kernel<1, true>), igrid, block, c->lds_bytes, c->stream, K, A);
-      else hipLaunchKernelGGL((init_dp_kernel<1, false>), igrid, block, c->lds_bytes, c->stream, K, A);
-    } else {
-      if (damp) hipLaunchKernelGGL((init_dp_kernel<3, true>), igrid, block, c->lds_bytes, c->stream, K, A);
-      else hipLaunchKernelGGL((init_dp_kernel<3, false>), igrid, block, c->lds_bytes, c->stream, K, A);
-    }
-  } else if (d == 1) {
-    if (damp_rk4) hipLaunchKernelGGL((init_kernel<1, true>), igrid, block, c->lds_bytes, c->stream, K, A);
-    else hipLaunchKernelGGL((init_kernel<1, false>), igrid, block, c->lds_bytes, c->stream, K, A);
-  } else {
-    if (damp_rk4) hipLaunchKernelGGL((init_kernel<3, true>), igrid, block, c->lds_bytes, c->stream, K, A);
-    else hipLaunchKernelGGL((init_kernel<3, false>), igrid, block, c->lds_bytes, c->stream, K, A);
-  }
-  if (c->m.flags & RSF_FLAG_FP32_SOLVE) {
-    if (d == 1) {
-      if (damp) hipLaunchKernelGGL((ssq32_kernel<1, true>), grid, block, c->lds_bytes, c->stream, K, C, A.q0, A.ssq);
-      else hipLaunchKernelGGL((ssq32_kernel<1, false>), grid, block, c->lds_bytes, c->stream, K, C, A.q0, A.ssq);
-    } else {
-      if (damp) hipLaunchKernelGGL((ssq32_kernel<3, true>), grid, block, c->lds_bytes, c->stream, K, C, A.q0, A.ssq);
-      else hipLaunchKernelGGL((ssq32_kernel<3, false>), grid, block, c->lds_bytes, c->stream, K, C, A.q0, A.ssq);
-    }
-  }
+  if ((rc = launch(c, init_fn(c, d), grid_for(c, C * (d + 1)), c->block, c->lds_bytes, K, A))) return rc;
+  if (mode_of(c) == RK4_F32 && (rc = launch(c, ssq32_fn(c, d), grid_for(c, C), c->block, c->lds_bytes, K, C, A.q0, A.ssq))) return rc;
   c->mc = *cfg;
   c->iters_done = 0;
   c->have_chains = true;
@@ -837,40 +879,30 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
 }
 
 int rsf_mcmc_get_state(rsf_ctx *c, double *q, double *ssq, double *std2, double *V) {
-  if (!c) return fail(RSF_ERR_INVALID, "rsf_mcmc_get_state: NULL ctx");
-  if (!c->have_chains) return fail(RSF_ERR_STATE, "rsf_mcmc_get_state: call rsf_mcmc_init first");
-  DeviceGuard guard(c->device);
+  RSF_ENTER(c, NEED_CHAINS);
+  int rc;
   const int d = c->mc.n_params;
   const size_t cb = (size_t)c->mc.n_chains * sizeof(double);
   const hipMemcpyKind kind = host_mem(c) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   const int64_t C = c->mc.n_chains;
-  void *dq, *dV;
-  int rc;
-  if ((rc = stage_out(c, 0, q, cb * d, &dq))) return rc;
-  if ((rc = stage_out(c, 1, V, cb * d * d, &dV))) return rc;
-  if (q && (rc = transpose(c, C, d, (const double *)c->q.p, (double *)dq, false))) return rc;
-  if (V && (rc = transpose(c, C, d * d, (const double *)c->V.p, (double *)dV, false))) return rc;
-  if ((rc = copy_back(c, 0, q, cb * d))) return rc;
-  if ((rc = copy_back(c, 1, V, cb * d * d))) return rc;
+  double *dq, *dV;
+  if ((rc = stage_out(c, SLOT_Q, q, cb * d, &dq))) return rc;
+  if ((rc = stage_out(c, SLOT_V, V, cb * d * d, &dV))) return rc;
+  if (q && (rc = transpose(c, C, d, (const double *)c->q.p, dq, false))) return rc;
+  if (V && (rc = transpose(c, C, d * d, (const double *)c->V.p, dV, false))) return rc;
+  if ((rc = copy_back(c, SLOT_Q, q, cb * d))) return rc;
+  if ((rc = copy_back(c, SLOT_V, V, cb * d * d))) return rc;
   if (ssq) HIP_TRY(hipMemcpyAsync(ssq, c->ssq.p, cb, kind, c->stream));
   if (std2) HIP_TRY(hipMemcpyAsync(std2, c->std2.p, cb, kind, c->stream));
   return finish(c);
 }
 
 int rsf_mcmc_set_state(rsf_ctx *c, const double *q, const double *ssq, const double *std2, const double *V) {
-  if (!c) return fail(RSF_ERR_INVALID, "rsf_mcmc_set_state: NULL ctx");
-  if (!c->have_chains) return fail(RSF_ERR_STATE, "rsf_mcmc_set_state: call rsf_mcmc_init first");
-  DeviceGuard guard(c->device);
-  const int d = c->mc.n_params;
+  RSF_ENTER(c, NEED_CHAINS);
+  int rc;
   const size_t cb = (size_t)c->mc.n_chains * sizeof(double);
   const hipMemcpyKind kind = host_mem(c) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  const int64_t C = c->mc.n_chains;
-  const void *dq, *dV;
-  int rc;
-  if ((rc = stage_in(c, 0, q, cb * d, &dq))) return rc;
-  if ((rc = stage_in(c, 1, V, cb * d * d, &dV))) return rc;
-  if (q && (rc = transpose(c, C, d, (const double *)dq, (double *)c->q.p, true))) return rc;
-  if (V && (rc = transpose(c, C, d * d, (const double *)dV, (double *)c->V.p, true))) return rc;
+  if ((rc = put_q_V(c, c->mc.n_chains, c->mc.n_params, q, V))) return rc;
   if (ssq) HIP_TRY(hipMemcpyAsync(c->ssq.p, ssq, cb, kind, c->stream));
   if (std2) HIP_TRY(hipMemcpyAsync(c->std2.p, std2, cb, kind, c->stream));
   return finish(c);
@@ -893,21 +925,13 @@ int rsf_mcmc_replay_ssq(rsf_ctx *c, int64_t n_iters, const double *z, const doub
 }
 
 int rsf_mcmc_init_state(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q, const double *ssq, const double *std2, const double *V) {
+  RSF_ENTER(c, NEED_NOTHING, cfg && q && ssq && std2 && V, "NULL argument");
   int rc;
-  if (!c || !cfg || !q || !ssq || !std2 || !V) return fail(RSF_ERR_INVALID, "rsf_mcmc_init_state: NULL argument");
   if ((rc = check_mcmc_config(cfg, "rsf_mcmc_init_state"))) return rc;
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_mcmc_init_state: cannot select device %d", c->device);
-  const int d = cfg->n_params;
-  const int64_t C = cfg->n_chains;
-  const size_t cb = (size_t)C * sizeof(double);
+  const size_t cb = (size_t)cfg->n_chains * sizeof(double);
   if ((rc = alloc_chains(c, cfg))) return rc;
   const hipMemcpyKind kind = host_mem(c) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  const void *dq, *dV;
-  if ((rc = stage_in(c, 0, q, cb * d, &dq))) return rc;
-  if ((rc = stage_in(c, 1, V, cb * d * d, &dV))) return rc;
-  if ((rc = transpose(c, C, d, (const double *)dq, (double *)c->q.p, true))) return rc;
-  if ((rc = transpose(c, C, d * d, (const double *)dV, (double *)c->V.p, true))) return rc;
+  if ((rc = put_q_V(c, cfg->n_chains, cfg->n_params, q, V))) return rc;
   HIP_TRY(hipMemcpyAsync(c->ssq.p, ssq, cb, kind, c->stream));
   HIP_TRY(hipMemcpyAsync(c->std2.p, std2, cb, kind, c->stream));
   if ((rc = reset_window(c, cfg))) return rc;
@@ -924,33 +948,24 @@ int rsf_mcmc_init_state(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q,
 int rsf_mcmc_propose(rsf_ctx *c, const double *z, double *q_new, uint8_t *in_bounds) {
   if (!c || !z || !q_new || !in_bounds) return fail(RSF_ERR_INVALID, "rsf_mcmc_propose: NULL argument");
   if (!c->have_chains) return fail(RSF_ERR_STATE, "rsf_mcmc_propose: call rsf_mcmc_init or rsf_mcmc_init_state first");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_mcmc_propose: cannot select device %d", c->device);
+  RSF_ENTER(c, NEED_NOTHING);
+  int rc;
   const int d = c->mc.n_params;
   const int64_t C = c->mc.n_chains;
-  const size_t cb = (size_t)C * sizeof(double);
-  const void *dz;
-  void *dqn, *dinb;
-  int rc;
-  if ((rc = stage_in(c, 0, z, cb * d, &dz))) return rc;
-  if ((rc = stage_out(c, 3, q_new, cb * d, &dqn))) return rc;
-  if ((rc = stage_out(c, 5, in_bounds, (size_t)C, &dinb))) return rc;
   ProposeArgs A{};
-  A.C = C; A.q = (const double *)c->q.p; A.V = (const double *)c->V.p; A.z = (const double *)dz;
+  A.C = C; A.q = (const double *)c->q.p; A.V = (const double *)c->V.p;
   for (int p = 0; p < RSF_MAX_PARAMS; ++p) { A.lo[p] = c->mc.lo[p]; A.hi[p] = c->mc.hi[p]; }
-  A.qn = (double *)dqn; A.inb = (uint8_t *)dinb;
-  const dim3 grid((unsigned)((C + kMaxBlock - 1) / kMaxBlock)), block(kMaxBlock);
-  if (d == 1) hipLaunchKernelGGL(propose_kernel<1>, grid, block, 0, c->stream, A);
-  else hipLaunchKernelGGL(propose_kernel<3>, grid, block, 0, c->stream, A);
-  if ((rc = copy_back(c, 3, q_new, cb * d))) return rc;
-  if ((rc = copy_back(c, 5, in_bounds, (size_t)C))) return rc;
+  if ((rc = stage_in(c, SLOT_Z, z, (size_t)C * d * sizeof(double), &A.z))) return rc;
+  if ((rc = stage_out(c, SLOT_Q_NEW, q_new, (size_t)C * d * sizeof(double), &A.qn))) return rc;
+  if ((rc = stage_out(c, SLOT_IN_BOUNDS, in_bounds, (size_t)C, &A.inb))) return rc;
+  if ((rc = launch(c, propose_fn(d), (unsigned)((C + kMaxBlock - 1) / kMaxBlock), kMaxBlock, 0, A))) return rc;
+  if ((rc = copy_back(c, SLOT_Q_NEW, q_new, (size_t)C * d * sizeof(double)))) return rc;
+  if ((rc = copy_back(c, SLOT_IN_BOUNDS, in_bounds, (size_t)C))) return rc;
   return finish(c);
 }
 
 int rsf_mcmc_stats(rsf_ctx *c, int64_t *n_acc, int64_t *n_eval, int64_t *n_nonfinite, int64_t *n_done) {
-  if (!c) return fail(RSF_ERR_INVALID, "rsf_mcmc_stats: NULL ctx");
-  if (!c->have_chains) return fail(RSF_ERR_STATE, "rsf_mcmc_stats: call rsf_mcmc_init first");
-  DeviceGuard guard(c->device);
+  RSF_ENTER(c, NEED_CHAINS);
   unsigned long long s[3];
   HIP_TRY(hipMemcpyAsync(s, c->stats.p, sizeof s, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -962,9 +977,7 @@ int rsf_mcmc_stats(rsf_ctx *c, int64_t *n_acc, int64_t *n_eval, int64_t *n_nonfi
 }
 
 int rsf_mcmc_counters(rsf_ctx *c, int64_t *out, int32_t n) {
-  if (!c || !out || n < 0) return fail(RSF_ERR_INVALID, "rsf_mcmc_counters: bad argument");
-  if (!c->have_chains) return fail(RSF_ERR_STATE, "rsf_mcmc_counters: call rsf_mcmc_init first");
-  DeviceGuard guard(c->device);
+  RSF_ENTER(c, NEED_CHAINS, out && n >= 0, "bad argument");
   unsigned long long s[RSF_CNT_COUNT];
   HIP_TRY(hipMemcpyAsync(s, c->stats.p, sizeof s, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -998,72 +1011,81 @@ int pool_moments(rsf_ctx *c, int64_t n, const double *dx, int64_t stride, double
 }  // namespace
 
 int rsf_pool_summary(rsf_ctx *c, int64_t n, const double *x, int64_t stride, double *out) {
-  if (!c || !x || !out || n < 1 || stride < 1) return fail(RSF_ERR_INVALID, "rsf_pool_summary: bad argument");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_pool_summary: cannot select device %d", c->device);
-  const void *dx;
-  int rc = stage_in(c, 0, x, (size_t)((n - 1) * stride + 1) * sizeof(double), &dx);
-  if (rc) return rc;
-  return pool_moments(c, n, (const double *)dx, stride, out);
+  RSF_ENTER(c, NEED_NOTHING, x && out && n >= 1 && stride >= 1, "bad argument");
+  int rc;
+  const double *dx;
+  if ((rc = stage_in(c, SLOT_X, x, (size_t)((n - 1) * stride + 1) * sizeof(double), &dx))) return rc;
+  return pool_moments(c, n, dx, stride, out);
 }
 
 int rsf_pool_kde(rsf_ctx *c, int64_t n, const double *x, int64_t stride, int32_t m, const double *grid, double bw_factor,
                  double *density) {
-  if (!c || !x || !grid || !density || n < 2 || m < 1 || stride < 1) return fail(RSF_ERR_INVALID, "rsf_pool_kde: bad argument");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_pool_kde: cannot select device %d", c->device);
-  const void *dx, *dg;
-  void *dd;
+  RSF_ENTER(c, NEED_NOTHING, x && grid && density && n >= 2 && m >= 1 && stride >= 1, "bad argument");
   int rc;
-  if ((rc = stage_in(c, 0, x, (size_t)((n - 1) * stride + 1) * sizeof(double), &dx))) return rc;
-  if ((rc = stage_in(c, 1, grid, (size_t)m * sizeof(double), &dg))) return rc;
-  if ((rc = stage_out(c, 2, density, (size_t)m * sizeof(double), &dd))) return rc;
+  const double *dx, *dg;
+  double *dd;
+  if ((rc = stage_in(c, SLOT_X, x, (size_t)((n - 1) * stride + 1) * sizeof(double), &dx))) return rc;
+  if ((rc = stage_in(c, SLOT_GRID, grid, (size_t)m * sizeof(double), &dg))) return rc;
+  if ((rc = stage_out(c, SLOT_POOL_OUT, density, (size_t)m * sizeof(double), &dd))) return rc;
   double s[5];
-  if ((rc = pool_moments(c, n, (const double *)dx, stride, s))) return rc;
+  if ((rc = pool_moments(c, n, dx, stride, s))) return rc;
   const double factor = bw_factor > 0.0 ? bw_factor : std::pow((double)n, -1.0 / 5.0);  // scipy scotts_factor, d = 1
   const double cov = s[2] * factor * factor;
   if (!(cov > 0.0)) return fail(RSF_ERR_INVALID, "rsf_pool_kde: the samples have zero variance (singular KDE)");
   const int blocks = (int)std::min<int64_t>(kPoolBlocks, (n + kKdeTile - 1) / kKdeTile);
-  DevBuf &ws = c->stage[7];
+  DevBuf &ws = c->poolws;
   if ((rc = ensure(ws, (size_t)blocks * (size_t)m * sizeof(double)))) return rc;
-  hipLaunchKernelGGL(pool_kde_kernel, dim3(blocks), dim3(kMaxBlock), 0, c->stream, n, (const double *)dx, stride, (int)m,
-                     (const double *)dg, 0.5 / cov, (double *)ws.p);
+  hipLaunchKernelGGL(pool_kde_kernel, dim3(blocks), dim3(kMaxBlock), 0, c->stream, n, dx, stride, (int)m, dg, 0.5 / cov,
+                     (double *)ws.p);
   hipLaunchKernelGGL(pool_kde_reduce_kernel, dim3((m + kMaxBlock - 1) / kMaxBlock), dim3(kMaxBlock), 0, c->stream, blocks, (int)m,
-                     (const double *)ws.p, 1.0 / ((double)n * std::sqrt(2.0 * 3.14159265358979323846 * cov)), (double *)dd);
-  if ((rc = copy_back(c, 2, density, (size_t)m * sizeof(double)))) return rc;
+                     (const double *)ws.p, 1.0 / ((double)n * std::sqrt(2.0 * 3.14159265358979323846 * cov)), dd);
+  if ((rc = copy_back(c, SLOT_POOL_OUT, density, (size_t)m * sizeof(double)))) return rc;
   return finish(c);
 }
 
 int rsf_pool_histogram(rsf_ctx *c, int64_t n, const double *x, int64_t stride, int32_t nbins, double lo, double hi, double *counts) {
   if (!c || !x || !counts || n < 1 || stride < 1 || nbins < 1 || nbins > kHistMaxBins || !(hi > lo) || !std::isfinite(hi - lo))
     return fail(RSF_ERR_INVALID, "rsf_pool_histogram: bad argument (1 <= nbins <= %d, finite lo < hi)", kHistMaxBins);
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_pool_histogram: cannot select device %d", c->device);
-  const void *dx;
-  void *dout;
+  RSF_ENTER(c, NEED_NOTHING);
   int rc;
+  const double *dx;
+  double *dout;
   const int nb = nbins + 2;
-  if ((rc = stage_in(c, 0, x, (size_t)((n - 1) * stride + 1) * sizeof(double), &dx))) return rc;
-  if ((rc = stage_out(c, 2, counts, (size_t)nb * sizeof(double), &dout))) return rc;
-  DevBuf &ws = c->stage[7];
+  if ((rc = stage_in(c, SLOT_X, x, (size_t)((n - 1) * stride + 1) * sizeof(double), &dx))) return rc;
+  if ((rc = stage_out(c, SLOT_POOL_OUT, counts, (size_t)nb * sizeof(double), &dout))) return rc;
+  DevBuf &ws = c->poolws;
   if ((rc = ensure(ws, (size_t)nb * sizeof(unsigned long long)))) return rc;
   HIP_TRY(hipMemsetAsync(ws.p, 0, (size_t)nb * sizeof(unsigned long long), c->stream));
   const int blocks = (int)std::min<int64_t>(kPoolBlocks, (n + kMaxBlock - 1) / kMaxBlock);
-  hipLaunchKernelGGL(pool_hist_kernel, dim3(blocks), dim3(kMaxBlock), (size_t)nb * sizeof(unsigned int), c->stream, n, (const double *)dx,
-                     stride, (int)nbins, lo, hi, (double)nbins / (hi - lo), (hi - lo) / (double)nbins, (unsigned long long *)ws.p);
+  hipLaunchKernelGGL(pool_hist_kernel, dim3(blocks), dim3(kMaxBlock), (size_t)nb * sizeof(unsigned int), c->stream, n, dx, stride,
+                     (int)nbins, lo, hi, (double)nbins / (hi - lo), (hi - lo) / (double)nbins, (unsigned long long *)ws.p);
   hipLaunchKernelGGL(pool_hist_finish_kernel, dim3((nb + kMaxBlock - 1) / kMaxBlock), dim3(kMaxBlock), 0, c->stream, nb,
-                     (const unsigned long long *)ws.p, (double *)dout);
-  if ((rc = copy_back(c, 2, counts, (size_t)nb * sizeof(double)))) return rc;
+                     (const unsigned long long *)ws.p, dout);
+  if ((rc = copy_back(c, SLOT_POOL_OUT, counts, (size_t)nb * sizeof(double)))) return rc;
   return finish(c);
 }
 
 // ---- convergence diagnostics (include/rsf_diag.h) ----------------------------------------------
 namespace {
+// The lags [lag_begin, lag_end) of a partials call on n draws of C chains and d parameters, and the grid they make: L lags in
+// ntiles tiles for each of nbc blocks of chains.  fn: the entry point the messages name.
+struct LagGrid { int64_t lag_begin, lag_end, L, nbc, ntiles; };
+
+int check_lags(const char *fn, int64_t n, int64_t C, int32_t d, int64_t lag_begin, int64_t lag_end, LagGrid *g) {
+  const int64_t N = n / 2;
+  if (lag_begin < 0 || lag_end <= lag_begin || lag_end > N)
+    return fail(RSF_ERR_INVALID, "%s: lags [%lld, %lld) are not a non-empty range within [0, %lld)", fn, (long long)lag_begin,
+                (long long)lag_end, (long long)N);
+  const int64_t L = lag_end - lag_begin;
+  *g = {lag_begin, lag_end, L, (C + kDiagBlock - 1) / kDiagBlock, (L + kLagTile - 1) / kLagTile};
+  if (g->nbc * d * g->ntiles > INT32_MAX) return fail(RSF_ERR_INVALID, "%s: too many lags for one call; ask for fewer", fn);
+  return RSF_OK;
+}
+
 // rsf_diag_partials after its checks, on a trace x already in device memory
 int diag_partials_dev(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double *x, int64_t S, const rsfk::DiagCenter &cen,
-                      int64_t lag_begin, int64_t lag_end, double *partials) {
-  const int64_t N = n / 2;
-  const int64_t L = lag_end - lag_begin, nbc = (C + kDiagBlock - 1) / kDiagBlock, ntiles = (L + kLagTile - 1) / kLagTile;
+                      const LagGrid &lg, double *partials) {
+  const int64_t N = n / 2, L = lg.L, nbc = lg.nbc;
   const int64_t K = S ? C / S : 0, nbs = S ? std::min<int64_t>(kDiagSuperBlocks, (K + kDiagBlock / 64 - 1) / (kDiagBlock / 64)) : 0;
   // workspace, doubles: mh[2][d][C] | fm[d][C] | fv[d][C] | chain partials[nbc][d][3] | superchain partials[nbs][d][4] |
   // lag partials[nbc][d][L] | sums[d*3 + d*4 + d*L]
@@ -1074,15 +1096,11 @@ int diag_partials_dev(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double 
   if ((rc = ensure(c->diag, (size_t)total * sizeof(double)))) return rc;
   double *w = (double *)c->diag.p;
   const rsfk::DiagShape sh{n, C, d, N, n - N};
-  switch (d) {
-    case 1: hipLaunchKernelGGL(diag_chain_kernel<1>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
-    case 2: hipLaunchKernelGGL(diag_chain_kernel<2>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
-    default: hipLaunchKernelGGL(diag_chain_kernel<3>, dim3((unsigned)nbc), dim3(kDiagBlock), 0, c->stream, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1); break;
-  }
+  if ((rc = launch(c, diag_chain_fn(d), (unsigned)nbc, kDiagBlock, 0, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1))) return rc;
   if (S) hipLaunchKernelGGL(diag_super_kernel, dim3((unsigned)nbs), dim3(kDiagBlock), 0, c->stream, C, (int)d, S, cen, (const double *)(w + o_fm),
                             (const double *)(w + o_fv), w + o_p2);
-  hipLaunchKernelGGL(diag_lag_kernel, dim3((unsigned)(nbc * d * ntiles)), dim3(kDiagBlock), 0, c->stream, sh, x, (const double *)w, lag_begin,
-                     lag_end, w + o_p3);
+  hipLaunchKernelGGL(diag_lag_kernel, dim3((unsigned)(nbc * d * lg.ntiles)), dim3(kDiagBlock), 0, c->stream, sh, x, (const double *)w,
+                     lg.lag_begin, lg.lag_end, w + o_p3);
   const int64_t sum_blocks = (std::max<int64_t>(nf1, std::max(nf2, nf3)) + kDiagBlock - 1) / kDiagBlock;
   hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbc, nf1, (const double *)(w + o_p1), w + o_sum);
   if (S) hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbs, nf2, (const double *)(w + o_p2),
@@ -1114,24 +1132,19 @@ int rsf_diag_partials(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double 
     return fail(RSF_ERR_INVALID, "rsf_diag_partials: need n_iters >= 4, n_chains >= 1, 1 <= n_params <= %d", RSF_MAX_PARAMS);
   if (S < 0 || (S > 0 && C % S)) return fail(RSF_ERR_INVALID, "rsf_diag_partials: chains_per_superchain %lld does not divide %lld chains",
                                              (long long)S, (long long)C);
-  const int64_t N = n / 2;
-  if (lag_begin < 0 || lag_end <= lag_begin || lag_end > N)
-    return fail(RSF_ERR_INVALID, "rsf_diag_partials: lags [%lld, %lld) are not a non-empty range within [0, %lld)", (long long)lag_begin,
-                (long long)lag_end, (long long)N);
   if (n > INT64_MAX / 8 / C / d) return fail(RSF_ERR_INVALID, "rsf_diag_partials: trace too large");
-  const int64_t L = lag_end - lag_begin, nbc = (C + kDiagBlock - 1) / kDiagBlock, ntiles = (L + kLagTile - 1) / kLagTile;
-  if (nbc * d * ntiles > INT32_MAX) return fail(RSF_ERR_INVALID, "rsf_diag_partials: too many lags for one call; ask for fewer");
+  LagGrid lg;
+  int rc;
+  if ((rc = check_lags("rsf_diag_partials", n, C, d, lag_begin, lag_end, &lg))) return rc;
   rsfk::DiagCenter cen{{0.0, 0.0, 0.0}};
   for (int p = 0; p < d; ++p) {
     if (!std::isfinite(center[p])) return fail(RSF_ERR_INVALID, "rsf_diag_partials: center[%d] is not finite", p);
     cen.v[p] = center[p];
   }
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_partials: cannot select device %d", c->device);
-  const void *dx;
-  int rc;
-  if ((rc = stage_in(c, 0, trace, (size_t)(n * C * d) * sizeof(double), &dx))) return rc;
-  return diag_partials_dev(c, n, C, d, (const double *)dx, S, cen, lag_begin, lag_end, partials);
+  RSF_ENTER(c, NEED_NOTHING);
+  const double *dx;
+  if ((rc = stage_in(c, SLOT_X, trace, (size_t)(n * C * d) * sizeof(double), &dx))) return rc;
+  return diag_partials_dev(c, n, C, d, dx, S, cen, lg, partials);
 }
 
 int rsf_diag_finish(int64_t n, int32_t d, int64_t S, const double *center, const double *partials, int64_t n_lags, double *out) {
@@ -1295,13 +1308,11 @@ int rsf_diag_rank_prepare(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const dou
     return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: the HDI of %g of %lld draws spans %g of them; need 1 <= k < n*C", hdi_prob,
                 (long long)A, kd);
   const int64_t khdi = (int64_t)kd;
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_rank_prepare: cannot select device %d", c->device);
-  c->rank_d = 0;
-  const void *dx;
+  RSF_ENTER(c, NEED_NOTHING);
   int rc;
-  if ((rc = stage_in(c, 0, trace, (size_t)(A * d) * sizeof(double), &dx))) return rc;
-  const double *x = (const double *)dx;
+  c->rank_d = 0;
+  const double *x;
+  if ((rc = stage_in(c, SLOT_X, trace, (size_t)(A * d) * sizeof(double), &x))) return rc;
   RankWs w;
   const size_t bytes = rank_ws_layout(A, d, n_probs, nullptr, &w);
   if ((rc = ensure(c->rankws, bytes))) return rc;
@@ -1361,21 +1372,16 @@ int rsf_diag_rank_prepare(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const dou
 int rsf_diag_rank_partials(rsf_ctx *c, int64_t lag_begin, int64_t lag_end, double *partials) {
   if (!c || !partials) return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: NULL argument");
   if (!c->rank_d || !c->rankws.p) return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: no prepared trace (call rsf_diag_rank_prepare first)");
-  const int64_t n = c->rank_n, C = c->rank_C, N = n / 2;
+  const int64_t n = c->rank_n, C = c->rank_C;
   const int32_t d = c->rank_d;
-  if (lag_begin < 0 || lag_end <= lag_begin || lag_end > N)
-    return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: lags [%lld, %lld) are not a non-empty range within [0, %lld)", (long long)lag_begin,
-                (long long)lag_end, (long long)N);
-  const int64_t L = lag_end - lag_begin, nbc = (C + kDiagBlock - 1) / kDiagBlock, ntiles = (L + kLagTile - 1) / kLagTile;
-  if (nbc * d * ntiles > INT32_MAX) return fail(RSF_ERR_INVALID, "rsf_diag_rank_partials: too many lags for one call; ask for fewer");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_diag_rank_partials: cannot select device %d", c->device);
+  LagGrid lg;
+  int rc;
+  if ((rc = check_lags("rsf_diag_rank_partials", n, C, d, lag_begin, lag_end, &lg))) return rc;
+  RSF_ENTER(c, NEED_NOTHING);
   const rsfk::DiagCenter zero{{0.0, 0.0, 0.0}};
   const double *series = (const double *)c->rankws.p;  // the workspace starts with the series
   for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
-    const int rc = diag_partials_dev(c, n, C, d, series + q * n * C * d, 0, zero, lag_begin, lag_end,
-                                     partials + (int64_t)q * d * (RSF_DIAG_HEAD + L));
-    if (rc) return rc;
+    if ((rc = diag_partials_dev(c, n, C, d, series + q * n * C * d, 0, zero, lg, partials + (int64_t)q * d * (RSF_DIAG_HEAD + lg.L)))) return rc;
   }
   return RSF_OK;
 }
@@ -1422,8 +1428,7 @@ int rsf_diag_rank_finish(int64_t n, int32_t d, const double *stats, int32_t n_pr
 }
 
 int rsf_diag_rank_release(rsf_ctx *c) {
-  if (!c) return fail(RSF_ERR_INVALID, "rsf_diag_rank_release: NULL argument");
-  DeviceGuard guard(c->device);
+  RSF_ENTER(c, NEED_NOTHING, true, "NULL argument");
   if (c->rankws.p) HIP_TRY(hipStreamSynchronize(c->stream));
   release(c->rankws);
   c->rank_d = 0;
@@ -1448,8 +1453,7 @@ int rsf_comm_init(rsf_ctx *c, int32_t world, int32_t rank, const uint8_t id[RSF_
   if (id) {  // (world = 1 with an id makes a real one-rank communicator: the single-GPU test of the RCCL binding)
     const Rccl *R = rccl();
     if (!R) return fail(RSF_ERR_UNSUPPORTED, "rsf_comm_init: RCCL (librccl.so) could not be loaded");
-    DeviceGuard guard(c->device);
-    if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_comm_init: cannot select device %d", c->device);
+    RSF_ENTER(c, NEED_NOTHING);
     ncclUniqueId u;
     std::memcpy(u.internal, id, RSF_COMM_ID_BYTES);
     RCCL_TRY(R, R->comm_init_rank(&c->comm, world, u, rank));
@@ -1475,36 +1479,30 @@ int rsf_comm_destroy(rsf_ctx *c) {
 }
 
 int rsf_pool_allgather(rsf_ctx *c, const double *send, int64_t count, double *recv) {
-  if (!c || !send || !recv || count < 1) return fail(RSF_ERR_INVALID, "rsf_pool_allgather: bad argument");
-  if (!c->world) return fail(RSF_ERR_STATE, "rsf_pool_allgather: call rsf_comm_init first");
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_pool_allgather: cannot select device %d", c->device);
-  const size_t bytes = (size_t)count * sizeof(double);
-  const void *ds;
-  void *dr;
+  RSF_ENTER(c, NEED_COMM, send && recv && count >= 1, "bad argument");
   int rc;
-  if ((rc = stage_in(c, 0, send, bytes, &ds))) return rc;
-  if ((rc = stage_out(c, 1, recv, bytes * (size_t)c->world, &dr))) return rc;
+  const size_t bytes = (size_t)count * sizeof(double);
+  const double *ds;
+  double *dr;
+  if ((rc = stage_in(c, SLOT_SEND, send, bytes, &ds))) return rc;
+  if ((rc = stage_out(c, SLOT_RECV, recv, bytes * (size_t)c->world, &dr))) return rc;
   if (!c->comm) {
     if (dr != ds) HIP_TRY(hipMemcpyAsync(dr, ds, bytes, hipMemcpyDeviceToDevice, c->stream));
   } else {
     const Rccl *R = rccl();
     RCCL_TRY(R, R->all_gather(ds, dr, (size_t)count, ncclFloat64, c->comm, c->stream));
   }
-  if ((rc = copy_back(c, 1, recv, bytes * (size_t)c->world))) return rc;
+  if ((rc = copy_back(c, SLOT_RECV, recv, bytes * (size_t)c->world))) return rc;
   return finish(c);
 }
 
 int rsf_pool_allreduce_sum(rsf_ctx *c, double *buf, int64_t count) {
-  if (!c || !buf || count < 1) return fail(RSF_ERR_INVALID, "rsf_pool_allreduce_sum: bad argument");
-  if (!c->world) return fail(RSF_ERR_STATE, "rsf_pool_allreduce_sum: call rsf_comm_init first");
+  RSF_ENTER(c, NEED_COMM, buf && count >= 1, "bad argument");
   if (!c->comm) return RSF_OK;
-  DeviceGuard guard(c->device);
-  if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_pool_allreduce_sum: cannot select device %d", c->device);
-  const size_t bytes = (size_t)count * sizeof(double);
-  const void *ds;
   int rc;
-  if ((rc = stage_in(c, 0, buf, bytes, &ds))) return rc;
+  const size_t bytes = (size_t)count * sizeof(double);
+  const double *ds;
+  if ((rc = stage_in(c, SLOT_SEND, buf, bytes, &ds))) return rc;
   const Rccl *R = rccl();
   RCCL_TRY(R, R->all_reduce(ds, (void *)ds, (size_t)count, ncclFloat64, ncclSum, c->comm, c->stream));
   if (host_mem(c)) HIP_TRY(hipMemcpyAsync(buf, ds, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1551,13 +1549,12 @@ int rsf_pool_allgather_all(rsf_ctx *const *ctxs, int32_t n, const double *const 
     if (!send[i] || !recv[i]) return fail(RSF_ERR_INVALID, "rsf_pool_allgather_all: send[%d] / recv[%d] is NULL", i, i);
   const Rccl *R = rccl();
   const size_t bytes = (size_t)count * sizeof(double);
-  std::vector<const void *> ds(n);
-  std::vector<void *> dr(n);
+  std::vector<const double *> ds(n);
+  std::vector<double *> dr(n);
   for (int32_t i = 0; i < n; ++i) {
-    DeviceGuard guard(ctxs[i]->device);
-    if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_pool_allgather_all: cannot select device %d", ctxs[i]->device);
-    if ((rc = stage_in(ctxs[i], 0, send[i], bytes, &ds[i]))) return rc;
-    if ((rc = stage_out(ctxs[i], 1, recv[i], bytes * (size_t)n, &dr[i]))) return rc;
+    RSF_ENTER(ctxs[i], NEED_NOTHING);
+    if ((rc = stage_in(ctxs[i], SLOT_SEND, send[i], bytes, &ds[i]))) return rc;
+    if ((rc = stage_out(ctxs[i], SLOT_RECV, recv[i], bytes * (size_t)n, &dr[i]))) return rc;
   }
   RCCL_TRY(R, R->group_start());
   for (int32_t i = 0; i < n; ++i) {
@@ -1568,7 +1565,7 @@ int rsf_pool_allgather_all(rsf_ctx *const *ctxs, int32_t n, const double *const 
   RCCL_TRY(R, R->group_end());
   for (int32_t i = 0; i < n; ++i) {
     DeviceGuard guard(ctxs[i]->device);
-    if ((rc = copy_back(ctxs[i], 1, recv[i], bytes * (size_t)n))) return rc;
+    if ((rc = copy_back(ctxs[i], SLOT_RECV, recv[i], bytes * (size_t)n))) return rc;
     if ((rc = finish(ctxs[i]))) return rc;
   }
   return RSF_OK;
@@ -1582,11 +1579,10 @@ int rsf_pool_allreduce_sum_all(rsf_ctx *const *ctxs, int32_t n, double *const *b
     if (!bufs[i]) return fail(RSF_ERR_INVALID, "rsf_pool_allreduce_sum_all: bufs[%d] is NULL", i);
   const Rccl *R = rccl();
   const size_t bytes = (size_t)count * sizeof(double);
-  std::vector<const void *> ds(n);
+  std::vector<const double *> ds(n);
   for (int32_t i = 0; i < n; ++i) {
-    DeviceGuard guard(ctxs[i]->device);
-    if (!guard.ok) return fail(RSF_ERR_DEVICE, "rsf_pool_allreduce_sum_all: cannot select device %d", ctxs[i]->device);
-    if ((rc = stage_in(ctxs[i], 0, bufs[i], bytes, &ds[i]))) return rc;
+    RSF_ENTER(ctxs[i], NEED_NOTHING);
+    if ((rc = stage_in(ctxs[i], SLOT_SEND, bufs[i], bytes, &ds[i]))) return rc;
   }
   RCCL_TRY(R, R->group_start());
   for (int32_t i = 0; i < n; ++i) {

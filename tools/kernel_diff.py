@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""Per-kernel comparison of the gfx950 device code of two builds of librsf_hip.so (no GPU needed).
+
+    tools/kernel_diff.py build/parent/librsf_hip.so bayesian-markov-chain-monte-carlo_amd/csrc/librsf_hip.so
+
+Takes the gfx950 code object out of each library, disassembles it and compares the instruction text of every kernel symbol
+with addresses stripped, so that a different ORDER of the kernels in the object does not count.  The one instruction whose
+encoding depends on where its kernel lies, the s_add_u32 after an s_getpc_b64 that forms the address of a constant table,
+is compared by the address it forms and by the bytes of .rodata from there to the section's end.  Prints one line per kernel
+that differs or exists on one side only, then a summary; exit status 1 if anything differs.  A host-side refactor must print
+none: anything else means a header was touched or an instantiation was added or dropped.
+"""
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = "/opt/rocm/llvm/bin/"
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+
+
+def kernels(lib, tmp, tag):
+    fat, co = f"{tmp}/{tag}.fatbin", f"{tmp}/{tag}.co"
+    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
+    subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fat}", f"--output={co}"])
+    text = subprocess.check_output([LLVM + "llvm-objdump", "-d", co], text=True)
+    ro_at, ro = rodata(co)
+    out, name, getpc = {}, None, False
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            name = m.group(1)
+            out[name] = []
+        elif name and line.strip():
+            # "\ts_load_dword s0, s[4:5], 0x0   // 000000001234: C0020002 00000000": drop the address, keep text and encoding
+            m = re.match(r"\s*s_add_u32 (s\d+), \1, (0x[0-9a-f]+)\s*// ([0-9A-F]+):", line)
+            if getpc and m:  # s_getpc_b64 gave this instruction's address
+                lit = int(m.group(2), 16)
+                at = int(m.group(3), 16) + (lit - (1 << 32) if lit >> 31 else lit)
+                data = ro[at - ro_at:] if ro_at <= at < ro_at + len(ro) else None
+                out[name].append(f"s_add_u32 {m.group(1)}: pc-relative address {at:#x} of {data!r}")
+            else:
+                out[name].append(re.sub(r"//\s*[0-9A-Fa-f]+:", "//", line.strip()))
+            getpc = "s_getpc_b64" in line
+    return out
+
+
+def rodata(co):
+    head = subprocess.check_output([LLVM + "llvm-objdump", "-h", co], text=True)
+    at = int(re.search(r"\.rodata\s+[0-9a-f]+\s+([0-9a-f]+)", head).group(1), 16)
+    dump = subprocess.check_output([LLVM + "llvm-objdump", "-s", "-j", ".rodata", co], text=True)
+    rows = [re.match(r" [0-9a-f]+ ((?:[0-9a-f]+ ?)+) ", l) for l in dump.splitlines()]
+    data = bytes.fromhex("".join(m.group(1).replace(" ", "") for m in rows if m))
+    assert data, ".rodata could not be read"
+    return at, data
+
+
+def main():
+    with tempfile.TemporaryDirectory() as tmp:
+        a, b = kernels(sys.argv[1], tmp, "a"), kernels(sys.argv[2], tmp, "b")
+    bad = 0
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            print(f"ONLY IN {'second' if name not in a else 'first'}: {name}")
+            bad += 1
+        elif a[name] != b[name]:
+            n = sum(x != y for x, y in zip(a[name], b[name])) + abs(len(a[name]) - len(b[name]))
+            print(f"DIFFERS ({n} lines): {name}")
+            bad += 1
+    print(f"{len(a)} symbols in the first, {len(b)} in the second, {len(set(a) & set(b))} in both; {bad} differ")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
