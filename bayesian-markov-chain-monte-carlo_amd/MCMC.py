@@ -59,6 +59,30 @@ class PosteriorPool:
         with Engine(mem="host") as eng:
             return eng.rank_diagnostics(self.samples, **kw)
 
+    def predictive(self, model, data, probs=(0.05, 0.5, 0.95), max_draws=None, engine=None, substeps=None):
+        """Posterior predictive checks of the kept draws against the observation `data`, computed on the GPU (Engine.predictive):
+        the draws are mapped back through `model`'s ODE (float64 RK4, `substeps` steps per output interval — by default the
+        model's own) → dict with, per output time, mean, var, pit, lpd, p_waic_k and the quantiles `probs` of the model series
+        (the credible band), and the totals elpd_waic, p_waic, elpd_waic_se, mean_std2.  max_draws: use an evenly strided subset
+        of at most that many draws (deterministic; the band materialises n * nout * 8 bytes).  engine: an Engine to run on (its
+        model is set here); by default a host-memory engine made for the call."""
+        n, C, d = self.samples.shape
+        q = np.asarray(self.samples.cpu() if hasattr(self.samples, "cpu") else self.samples, dtype=np.float64).reshape(n * C, d)
+        s2 = np.asarray(self.std2.cpu() if hasattr(self.std2, "cpu") else self.std2, dtype=np.float64).reshape(n * C)
+        if max_draws is not None:
+            if int(max_draws) < 1:
+                raise ValueError("max_draws must be >= 1")
+            if int(max_draws) < n * C:
+                idx = (np.arange(int(max_draws), dtype=np.int64) * (n * C)) // int(max_draws)  # evenly strided, no RNG
+                q, s2 = q[idx], s2[idx]
+        S = int(getattr(model, "substeps", 1) if substeps is None else substeps)
+        if engine is not None:
+            engine.set_model(model, S)
+            return engine.predictive(q, s2, data, probs=probs)
+        with Engine(mem="host") as eng:
+            eng.set_model(model, S)
+            return eng.predictive(q, s2, data, probs=probs)
+
     def pooled(self):
         """(d, n_keep*C): every kept draw of every chain, the reference's (d, n) layout."""
         n, C, d = self.samples.shape

@@ -144,6 +144,21 @@ DIAG_RANK_STATS = ("median", "q05", "q95", "hdi_lo", "hdi_hi", "nonfinite", "con
 DIAG_RANK_OUT = ("rhat", "rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail", "ess_q05", "ess_q95", "lags_complete")
 
 
+# include/rsf_predict.h: posterior predictive checks; exported by librsf_hip.so only, bound by load()
+PREDICT_PROTOTYPES = {
+    "rsf_predict_partials": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, POINTER(c_double), POINTER(c_double), POINTER(c_double), _P]),
+    "rsf_predict_finish": (c_int, [c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double),
+                                   POINTER(c_double)]),
+    "rsf_predict_quantiles": (c_int, [c_void_p, c_int64, c_int64, _P, c_int32, POINTER(c_double), POINTER(c_double)]),
+}
+PREDICT_HEAD = 2  # RSF_PREDICT_HEAD: n, sum of sigma^2
+# the partials' fields per output time (RSF_PREDICT_FIELDS), rsf_predict_finish's out_rows and out_totals, in index order
+PREDICT_FIELDS = ("sum_y", "sum_y2", "sum_l", "sum_l2", "sum_exp", "sum_phi", "nonfinite")
+PREDICT_OUT = ("mean", "var", "pit", "lpd", "p_waic_k")
+PREDICT_TOTALS = ("mean_std2", "elpd_waic", "p_waic", "elpd_waic_se")
+PREDICT_MAX_PROBS = 16  # RSF_PREDICT_MAX_PROBS: probabilities per rsf_predict_quantiles call
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -187,9 +202,10 @@ def load():
                                "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
-        for name, (restype, argtypes) in DIAG_PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, argtypes
+        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES):
+            for name, (restype, argtypes) in table.items():
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = restype, argtypes
         if lib.rsf_version() != ABI_VERSION:
             raise RsfError(-1, f"ABI version mismatch: library {lib.rsf_version()}, binding {ABI_VERSION}")
         _lib = lib

@@ -20,9 +20,11 @@
 
 #include "../../include/rsf_abi.h"
 #include "../../include/rsf_diag.h"
+#include "../../include/rsf_predict.h"
 #include "rsf_kernels.h"
 #include "rsf_diag.h"
 #include "rsf_diag_rank.h"
+#include "rsf_predict.h"
 
 using rsf::Consts;
 using namespace rsfk;
@@ -81,6 +83,8 @@ enum Slot : int {
   SLOT_Q = SLOT_Z, SLOT_V = SLOT_U,
   // rsf_pool_summary / _kde / _histogram, rsf_diag_partials, rsf_diag_rank_prepare: the samples or the trace in SLOT_X
   SLOT_X = SLOT_Z, SLOT_GRID = SLOT_U, SLOT_POOL_OUT = SLOT_G,
+  // rsf_predict_partials (std2 in SLOT_U), rsf_predict_quantiles (the series in SLOT_X)
+  SLOT_STD2 = SLOT_U, SLOT_OBS = SLOT_G, SLOT_SERIES = SLOT_TQ,
   // rsf_pool_allgather[_all] / _allreduce_sum[_all] (the reduction is in place in SLOT_SEND)
   SLOT_SEND = SLOT_Z, SLOT_RECV = SLOT_U,
 };
@@ -136,6 +140,7 @@ struct rsf_ctx {
   DevBuf rankws;  // rank workspace (rsf_diag_rank_prepare): the four derived series, then the sort buffers
   int64_t rank_n = 0, rank_C = 0;  // shape of the prepared trace; rank_d 0 = nothing prepared
   int32_t rank_d = 0;
+  DevBuf predict;  // workspace of the posterior predictive checks (rsf_predict_*): per-wave partials and their sums; quantiles
 };
 
 namespace {
@@ -304,6 +309,15 @@ SamplerFn sampler_fn(const rsf_ctx *c, bool replay, bool inject) {
           else return mcmc_kernel<D, DAMP, REPLAY, MODE>;
         });
       });
+    });
+  });
+}
+
+// rsf_predict_partials' solve, void (*)(Consts, PredictArgs): the float64 RK4 tiers, in the float32 mode as well (like init_kernel)
+auto predict_fn(const rsf_ctx *c, int d, bool want_series) {
+  return with<1, 3>(d, [&](auto D) {
+    return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) {
+      return with<true, false>(want_series, [&](auto SERIES) { return predict_kernel<D, DAMP, SERIES>; });
     });
   });
 }
@@ -677,6 +691,7 @@ int rsf_destroy(rsf_ctx *c) {
     release(c->poolws);
     release(c->diag);
     release(c->rankws);
+    release(c->predict);
     release_replay_graph(c);
     if (c->comm) { const Rccl *R = rccl(); if (R) (void)R->comm_destroy(c->comm); }
     for (auto &e : c->ev_done) if (e) (void)hipEventDestroy(e);
@@ -1432,6 +1447,126 @@ int rsf_diag_rank_release(rsf_ctx *c) {
   if (c->rankws.p) HIP_TRY(hipStreamSynchronize(c->stream));
   release(c->rankws);
   c->rank_d = 0;
+  return RSF_OK;
+}
+
+// ---- posterior predictive checks (include/rsf_predict.h) -----------------------------------------
+int rsf_predict_partials(rsf_ctx *c, int64_t n, int32_t d, const double *q, const double *std2, const double *data,
+                         const double *center_y, const double *center_l, double *partials, double *series_out) {
+  RSF_ENTER(c, NEED_MODEL, q && std2 && data && center_y && center_l && partials, "NULL argument");
+  if (n < 1 || (d != 1 && d != 3)) return fail(RSF_ERR_INVALID, "rsf_predict_partials: need n >= 1 and d = 1 or 3");
+  if (c->m.flags & RSF_FLAG_DOP853)
+    return fail(RSF_ERR_UNSUPPORTED, "rsf_predict_partials: a model flagged RSF_FLAG_DOP853 is not supported (the predictive solve is the float64 RK4)");
+  const int64_t nout = c->nout;
+  const int S = c->m.substeps, wpb = c->block / 64;
+  const int64_t grid = (n + c->block - 1) / c->block, nwaves = grid * wpb, nslabs = (nwaves + kPredSlab - 1) / kPredSlab;
+  const int64_t nf = nout * kPredFields;
+  if (nslabs > 65535 || n > INT64_MAX / 64 / nout) return fail(RSF_ERR_INVALID, "rsf_predict_partials: too many draws for one call; split the pool into shards");
+  // the kernel's own chunking of the loading table: its waves' tiles share LDS with the chunk (rsf_predict.h, kPredTableBudget)
+  const int64_t kc = std::min<int64_t>(((int64_t)(kPredTableBudget / sizeof(double)) - 1) / (2 * (int64_t)S), nout - 1);
+  if (kc < 1) return fail(RSF_ERR_UNSUPPORTED, "rsf_predict_partials: substeps=%d does not fit the LDS staging budget", S);
+  int rc;
+  const size_t nb = (size_t)n * sizeof(double), rowb = (size_t)nout * sizeof(double);
+  const double *dq, *dstd2, *ddata;
+  double *dser = nullptr;
+  // (the largest allocation first: it fails before anything is copied)
+  if (series_out && (rc = stage_out(c, SLOT_SERIES, series_out, nb * (size_t)nout, &dser))) {
+    (void)hipGetLastError();
+    return fail(RSF_ERR_NOMEM, "rsf_predict_partials: cannot allocate the series' device copy (%lld x %lld doubles); pass fewer draws per call",
+                (long long)nout, (long long)n);
+  }
+  if ((rc = stage_in(c, SLOT_Q, q, nb * d, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_STD2, std2, nb, &dstd2))) return rc;
+  if ((rc = stage_in(c, SLOT_OBS, data, rowb, &ddata))) return rc;
+  // workspace, doubles: per-wave partials[nwaves][nf] | slab sums[nslabs][nf] | sums[nf] | center_y[nout] | center_l[nout]
+  const int64_t o_slab = nwaves * nf, o_sum = o_slab + nslabs * nf, o_cy = o_sum + nf, o_cl = o_cy + nout, total = o_cl + nout;
+  if ((rc = ensure(c->predict, (size_t)total * sizeof(double)))) return rc;
+  double *w = (double *)c->predict.p;
+  HIP_TRY(hipMemcpyAsync(w + o_cy, center_y, rowb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(w + o_cl, center_l, rowb, hipMemcpyHostToDevice, c->stream));
+  Consts K = make_consts(c, nullptr);
+  K.kc = (int32_t)kc;
+  K.nchunks = (int32_t)((nout - 1 + kc - 1) / kc);
+  PredictArgs A{};
+  A.n = n; A.q = dq; A.std2 = dstd2; A.data = ddata; A.cy = w + o_cy; A.cl = w + o_cl; A.part = w; A.series = dser;
+  A.tab_doubles = (int32_t)((2 * S * kc + 1 + 1) & ~(int64_t)1);
+  const size_t lds = ((size_t)A.tab_doubles + (size_t)wpb * kPredWaveDoubles) * sizeof(double);
+  if ((rc = launch(c, predict_fn(c, d, dser != nullptr), (unsigned)grid, c->block, lds, K, A))) return rc;
+  const unsigned fb = (unsigned)((nf + 255) / 256);
+  hipLaunchKernelGGL(predict_sum_kernel, dim3(fb, (unsigned)nslabs), dim3(256), 0, c->stream, nwaves, (int64_t)kPredSlab, nf, (const double *)w, w + o_slab);
+  hipLaunchKernelGGL(predict_sum_kernel, dim3(fb, 1), dim3(256), 0, c->stream, nslabs, nslabs, nf, (const double *)(w + o_slab), w + o_sum);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> h((size_t)nf);
+  HIP_TRY(hipMemcpyAsync(h.data(), w + o_sum, (size_t)nf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = copy_back(c, SLOT_SERIES, series_out, nb * (size_t)nout))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  partials[0] = (double)n;
+  partials[1] = h[kPredFields - 1];  // sum of sigma^2: the same in every row, taken from row 0
+  for (int64_t k = 0; k < nout; ++k)
+    for (int f = 0; f < RSF_PREDICT_FIELDS; ++f) partials[RSF_PREDICT_HEAD + k * RSF_PREDICT_FIELDS + f] = h[(size_t)(k * kPredFields + f)];
+  return RSF_OK;
+}
+
+int rsf_predict_finish(int64_t n_rows, const double *partials, const double *center_y, const double *center_l, double *out_rows,
+                       double *out_totals) {
+  if (!partials || !center_y || !center_l || !out_rows || !out_totals) return fail(RSF_ERR_INVALID, "rsf_predict_finish: NULL argument");
+  if (n_rows < 1) return fail(RSF_ERR_INVALID, "rsf_predict_finish: n_rows < 1");
+  const double n = partials[0];
+  double elpd = 0.0, pw = 0.0;
+  for (int64_t k = 0; k < n_rows; ++k) {
+    const double *p = partials + RSF_PREDICT_HEAD + k * RSF_PREDICT_FIELDS;
+    double *o = out_rows + k * RSF_PREDICT_OUT;
+    bool finite = p[RSF_PREDICT_NONFINITE] == 0.0 && std::isfinite(center_y[k]) && std::isfinite(center_l[k]);
+    for (int f = 0; f < RSF_PREDICT_NONFINITE; ++f) finite = finite && std::isfinite(p[f]);
+    if (!finite) {  // a non-finite draw: every statistic of this output time is NaN
+      for (int f = 0; f < RSF_PREDICT_OUT; ++f) o[f] = NAN;
+    } else {
+      const double my = p[RSF_PREDICT_SUM_Y] / n, ml = p[RSF_PREDICT_SUM_L] / n;
+      o[RSF_PREDICT_MEAN] = center_y[k] + my;
+      o[RSF_PREDICT_VAR] = (p[RSF_PREDICT_SUM_Y2] - p[RSF_PREDICT_SUM_Y] * my) / (n - 1.0);
+      o[RSF_PREDICT_PIT] = p[RSF_PREDICT_SUM_PHI] / n;
+      o[RSF_PREDICT_LPD] = center_l[k] + std::log(p[RSF_PREDICT_SUM_EXP] / n);
+      o[RSF_PREDICT_P_WAIC] = (p[RSF_PREDICT_SUM_L2] - p[RSF_PREDICT_SUM_L] * ml) / (n - 1.0);
+    }
+    elpd += o[RSF_PREDICT_LPD] - o[RSF_PREDICT_P_WAIC];
+    pw += o[RSF_PREDICT_P_WAIC];
+  }
+  const double nr = (double)n_rows, me = elpd / nr;
+  double ss = 0.0;
+  for (int64_t k = 0; k < n_rows; ++k) {
+    const double e = out_rows[k * RSF_PREDICT_OUT + RSF_PREDICT_LPD] - out_rows[k * RSF_PREDICT_OUT + RSF_PREDICT_P_WAIC] - me;
+    ss += e * e;
+  }
+  out_totals[RSF_PREDICT_MEAN_STD2] = partials[1] / n;
+  out_totals[RSF_PREDICT_ELPD_WAIC] = elpd;
+  out_totals[RSF_PREDICT_P_WAIC_TOTAL] = pw;
+  out_totals[RSF_PREDICT_ELPD_WAIC_SE] = std::sqrt(nr * (ss / (nr - 1.0)));
+  return RSF_OK;
+}
+
+int rsf_predict_quantiles(rsf_ctx *c, int64_t n, int64_t nout, const double *series, int32_t n_probs, const double *probs, double *out) {
+  RSF_ENTER(c, NEED_NOTHING, series && probs && out, "NULL argument");
+  if (n < 1 || n >= (INT64_C(1) << 31) || nout < 1 || nout > INT32_MAX || n > INT64_MAX / 8 / nout)
+    return fail(RSF_ERR_INVALID, "rsf_predict_quantiles: need 1 <= n < 2^31 draws and 1 <= nout rows");
+  if (n_probs < 1 || n_probs > RSF_PREDICT_MAX_PROBS)
+    return fail(RSF_ERR_INVALID, "rsf_predict_quantiles: n_probs outside 1..%d", RSF_PREDICT_MAX_PROBS);
+  PredictProbs P{};
+  for (int i = 0; i < n_probs; ++i) {
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return fail(RSF_ERR_INVALID, "rsf_predict_quantiles: probs[%d] is outside [0, 1]", i);
+    P.p[i] = probs[i];
+  }
+  int rc;
+  const double *ds;
+  if ((rc = stage_in(c, SLOT_X, series, (size_t)n * (size_t)nout * sizeof(double), &ds))) {
+    (void)hipGetLastError();
+    return fail(RSF_ERR_NOMEM, "rsf_predict_quantiles: cannot allocate the series' device copy (%lld x %lld doubles)", (long long)nout, (long long)n);
+  }
+  const size_t ob = (size_t)n_probs * (size_t)nout * sizeof(double);
+  if ((rc = ensure(c->poolws, ob))) return rc;
+  hipLaunchKernelGGL(predict_select_kernel, dim3((unsigned)nout), dim3(kPredSelectThreads), 0, c->stream, n, nout, ds, (int)n_probs, P, (double *)c->poolws.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, c->poolws.p, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return RSF_OK;
 }
 

@@ -1,0 +1,285 @@
+// rsf_predict.h — posterior predictive checks of pooled draws (include/rsf_predict.h), the kernels:
+//   predict_kernel         one lane per draw: the float64 RK4 tier code driven exactly as init_kernel drives it, and at every
+//                          completed output sample the wave's 64 values y_ik go through an LDS tile to the lanes that reduce them;
+//   predict_sum_kernel     fixed-order sum of the per-wave partials, in two levels (slabs of waves, then the slabs);
+//   predict_select_kernel  exact order statistics of every row of a materialised series by radix select, then NumPy's _lerp.
+// No float atomics; every sum across lanes, waves and workgroups has a fixed order, so the same draws give the same bits.
+//
+// The per-sample hook.  A wave parks its 64 samples of an output time in one slot of a ring of kPredSlots slots (64 doubles
+// each) — a conflict-free store, lane = bank.  Once a trip of RK4 steps is done and at least kPredTile slots are filled, the
+// wave reads them back transposed: lane l = 8 g + m owns output time (tile's first + g) and the eight draws m + 8 ((t + g) & 7),
+// t = 0..7 — rotated by g so that the 64 lanes of one read hit 64 different doubles.  Each lane evaluates l, exp and erfc for its
+// eight draws with the draws' constants (read from LDS, written once per launch), accumulates the seven sums privately, and
+// three DPP butterfly steps (quad_perm x2, row_half_mirror) leave the totals of the eight lanes in all of them; lane 8 g + f
+// then stores field f of time g: one 512-byte row store per tile.  Per output sample that is one element evaluation per lane
+// and 21/8 DPP pairs per field set, instead of six full-wave reductions.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "rsf_kernels.h"
+#include "rsf_diag_rank.h"
+
+namespace rsfk {
+
+constexpr int kPredFields = 8;   // per (wave, output time) in the workspace: the seven of RSF_PREDICT_FIELDS + sum of sigma^2
+constexpr int kPredTile = 8;     // output times reduced per flush: 8 times x 8 lanes
+constexpr int kPredSlots = 16;   // ring of parked samples: up to kPredTile - 1 left over + one trip's worth (<= 8)
+constexpr int kPredParams = 4;   // per draw in LDS: -1/2 log(2 pi s2), 1/(2 s2), 1/sqrt(2 s2), s2
+constexpr int kPredWaveDoubles = kPredSlots * 64 + kPredParams * 64;  // 10 KiB per wave
+// LDS of a predict launch: the loading table chunk, then kPredWaveDoubles per wave.  Two workgroups of four waves per CU
+// (160 KiB): 40 KiB of wave areas + at most this much table; nsteps 2000 (32 KB of loading values) stays resident.
+constexpr size_t kPredTableBudget = 38 * 1024;
+constexpr int kPredSlab = 64;    // waves per slab of the first level of predict_sum_kernel
+
+struct PredictArgs {
+  int64_t n;
+  const double *q;     // [n][D], the C ABI's layout
+  const double *std2;  // [n]
+  const double *data, *cy, *cl;  // [nout]
+  double *part;        // [waves][nout][kPredFields]
+  double *series;      // WANT_SERIES: [nout][n]
+  int32_t tab_doubles; // offset of the wave areas behind the table chunk
+};
+
+template <int CTRL>
+__device__ __forceinline__ double pred_dpp(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+// the sum over an aligned group of eight lanes, in all eight (a + b == b + a bit for bit, so the butterfly agrees everywhere)
+__device__ __forceinline__ double pred_sum8(double v) {
+  v += pred_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += pred_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += pred_dpp<0x141>(v);  // row_half_mirror: the other quad of the eight
+  return v;
+}
+
+// Reduces `count` (<= kPredTile) parked output times starting at ring slot `head`, absolute time k0, and stores their fields.
+__device__ __forceinline__ void predict_flush(const double *ring, const double *par, const PredictArgs &A, int nout, int head, int count, int k0,
+                                              int nvalid, double *wave_part) {
+  const unsigned lane = threadIdx.x & 63;
+  const int g = (int)(lane >> 3), m = (int)(lane & 7);
+  const bool mine = g < count;
+  const int k = mine ? k0 + g : k0;
+  const double obs = A.data[k], cy = A.cy[k], cl = A.cl[k];
+  const double *row = ring + ((head + g) & (kPredSlots - 1)) * 64;
+  double s[kPredFields];
+#pragma unroll
+  for (int f = 0; f < kPredFields; ++f) s[f] = 0.0;
+#pragma unroll 1
+  for (int t = 0; t < 8; ++t) {
+    const int i = m + 8 * ((t + g) & 7);
+    const double y = row[i];
+    const double lognorm = par[i], h = par[64 + i], isr = par[128 + i], s2 = par[192 + i];
+    const bool valid = i < nvalid, use = valid && isfinite(y);
+    const double ys = use ? y : cy;
+    const double dy = ys - cy, r = obs - ys;
+    const double dl = (lognorm - (r * r) * h) - cl;
+    const double e = exp(dl), phi = 0.5 * erfc(-(r * isr));
+    s[0] += use ? dy : 0.0;
+    s[1] += use ? dy * dy : 0.0;
+    s[2] += use ? dl : 0.0;
+    s[3] += use ? dl * dl : 0.0;
+    s[4] += use ? e : 0.0;
+    s[5] += use ? phi : 0.0;
+    s[6] += (valid && !use) ? 1.0 : 0.0;
+    s[7] += valid ? s2 : 0.0;
+  }
+  double out = 0.0;
+#pragma unroll
+  for (int f = 0; f < kPredFields; ++f) {
+    const double tot = pred_sum8(s[f]);
+    out = m == f ? tot : out;
+  }
+  if (mine) wave_part[(int64_t)k * kPredFields + m] = out;
+}
+
+template <int D, bool DAMP, bool WANT_SERIES>
+__global__ void __launch_bounds__(kMaxBlock, kMinBlocks) predict_kernel(Consts K, PredictArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  constexpr int NU = 8;
+  static_assert(rsf::kResync % NU == 0, "the resync test looks at the first step of a trip");
+  static_assert(NU <= kPredSlots - (kPredTile - 1), "a trip's samples fit the ring behind the left-over ones");
+  const unsigned t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + t;
+  const int64_t wave_first = i - lane;
+  const bool active = i < A.n;
+  const int nvalid = (int)(A.n - wave_first < 64 ? (A.n - wave_first > 0 ? A.n - wave_first : 0) : 64);
+  double *ring = lds + A.tab_doubles + wave * kPredWaveDoubles, *par = ring + kPredSlots * 64;
+  double *wave_part = A.part + ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * (int64_t)K.nout * kPredFields;
+  double pq[3] = {1000.0, K.a_def, K.b_def};  // lanes past the last draw carry a harmless Dc
+  double s2 = 1.0;
+  if (active) {
+    pq[0] = A.q[i * D];
+    if (D == 3) { pq[1] = A.q[i * D + 1]; pq[2] = A.q[i * D + 2]; }
+    s2 = A.std2[i];
+  }
+  par[lane] = -0.5 * log(6.283185307179586476925 * s2);
+  par[64 + lane] = 0.5 / s2;
+  par[128 + lane] = 1.0 / sqrt(2.0 * s2);
+  par[192 + lane] = s2;
+  const rsf::Lane L = rsf::make_lane<DAMP>(pq[0], pq[1], pq[2], K);
+  rsf::State st = rsf::initial_state(pq[0], L, K);
+  double dsum = 0.0;
+  // ring of parked samples: `cnt` filled slots from `head`, the first of them output time `kt` (all wave-uniform)
+  int head = 0, cnt = 0, kt = 0, kabs = 0;
+  auto park = [&](double y) {
+    ring[((head + cnt) & (kPredSlots - 1)) * 64 + lane] = y;
+    if (WANT_SERIES && active) A.series[(int64_t)kabs * A.n + i] = y;
+    ++cnt;
+    ++kabs;
+  };
+  auto flush = [&](int count) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    predict_flush(ring, par, A, K.nout, head, count, kt, nvalid, wave_part);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    head = (head + count) & (kPredSlots - 1);
+    cnt -= count;
+    kt += count;
+  };
+  park(0.0);  // y_i0 = 0
+  int phase = 0;  // RK4 steps since the last output sample (wave-uniform)
+  for (int k0 = 1; k0 < K.nout; k0 += K.kc) {
+    const int kn = min(K.kc, K.nout - k0);
+    rsf::stage_chunk(lds, K, k0, kn);
+    const int nsteps = K.S * kn;
+    // (every lane of the wave integrates, so that the wave-uniform tier decisions see whole waves)
+    int tier = rsf::start_tier(L, K);
+    int r = 0;
+    auto trip = [&](auto tier_tag, auto nu_tag) {  // one trip of tier T, NUT steps; a tripped guard: that lane redoes it in full
+      constexpr int T = decltype(tier_tag)::value, NUT = decltype(nu_tag)::value;
+      const double *v = lds + 2 * r;
+      rsf::Lane Lt = L;
+      rsf::set_tier<T>(Lt);
+      const rsf::State save = st;
+      double dv[NUT];
+      rsf::tier_enter<DAMP, T>(st, Lt);
+      const bool bad = rsf::trip_fast<DAMP, T, NUT>(v, Lt, K, st, dv);
+      rsf::tier_leave<DAMP, T>(st, Lt);
+      const bool any_bad = rsf::ballot(bad) != 0;
+      if (__builtin_expect(any_bad, 0)) {
+        if (bad) {  // back to the trip's start (the plain state: saved before tier_enter) and through it with full evaluations
+          st = save;
+          rsf::trip_cold_plain<DAMP, NUT>(v, L, K, st, dv);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NUT; ++j) {
+        dsum += dv[j];
+        if (++phase == K.S) { phase = 0; park(dsum * L.cv); dsum = 0.0; }
+      }
+      return any_bad;
+    };
+    for (; r + NU <= nsteps; r += NU) {
+      if ((r & (rsf::kResync - 1)) == 0) rsf::eval_full(st.ms, st.x, L, K, st.w, st.rx);
+      bool any_bad;
+      if (tier == rsf::TIGHT) any_bad = trip(std::integral_constant<int, rsf::TIGHT>{}, std::integral_constant<int, NU>{});
+      else if (tier == rsf::NARROW) any_bad = trip(std::integral_constant<int, rsf::NARROW>{}, std::integral_constant<int, NU>{});
+      else any_bad = trip(std::integral_constant<int, rsf::WIDE>{}, std::integral_constant<int, NU>{});
+      if (any_bad && tier < rsf::WIDE) ++tier;
+      if (cnt >= kPredTile) flush(kPredTile);
+    }
+    for (; r < nsteps; ++r) {  // fewer than NU steps left in the chunk: one at a time
+      if ((r & (rsf::kResync - 1)) == 0) rsf::eval_full(st.ms, st.x, L, K, st.w, st.rx);
+      trip(std::integral_constant<int, rsf::WIDE>{}, std::integral_constant<int, 1>{});
+      if (cnt >= kPredTile) flush(kPredTile);
+    }
+  }
+  while (cnt > 0) flush(cnt < kPredTile ? cnt : kPredTile);
+}
+
+// out[s][f] = sum over the blocks b of slab s (b = s * per .. min(nblocks, (s + 1) * per) - 1, in order) of part[b][f]
+__global__ void __launch_bounds__(256) predict_sum_kernel(int64_t nblocks, int64_t per, int64_t nf, const double *__restrict__ part,
+                                                          double *__restrict__ out) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t b0 = (int64_t)blockIdx.y * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
+  double t = 0.0;
+  for (int64_t b = b0; b < b1; ++b) t += part[b * nf + f];
+  out[(int64_t)blockIdx.y * nf + f] = t;
+}
+
+// ---- exact quantiles of every row ---------------------------------------------------------------------------------------
+constexpr int kPredSelectThreads = 256;
+constexpr int kPredMaxRanks = 32;  // two order statistics per probability, RSF_PREDICT_MAX_PROBS = 16
+
+struct PredictProbs {
+  double p[kPredMaxRanks / 2];
+};
+
+// One workgroup per row of series[nout][n].  Keys are rank_key's order-preserving map; eight passes of eight bits from the
+// top, each a read of the row: per target rank a 256-bin histogram (LDS, integer atomics) of the keys that agree with the
+// rank's prefix so far; one thread per rank then walks its bins to the digit that holds the rank.  Both order statistics of
+// np.quantile's "linear" method are found per probability, then NumPy's _lerp (the operations of rank_quantile).
+__global__ void __launch_bounds__(kPredSelectThreads)
+predict_select_kernel(int64_t n, int64_t nout, const double *__restrict__ series, int nprobs, PredictProbs P, double *__restrict__ out) {
+  __shared__ uint32_t hist[kPredMaxRanks][256];
+  __shared__ uint64_t prefix[kPredMaxRanks];
+  __shared__ uint32_t want[kPredMaxRanks];
+  __shared__ uint32_t nonfinite;
+  const int nr = 2 * nprobs;
+  const int64_t k = blockIdx.x;
+  const double *row = series + k * n;
+  const unsigned t = threadIdx.x;
+  if (t < (unsigned)nr) {
+    const double h = (double)(n - 1) * P.p[t >> 1];
+    int64_t lo = (int64_t)floor(h);
+    lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+    want[t] = (uint32_t)((t & 1) ? (lo + 1 < n ? lo + 1 : n - 1) : lo);
+    prefix[t] = 0;
+  }
+  if (t == 0) nonfinite = 0;
+  for (int pass = 0; pass < 8; ++pass) {
+    const int shift = 56 - 8 * pass;
+    const uint64_t mask = pass == 0 ? 0ull : ~0ull << (shift + 8);
+    for (int e = t; e < nr * 256; e += kPredSelectThreads) (&hist[0][0])[e] = 0;
+    __syncthreads();
+    bool bad = false;
+    for (int64_t j = t; j < n; j += kPredSelectThreads) {
+      const double v = row[j];
+      bad = bad || !isfinite(v);
+      const uint64_t key = rank_key(v);
+      const unsigned dig = (unsigned)(key >> shift) & 255u;
+      if (pass == 0) {
+        atomicAdd(&hist[0][dig], 1u);  // no prefix yet: every rank shares one histogram
+      } else {
+        for (int q = 0; q < nr; ++q)
+          if ((key & mask) == prefix[q]) atomicAdd(&hist[q][dig], 1u);
+      }
+    }
+    if (pass == 0 && bad) nonfinite = 1;
+    __syncthreads();
+    if (t < (unsigned)nr) {
+      const uint32_t *hq = hist[pass == 0 ? 0 : t];
+      uint32_t below = 0, w = want[t];
+      int dig = 0;
+      for (; dig < 255; ++dig) {
+        const uint32_t c = hq[dig];
+        if (below + c > w) break;
+        below += c;
+      }
+      want[t] = w - below;
+      prefix[t] |= (uint64_t)dig << shift;
+    }
+    __syncthreads();
+  }
+  if (t < (unsigned)nprobs) {
+#pragma clang fp contract(off)  // bit for bit NumPy: no fused multiply-add
+    const double prob = P.p[t];
+    const double h = (double)(n - 1) * prob;
+    const double fl = floor(h);
+    const double g = h - fl;
+    const double a = rank_value(prefix[2 * t]), b = rank_value(prefix[2 * t + 1]);
+    const double diff = b - a;
+    const double v = g < 0.5 ? a + diff * g : b - diff * (1.0 - g);
+    out[(int64_t)t * nout + k] = nonfinite ? __longlong_as_double(0x7ff8000000000000ll) : v;
+  }
+}
+
+}  // namespace rsfk

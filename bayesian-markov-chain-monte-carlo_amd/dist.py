@@ -121,6 +121,13 @@ def allreduce_diag_partials(partials, group=None, device=None):
     return t
 
 
+def allreduce_predictive_partials(partials, group=None, device=None):
+    """Per-rank `Engine.predictive_partials` (every rank's own shard of the pooled draws, the same centres) → the partials of
+    all ranks' draws: one all-reduce SUM of PREDICT_HEAD + nout * len(PREDICT_FIELDS) doubles.  Feed the result to
+    `Engine.predictive_finish`."""
+    return allreduce_diag_partials(partials, group=group, device=device)
+
+
 def pool_to_chain_major(pool):
     """(G, n_keep, C_local, d) → (n_keep, G*C_local, d): global chain id = g*C_local + c."""
     G, n, C, d = pool.shape

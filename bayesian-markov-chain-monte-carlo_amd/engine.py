@@ -473,6 +473,141 @@ class Engine:
             res.append(r)
         return res
 
+    # -- posterior predictive checks of pooled draws (include/rsf_predict.h) ---------------------
+    def _predict_args(self, q, std2, data):
+        self._need_model()
+        q, std2, data = self._in(q), self._in(std2), self._in(data)
+        if q.ndim == 1:
+            q = q.reshape(-1, 1)
+        if q.ndim != 2 or int(q.shape[1]) not in (1, 3):
+            raise ValueError("draws are (n,) or (n, d) with d = 1 (Dc) or 3 (Dc, a, b)")
+        n = int(q.shape[0])
+        if n < 1:
+            raise ValueError("no draws")
+        if std2.ndim != 1 or int(std2.shape[0]) != n:
+            raise ValueError(f"std2 has shape {tuple(std2.shape)}, the draws are {n}")
+        if data.ndim != 1 or int(data.shape[0]) != self.nout:
+            raise ValueError(f"data has shape {tuple(data.shape)}, the model produces {self.nout} samples")
+        return q, std2, data, n, int(q.shape[1])
+
+    def _predict_centers(self, center_y, center_l):
+        c = []
+        for v in (center_y, center_l):
+            v = np.ascontiguousarray(np.asarray(v.cpu() if hasattr(v, "cpu") else v, dtype=np.float64))
+            if v.shape != (self.nout,):
+                raise ValueError(f"a centre has shape {v.shape}, the model produces {self.nout} samples")
+            c.append(v)
+        return c
+
+    def predictive_partials(self, q, std2, data, center_y, center_l, return_series=False):
+        """rsf_predict_partials: one forward solve per draw (q (n,) or (n, d), std2 (n,)) and the additive partials of the
+        predictive statistics about the centres center_y, center_l (nout,) → (PREDICT_HEAD + nout * len(PREDICT_FIELDS),)
+        float64 on the host; with return_series also the series (nout, n) in this engine's memory space.  Partials of disjoint
+        shards of a pool taken about the same centres add (dist.allreduce_predictive_partials)."""
+        q, std2, data, n, d = self._predict_args(q, std2, data)
+        cy, cl = self._predict_centers(center_y, center_l)
+        series = None
+        if return_series:
+            try:
+                series = self._empty((self.nout, n))
+            except (MemoryError, RuntimeError) as e:
+                raise MemoryError(f"cannot allocate the predictive series ({self.nout} x {n} doubles = {8 * self.nout * n} bytes); "
+                                  "pass fewer draws (max_draws)") from e
+        out = np.empty(_abi.PREDICT_HEAD + self.nout * len(_abi.PREDICT_FIELDS))
+        dbl = ctypes.POINTER(ctypes.c_double)
+        try:
+            _abi.check(self.lib, self.lib.rsf_predict_partials(self._ctx, n, d, self._ptr(q), self._ptr(std2), self._ptr(data),
+                                                               cy.ctypes.data_as(dbl), cl.ctypes.data_as(dbl), out.ctypes.data_as(dbl),
+                                                               self._ptr(series)))
+        except _abi.RsfError as e:
+            if e.code == -4:  # RSF_ERR_NOMEM
+                raise _abi.RsfError(e.code, f"{e}; pass fewer draws (max_draws)") from e
+            raise
+        return (out, series) if return_series else out
+
+    def predictive_finish(self, partials, center_y, center_l):
+        """rsf_predict_finish (host only): the statistics of summed partials → dict of (nout,) arrays mean, var, pit, lpd,
+        p_waic_k and the totals mean_std2, elpd_waic, p_waic, elpd_waic_se, n."""
+        part = np.ascontiguousarray(np.asarray(partials.cpu() if hasattr(partials, "cpu") else partials, dtype=np.float64)).reshape(-1)
+        nf = len(_abi.PREDICT_FIELDS)
+        if part.size <= _abi.PREDICT_HEAD or (part.size - _abi.PREDICT_HEAD) % nf:
+            raise ValueError(f"partials have {part.size} entries, not PREDICT_HEAD + rows * {nf}")
+        rows = (part.size - _abi.PREDICT_HEAD) // nf
+        cy = np.ascontiguousarray(np.asarray(center_y, dtype=np.float64))
+        cl = np.ascontiguousarray(np.asarray(center_l, dtype=np.float64))
+        if cy.shape != (rows,) or cl.shape != (rows,):
+            raise ValueError(f"the centres have shapes {cy.shape}, {cl.shape}, the partials {rows} rows")
+        out = np.empty((rows, len(_abi.PREDICT_OUT)))
+        tot = np.empty(len(_abi.PREDICT_TOTALS))
+        dbl = ctypes.POINTER(ctypes.c_double)
+        _abi.check(self.lib, self.lib.rsf_predict_finish(rows, part.ctypes.data_as(dbl), cy.ctypes.data_as(dbl), cl.ctypes.data_as(dbl),
+                                                         out.ctypes.data_as(dbl), tot.ctypes.data_as(dbl)))
+        res = {name: np.ascontiguousarray(out[:, j]) for j, name in enumerate(_abi.PREDICT_OUT)}
+        res.update({name: float(v) for name, v in zip(_abi.PREDICT_TOTALS, tot)})
+        res["n"] = int(part[0])
+        return res
+
+    def predictive_quantiles(self, series, probs):
+        """rsf_predict_quantiles: np.quantile(series, probs, axis=1) (method "linear", exact) of a series (nout, n) in this
+        engine's memory space → (len(probs), nout) float64 on the host."""
+        probs = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if probs.ndim != 1 or probs.size < 1:
+            raise ValueError("probs is a non-empty sequence of probabilities")
+        if not np.all((probs >= 0.0) & (probs <= 1.0)):
+            raise ValueError("probabilities lie in [0, 1]")
+        x = self._in(series)
+        if x.ndim != 2 or int(x.shape[1]) < 1 or int(x.shape[0]) < 1:
+            raise ValueError("a series is (nout, n)")
+        rows, n = int(x.shape[0]), int(x.shape[1])
+        out = np.empty((probs.size, rows))
+        dbl = ctypes.POINTER(ctypes.c_double)
+        for j in range(0, probs.size, _abi.PREDICT_MAX_PROBS):
+            pj = np.ascontiguousarray(probs[j:j + _abi.PREDICT_MAX_PROBS])
+            oj = np.empty((pj.size, rows))
+            _abi.check(self.lib, self.lib.rsf_predict_quantiles(self._ctx, n, rows, self._ptr(x), int(pj.size), pj.ctypes.data_as(dbl),
+                                                                oj.ctypes.data_as(dbl)))
+            out[j:j + pj.size] = oj
+        return out
+
+    def predictive(self, q, std2, data, probs=(), center=None, return_series=False):
+        """Posterior predictive checks of n draws against the observation `data`: per output time the model series' mean and
+        variance over the draws, the probability integral transform of the observation (pit), the log pointwise predictive
+        density (lpd) and the WAIC penalty (p_waic_k); the totals mean_std2, elpd_waic, p_waic, elpd_waic_se; with `probs` the
+        exact quantiles (len(probs), nout) of the series over the draws, the credible band.  center = (center_y, center_l)
+        (default: the series at the draws' mean parameter vector, and its log density with the mean sigma^2).  With probs or
+        return_series the series (nout, n) is materialised: n * nout * 8 bytes."""
+        q, std2, data, n, d = self._predict_args(q, std2, data)
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if probs.ndim != 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
+            raise ValueError("probs is a sequence of probabilities in [0, 1]")
+
+        def host(x):
+            return np.asarray(x.cpu() if hasattr(x, "cpu") else x, dtype=np.float64)
+
+        if center is None:
+            qm = host(q.mean(0)).reshape(d)
+            _, acc = self.forward(qm[:1], a=qm[1:2] if d == 3 else None, b=qm[2:3] if d == 3 else None)
+            cy = host(acc).reshape(self.nout)
+            ms = float(host(std2).mean())
+            cl = -0.5 * np.log(2.0 * np.pi * ms) - (host(data) - cy) ** 2 / (2.0 * ms)
+            if not (np.isfinite(cy).all() and np.isfinite(cl).all()):
+                raise ValueError("the series at the draws' mean parameters is not finite; pass center=(center_y, center_l)")
+        else:
+            cy, cl = center
+        cy, cl = self._predict_centers(cy, cl)
+        want_series = bool(return_series) or probs.size > 0
+        part = self.predictive_partials(q, std2, data, cy, cl, return_series=want_series)
+        series = None
+        if want_series:
+            part, series = part
+        res = self.predictive_finish(part, cy, cl)
+        res.update(partials=part, center_y=cy, center_l=cl)
+        if probs.size:
+            res["probs"], res["quantiles"] = probs, self.predictive_quantiles(series, probs)
+        if return_series:
+            res["series"] = series
+        return res
+
     # -- multi-GPU posterior pool through the C ABI (RCCL bound inside the library; SURVEY §8e) -----
     def comm_unique_id(self):
         """Rank 0: the 128-byte id every rank passes to comm_init (send it over any channel)."""
