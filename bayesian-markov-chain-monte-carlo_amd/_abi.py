@@ -159,6 +159,17 @@ PREDICT_TOTALS = ("mean_std2", "elpd_waic", "p_waic", "elpd_waic_se")
 PREDICT_MAX_PROBS = 16  # RSF_PREDICT_MAX_PROBS: probabilities per rsf_predict_quantiles call
 
 
+# include/rsf_psis.h: PSIS-LOO on the predictive series; exported by librsf_hip.so only, bound by load()
+PSIS_PROTOTYPES = {
+    "rsf_predict_psis_loo": (c_int, [c_void_p, c_int64, c_int64, _P, _P, _P, c_double, POINTER(c_double)]),
+    "rsf_predict_psis_finish": (c_int, [c_int64, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+}
+# rsf_predict_psis_loo's out_rows and rsf_predict_psis_finish's out_totals, in index order
+PSIS_OUT = ("elpd_loo_k", "pareto_k", "n_tail", "weight_ess")
+PSIS_TOTALS = ("elpd_loo", "p_loo", "elpd_loo_se", "k_threshold", "n_high_k", "max_pareto_k")
+PSIS_MAX_TAIL = 8192  # RSF_PSIS_MAX_TAIL: largest ceil(min(0.2 n, 3 sqrt(n / r_eff)))
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -202,7 +213,7 @@ def load():
                                "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
-        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES):
+        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

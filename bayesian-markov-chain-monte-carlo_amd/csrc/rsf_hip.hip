@@ -25,6 +25,7 @@
 #include "rsf_diag.h"
 #include "rsf_diag_rank.h"
 #include "rsf_predict.h"
+#include "rsf_psis.h"
 
 using rsf::Consts;
 using namespace rsfk;
@@ -84,6 +85,7 @@ enum Slot : int {
   // rsf_pool_summary / _kde / _histogram, rsf_diag_partials, rsf_diag_rank_prepare: the samples or the trace in SLOT_X
   SLOT_X = SLOT_Z, SLOT_GRID = SLOT_U, SLOT_POOL_OUT = SLOT_G,
   // rsf_predict_partials (std2 in SLOT_U), rsf_predict_quantiles (the series in SLOT_X)
+  // rsf_predict_psis_loo: the series in SLOT_SERIES, std2 in SLOT_STD2, the observation in SLOT_OBS
   SLOT_STD2 = SLOT_U, SLOT_OBS = SLOT_G, SLOT_SERIES = SLOT_TQ,
   // rsf_pool_allgather[_all] / _allreduce_sum[_all] (the reduction is in place in SLOT_SEND)
   SLOT_SEND = SLOT_Z, SLOT_RECV = SLOT_U,
@@ -1567,6 +1569,75 @@ int rsf_predict_quantiles(rsf_ctx *c, int64_t n, int64_t nout, const double *ser
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, c->poolws.p, ob, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return RSF_OK;
+}
+
+int rsf_predict_psis_loo(rsf_ctx *c, int64_t n, int64_t nout, const double *series, const double *std2, const double *data, double r_eff,
+                         double *out_rows) {
+  RSF_ENTER(c, NEED_NOTHING, series && std2 && data && out_rows, "NULL argument");
+  if (n < 1 || n >= (INT64_C(1) << 31) || nout < 1 || nout > INT32_MAX || n > INT64_MAX / 8 / nout)
+    return fail(RSF_ERR_INVALID, "rsf_predict_psis_loo: need 1 <= n < 2^31 draws and 1 <= nout rows");
+  if (!(std::isfinite(r_eff) && r_eff > 0.0)) return fail(RSF_ERR_INVALID, "rsf_predict_psis_loo: r_eff must be finite and > 0");
+  const double tl = std::ceil(std::min(0.2 * (double)n, 3.0 * std::sqrt((double)n / r_eff)));
+  if (tl > (double)RSF_PSIS_MAX_TAIL)
+    return fail(RSF_ERR_UNSUPPORTED, "rsf_predict_psis_loo: a tail of %.0f draws exceeds RSF_PSIS_MAX_TAIL = %d (n = %lld, r_eff = %g)", tl,
+                RSF_PSIS_MAX_TAIL, (long long)n, r_eff);
+  static_assert(kPsisMaxTail == RSF_PSIS_MAX_TAIL && kPsisOut == RSF_PSIS_OUT, "csrc/rsf_psis.h and include/rsf_psis.h agree");
+  int rc;
+  const size_t nb = (size_t)n * sizeof(double), rowb = (size_t)nout * sizeof(double);
+  const double *ds, *dstd2, *ddata;
+  // (the largest allocation first: it fails before anything is copied)
+  if ((rc = stage_in(c, SLOT_SERIES, series, nb * (size_t)nout, &ds))) {
+    (void)hipGetLastError();
+    return fail(RSF_ERR_NOMEM, "rsf_predict_psis_loo: cannot allocate the series' device copy (%lld x %lld doubles)", (long long)nout, (long long)n);
+  }
+  if ((rc = stage_in(c, SLOT_STD2, std2, nb, &dstd2))) return rc;
+  if ((rc = stage_in(c, SLOT_OBS, data, rowb, &ddata))) return rc;
+  // workspace: the draws' constants [2][n] in c->predict, the rows [nout][RSF_PSIS_OUT] in c->poolws
+  const size_t ob = (size_t)nout * RSF_PSIS_OUT * sizeof(double);
+  if ((rc = ensure(c->predict, 2 * nb))) return rc;
+  if ((rc = ensure(c->poolws, ob))) return rc;
+  PsisArgs A{};
+  A.n = n; A.nout = nout; A.series = ds; A.par = (const double *)c->predict.p; A.data = ddata; A.out = (double *)c->poolws.p;
+  A.tail_len = (int32_t)tl;
+  A.cap = 8;
+  while (A.cap < A.tail_len) A.cap <<= 1;
+  const size_t lds = 2 * (size_t)A.cap * sizeof(double);
+  if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)psis_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if ((rc = launch(c, psis_params_kernel, (unsigned)((n + 255) / 256), 256, 0, n, dstd2, (double *)c->predict.p))) return rc;
+  if ((rc = launch(c, psis_row_kernel, (unsigned)nout, kPsisThreads, lds, A))) return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_rows, c->poolws.p, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RSF_OK;
+}
+
+int rsf_predict_psis_finish(int64_t nout, int64_t n, const double *psis_rows, const double *lpd_rows, double *out_totals) {
+  if (!psis_rows || !lpd_rows || !out_totals) return fail(RSF_ERR_INVALID, "rsf_predict_psis_finish: NULL argument");
+  if (nout < 1 || n < 1) return fail(RSF_ERR_INVALID, "rsf_predict_psis_finish: nout < 1 or n < 1");
+  const double thr = n > 1 ? std::min(1.0 - 1.0 / std::log10((double)n), 0.7) : -INFINITY;
+  double elpd = 0.0, p = 0.0, kmax = -INFINITY, high = 0.0;
+  bool ok = true;
+  for (int64_t k = 0; k < nout; ++k) {
+    const double e = psis_rows[k * RSF_PSIS_OUT + RSF_PSIS_ELPD], pk = psis_rows[k * RSF_PSIS_OUT + RSF_PSIS_PARETO_K];
+    ok = ok && std::isfinite(e) && !std::isnan(pk) && std::isfinite(lpd_rows[k]);
+    elpd += e;
+    p += lpd_rows[k] - e;
+    kmax = std::max(kmax, pk);
+    high += pk > thr ? 1.0 : 0.0;
+  }
+  const double nr = (double)nout, me = elpd / nr;
+  double ss = 0.0;
+  for (int64_t k = 0; k < nout; ++k) {
+    const double e = psis_rows[k * RSF_PSIS_OUT + RSF_PSIS_ELPD] - me;
+    ss += e * e;
+  }
+  out_totals[RSF_PSIS_ELPD_LOO] = ok ? elpd : NAN;
+  out_totals[RSF_PSIS_P_LOO] = ok ? p : NAN;
+  out_totals[RSF_PSIS_ELPD_LOO_SE] = ok ? std::sqrt(nr * (ss / (nr - 1.0))) : NAN;
+  out_totals[RSF_PSIS_K_THRESHOLD] = thr;
+  out_totals[RSF_PSIS_N_HIGH_K] = ok ? high : NAN;
+  out_totals[RSF_PSIS_MAX_PARETO_K] = ok ? kmax : NAN;
   return RSF_OK;
 }
 

@@ -569,13 +569,49 @@ class Engine:
             out[j:j + pj.size] = oj
         return out
 
-    def predictive(self, q, std2, data, probs=(), center=None, return_series=False):
+    def psis_loo(self, series, std2, data, lpd, r_eff=1.0):
+        """rsf_predict_psis_loo and rsf_predict_psis_finish: PSIS-LOO of a series (nout, n) in this engine's memory space (as
+        predictive_partials(return_series=True) leaves it) with the draws' noise variances std2 (n,), the observation data
+        (nout,) and lpd (nout,) of predictive_finish → dict of (nout,) arrays elpd_loo_k, pareto_k, n_tail, weight_ess and the
+        totals elpd_loo, p_loo, elpd_loo_se (ddof 1, as elpd_waic_se; ArviZ uses ddof 0), k_threshold, n_high_k, max_pareto_k,
+        n.  r_eff: the relative efficiency of the draws (ESS / n, e.g. from rank_diagnostics); it sets the tail length only.
+        A row with at most four draws above the cutoff — also a row whose log-likelihoods are all equal, as k = 0 is when every
+        std2 is equal — has pareto_k = +inf and is not smoothed (ArviZ's behaviour).  Ranks of the tail are global over the
+        draws: nothing here is additive over shards, a multi-rank pool is gathered first."""
+        x, s2, obs = self._in(series), self._in(std2), self._in(data)
+        if x.ndim != 2 or int(x.shape[0]) < 1 or int(x.shape[1]) < 1:
+            raise ValueError("a series is (nout, n)")
+        rows, n = int(x.shape[0]), int(x.shape[1])
+        if s2.ndim != 1 or int(s2.shape[0]) != n:
+            raise ValueError(f"std2 has shape {tuple(s2.shape)}, the series has {n} draws")
+        if obs.ndim != 1 or int(obs.shape[0]) != rows:
+            raise ValueError(f"data has shape {tuple(obs.shape)}, the series has {rows} rows")
+        lpd = np.ascontiguousarray(np.asarray(lpd.cpu() if hasattr(lpd, "cpu") else lpd, dtype=np.float64))
+        if lpd.shape != (rows,):
+            raise ValueError(f"lpd has shape {lpd.shape}, the series has {rows} rows")
+        r_eff = float(r_eff)
+        if not (np.isfinite(r_eff) and r_eff > 0.0):
+            raise ValueError("r_eff is finite and > 0")
+        out = np.empty((rows, len(_abi.PSIS_OUT)))
+        tot = np.empty(len(_abi.PSIS_TOTALS))
+        dbl = ctypes.POINTER(ctypes.c_double)
+        _abi.check(self.lib, self.lib.rsf_predict_psis_loo(self._ctx, n, rows, self._ptr(x), self._ptr(s2), self._ptr(obs), r_eff,
+                                                           out.ctypes.data_as(dbl)))
+        _abi.check(self.lib, self.lib.rsf_predict_psis_finish(rows, n, out.ctypes.data_as(dbl), lpd.ctypes.data_as(dbl),
+                                                              tot.ctypes.data_as(dbl)))
+        res = {name: np.ascontiguousarray(out[:, j]) for j, name in enumerate(_abi.PSIS_OUT)}
+        res.update({name: float(v) for name, v in zip(_abi.PSIS_TOTALS, tot)})
+        res["n"] = n
+        return res
+
+    def predictive(self, q, std2, data, probs=(), center=None, return_series=False, loo=False, r_eff=1.0):
         """Posterior predictive checks of n draws against the observation `data`: per output time the model series' mean and
         variance over the draws, the probability integral transform of the observation (pit), the log pointwise predictive
         density (lpd) and the WAIC penalty (p_waic_k); the totals mean_std2, elpd_waic, p_waic, elpd_waic_se; with `probs` the
         exact quantiles (len(probs), nout) of the series over the draws, the credible band.  center = (center_y, center_l)
         (default: the series at the draws' mean parameter vector, and its log density with the mean sigma^2).  With probs or
-        return_series the series (nout, n) is materialised: n * nout * 8 bytes."""
+        return_series the series (nout, n) is materialised: n * nout * 8 bytes.  loo=True materialises it as well and adds
+        psis_loo's entries (with r_eff) to the result; the default leaves the result as it is without."""
         q, std2, data, n, d = self._predict_args(q, std2, data)
         probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
         if probs.ndim != 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
@@ -595,7 +631,7 @@ class Engine:
         else:
             cy, cl = center
         cy, cl = self._predict_centers(cy, cl)
-        want_series = bool(return_series) or probs.size > 0
+        want_series = bool(return_series) or probs.size > 0 or bool(loo)
         part = self.predictive_partials(q, std2, data, cy, cl, return_series=want_series)
         series = None
         if want_series:
@@ -604,6 +640,8 @@ class Engine:
         res.update(partials=part, center_y=cy, center_l=cl)
         if probs.size:
             res["probs"], res["quantiles"] = probs, self.predictive_quantiles(series, probs)
+        if loo:
+            res.update({name: v for name, v in self.psis_loo(series, std2, data, res["lpd"], r_eff=r_eff).items() if name != "n"})
         if return_series:
             res["series"] = series
         return res

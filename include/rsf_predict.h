@@ -1,6 +1,7 @@
 /*
  * rsf_predict.h — posterior predictive checks of pooled draws: the model series' credible spread, the probability
- * integral transform of the observation, the log pointwise predictive density and WAIC, and exact credible bands.
+ * integral transform of the observation, the log pointwise predictive density and WAIC, exact credible bands, and PSIS-LOO
+ * with the Pareto shape per output time (rsf_psis.h, included at the end).
  *
  * Exported by librsf_hip.so only (the CPU checker implements rsf_abi.h alone; tests/predictive_reference.py is the
  * specification these entry points are tested against).  Same conventions as rsf_abi.h: int status, rsf_last_error(),
@@ -86,4 +87,8 @@ int rsf_predict_quantiles(rsf_ctx *ctx, int64_t n, int64_t nout, const double *s
 #ifdef __cplusplus
 }
 #endif
+
+/* PSIS-LOO and the Pareto shape per output time, on the series this header's entry points leave: declared in rsf_psis.h */
+#include "rsf_psis.h"
+
 #endif /* RSF_PREDICT_H */
