@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "rsf_math.h"
 
 namespace rsf {
@@ -533,6 +535,14 @@ struct Wave {
 
 __device__ __forceinline__ unsigned long long ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ bool lane_in(unsigned long long mask) { return (mask >> (threadIdx.x & 63)) & 1; }
+// a double from the lane that DPP control CTRL names (quad_perm, row_half_mirror, ...): two moves in the VALU, one per half —
+// no trip through the LDS pipe as a general shuffle (ds_bpermute) takes
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
 
 // (the statistics members are the caller's to zero: they accumulate over the solves of a launch)
 __device__ __forceinline__ void wave_begin(Wave &W, bool active, const Lane &L, const Consts &K) {
@@ -659,13 +669,82 @@ __device__ __forceinline__ int integrate_full(const double *lds, const double *l
   return r;
 }
 
-// Wave-uniform choice of the starting tier of the init kernel's lockstep trajectories (rsf_kernels.h) — a speed decision
+// Wave-uniform choice of the starting tier of the lockstep trajectories (integrate_lockstep below) — a speed decision
 // only: every tier is exact to rounding inside its guard.  TIGHT and NARROW are tried whenever the mu increment allows it
 // (|V_l - v| <~ 1.2 V_ref against their |dlt| guards 2^-9 / 2^-7): theta tracks its steady state closely (|dtheta/theta| ~ 1e-7
 // per stage at Dc ~ 1000, h = 0.1), which no a-priori bound captures.  (The solve below decides the same per lane: wave_begin.)
 __device__ __forceinline__ int start_tier(const Lane &L, const Consts &K) {
   const double dk = 1.2 * K.V_ref * K.h * L.kia;
   return !__any(!(dk < 0x1.0p-9)) ? TIGHT : (!__any(!(dk < 0x1.0p-7)) ? NARROW : WIDE);
+}
+
+// The lockstep driver, one staged chunk of kn output intervals: every lane of a wave takes the tier code through the chunk, trip
+// by trip, in converged control flow, so that the caller's hooks may exchange values between lanes (init_kernel's groups,
+// predict_kernel's ring).  The wave starts at start_tier and only ever moves to a wider tier, in trips of kLockstepTrip steps; a
+// tripped guard sends that lane alone back to the trip's start and through it with full evaluations (trip_cold_plain); the
+// chunk's last steps, fewer than a trip, go one at a time with the WIDE series.  (w, 1/x) are re-evaluated in full every
+// kResync steps.  A chunk is a whole number of output intervals, so the interval's running sum starts and ends at zero here.
+//   on_sample(ak, ko)  an output sample is complete: ak = cv * (the interval's V-derivative sums, like emit_incr), ko its index
+//                      within the chunk's observations;
+//   after_trip()       once after every trip.
+// The caller keeps the chunk loop and stages the chunk, as solve() does (why: profiles/lockstep_driver).  solve() above is the
+// sampler's per-lane tier machine (lanes leave early, tiers go both ways): different on purpose.
+constexpr int kLockstepTrip = 8;
+template <bool DAMP, typename OnSample, typename AfterTrip>
+__device__ __forceinline__ void integrate_lockstep(double *lds, const Consts &K, const Lane &L, State &st, int kn, OnSample on_sample,
+                                                   AfterTrip after_trip) {
+  constexpr int NU = kLockstepTrip;
+  static_assert(kResync % NU == 0, "the resync test looks at the first step of a trip");
+  const int nsteps = K.S * kn;
+  double dsum = 0.0;
+  int phase = 0, ko = 0;  // RK4 steps since the last output sample; samples completed (both wave-uniform)
+  // (every lane of the wave integrates — lanes past the last trajectory carry a harmless Dc = 1000 — so that the shuffles
+  // and the wave-uniform tier decisions see whole waves)
+  int tier = start_tier(L, K);
+  int r = 0;
+  auto trip = [&](auto tier_tag, auto nu_tag) {  // one trip of tier T, NUT steps; a tripped guard: that lane redoes it in full
+    constexpr int T = decltype(tier_tag)::value, NUT = decltype(nu_tag)::value;
+    const double *v = lds + 2 * r;
+    Lane Lt = L;
+    set_tier<T>(Lt);
+    const State save = st;
+    double dv[NUT];
+    tier_enter<DAMP, T>(st, Lt);
+    const bool bad = trip_fast<DAMP, T, NUT>(v, Lt, K, st, dv);
+    tier_leave<DAMP, T>(st, Lt);
+    const bool any_bad = ballot(bad) != 0;
+    if (__builtin_expect(any_bad, 0)) {
+      if (bad) {  // back to the trip's start (the plain state: saved before tier_enter) and through it with full evaluations
+        st = save;
+        trip_cold_plain<DAMP, NUT>(v, L, K, st, dv);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NUT; ++j) {
+      dsum += dv[j];
+      if (++phase == K.S) {
+        phase = 0;
+        on_sample(dsum * L.cv, ko);
+        dsum = 0.0;
+        ++ko;
+      }
+    }
+    return any_bad;
+  };
+  for (; r + NU <= nsteps; r += NU) {
+    if ((r & (kResync - 1)) == 0) eval_full(st.ms, st.x, L, K, st.w, st.rx);
+    bool any_bad;
+    if (tier == TIGHT) any_bad = trip(std::integral_constant<int, TIGHT>{}, std::integral_constant<int, NU>{});
+    else if (tier == NARROW) any_bad = trip(std::integral_constant<int, NARROW>{}, std::integral_constant<int, NU>{});
+    else any_bad = trip(std::integral_constant<int, WIDE>{}, std::integral_constant<int, NU>{});
+    if (any_bad && tier < WIDE) ++tier;
+    after_trip();
+  }
+  for (; r < nsteps; ++r) {  // fewer than NU steps left in the chunk: one at a time
+    if ((r & (kResync - 1)) == 0) eval_full(st.ms, st.x, L, K, st.w, st.rx);
+    trip(std::integral_constant<int, WIDE>{}, std::integral_constant<int, 1>{});
+    after_trip();
+  }
 }
 
 // trips of tier T from chunk step r (at least two steps are left): long trips while they fit, then pairs

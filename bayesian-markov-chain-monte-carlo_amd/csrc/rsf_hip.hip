@@ -1309,6 +1309,29 @@ int rank_scores(rsf_ctx *c, RankWs &w, const RankShape &rs, int s, double *out) 
 int rank_grid(int64_t work, int64_t cap) { return (int)std::max<int64_t>(1, std::min<int64_t>(cap, (work + kRankThreads - 1) / kRankThreads)); }
 }  // namespace
 
+namespace {
+// the first probability outside [0, 1] (NaN included), or -1
+int first_bad_prob(int n, const double *probs) {
+  for (int i = 0; i < n; ++i)
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return i;
+  return -1;
+}
+// a materialised series [nout][n] as the select kernels index it
+int check_series_shape(const char *fn, int64_t n, int64_t nout) {
+  if (n < 1 || n >= (INT64_C(1) << 31) || nout < 1 || nout > INT32_MAX || n > INT64_MAX / 8 / nout)
+    return fail(RSF_ERR_INVALID, "%s: need 1 <= n < 2^31 draws and 1 <= nout rows", fn);
+  return RSF_OK;
+}
+// the series is the largest allocation of its call: a failure to stage it is reported as RSF_ERR_NOMEM with its size
+int series_nomem(const char *fn, int64_t n, int64_t nout, const char *advice = "") {
+  (void)hipGetLastError();
+  return fail(RSF_ERR_NOMEM, "%s: cannot allocate the series' device copy (%lld x %lld doubles)%s", fn, (long long)nout, (long long)n, advice);
+}
+int stage_series(rsf_ctx *c, const char *fn, Slot slot, const double *series, int64_t n, int64_t nout, const double **dev) {
+  return stage_in(c, slot, series, (size_t)n * (size_t)nout * sizeof(double), dev) ? series_nomem(fn, n, nout) : RSF_OK;
+}
+}  // namespace
+
 int rsf_diag_rank_prepare(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double *trace, int32_t n_probs, const double *probs,
                           double hdi_prob, double *stats, double *series) {
   if (!c || !trace || !stats || (n_probs > 0 && !probs)) return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: NULL argument");
@@ -1316,8 +1339,7 @@ int rsf_diag_rank_prepare(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const dou
     return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: need n_iters >= 4, n_chains >= 1, 1 <= n_params <= %d, n_probs >= 0", RSF_MAX_PARAMS);
   if (n >= kRankMaxDraws || C >= kRankMaxDraws || n * C >= kRankMaxDraws)
     return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: n_iters * n_chains must be below 2^32");
-  for (int i = 0; i < n_probs; ++i)
-    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: probs[%d] outside [0, 1]", i);
+  if (const int i = first_bad_prob(n_probs, probs); i >= 0) return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: probs[%d] outside [0, 1]", i);
   const int64_t A = n * C;
   if (!(hdi_prob > 0.0 && hdi_prob < 1.0)) return fail(RSF_ERR_INVALID, "rsf_diag_rank_prepare: hdi_prob outside (0, 1)");
   const double kd = std::floor(hdi_prob * (double)A);  // ArviZ: int(floor(hdi_prob * n))
@@ -1472,11 +1494,7 @@ int rsf_predict_partials(rsf_ctx *c, int64_t n, int32_t d, const double *q, cons
   const double *dq, *dstd2, *ddata;
   double *dser = nullptr;
   // (the largest allocation first: it fails before anything is copied)
-  if (series_out && (rc = stage_out(c, SLOT_SERIES, series_out, nb * (size_t)nout, &dser))) {
-    (void)hipGetLastError();
-    return fail(RSF_ERR_NOMEM, "rsf_predict_partials: cannot allocate the series' device copy (%lld x %lld doubles); pass fewer draws per call",
-                (long long)nout, (long long)n);
-  }
+  if (series_out && stage_out(c, SLOT_SERIES, series_out, nb * (size_t)nout, &dser)) return series_nomem(__func__, n, nout, "; pass fewer draws per call");
   if ((rc = stage_in(c, SLOT_Q, q, nb * d, &dq))) return rc;
   if ((rc = stage_in(c, SLOT_STD2, std2, nb, &dstd2))) return rc;
   if ((rc = stage_in(c, SLOT_OBS, data, rowb, &ddata))) return rc;
@@ -1548,21 +1566,15 @@ int rsf_predict_finish(int64_t n_rows, const double *partials, const double *cen
 
 int rsf_predict_quantiles(rsf_ctx *c, int64_t n, int64_t nout, const double *series, int32_t n_probs, const double *probs, double *out) {
   RSF_ENTER(c, NEED_NOTHING, series && probs && out, "NULL argument");
-  if (n < 1 || n >= (INT64_C(1) << 31) || nout < 1 || nout > INT32_MAX || n > INT64_MAX / 8 / nout)
-    return fail(RSF_ERR_INVALID, "rsf_predict_quantiles: need 1 <= n < 2^31 draws and 1 <= nout rows");
+  int rc;
+  if ((rc = check_series_shape(__func__, n, nout))) return rc;
   if (n_probs < 1 || n_probs > RSF_PREDICT_MAX_PROBS)
     return fail(RSF_ERR_INVALID, "rsf_predict_quantiles: n_probs outside 1..%d", RSF_PREDICT_MAX_PROBS);
+  if (const int i = first_bad_prob(n_probs, probs); i >= 0) return fail(RSF_ERR_INVALID, "rsf_predict_quantiles: probs[%d] is outside [0, 1]", i);
   PredictProbs P{};
-  for (int i = 0; i < n_probs; ++i) {
-    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return fail(RSF_ERR_INVALID, "rsf_predict_quantiles: probs[%d] is outside [0, 1]", i);
-    P.p[i] = probs[i];
-  }
-  int rc;
+  std::copy(probs, probs + n_probs, P.p);
   const double *ds;
-  if ((rc = stage_in(c, SLOT_X, series, (size_t)n * (size_t)nout * sizeof(double), &ds))) {
-    (void)hipGetLastError();
-    return fail(RSF_ERR_NOMEM, "rsf_predict_quantiles: cannot allocate the series' device copy (%lld x %lld doubles)", (long long)nout, (long long)n);
-  }
+  if ((rc = stage_series(c, __func__, SLOT_X, series, n, nout, &ds))) return rc;
   const size_t ob = (size_t)n_probs * (size_t)nout * sizeof(double);
   if ((rc = ensure(c->poolws, ob))) return rc;
   hipLaunchKernelGGL(predict_select_kernel, dim3((unsigned)nout), dim3(kPredSelectThreads), 0, c->stream, n, nout, ds, (int)n_probs, P, (double *)c->poolws.p);
@@ -1575,22 +1587,18 @@ int rsf_predict_quantiles(rsf_ctx *c, int64_t n, int64_t nout, const double *ser
 int rsf_predict_psis_loo(rsf_ctx *c, int64_t n, int64_t nout, const double *series, const double *std2, const double *data, double r_eff,
                          double *out_rows) {
   RSF_ENTER(c, NEED_NOTHING, series && std2 && data && out_rows, "NULL argument");
-  if (n < 1 || n >= (INT64_C(1) << 31) || nout < 1 || nout > INT32_MAX || n > INT64_MAX / 8 / nout)
-    return fail(RSF_ERR_INVALID, "rsf_predict_psis_loo: need 1 <= n < 2^31 draws and 1 <= nout rows");
+  int rc;
+  if ((rc = check_series_shape(__func__, n, nout))) return rc;
   if (!(std::isfinite(r_eff) && r_eff > 0.0)) return fail(RSF_ERR_INVALID, "rsf_predict_psis_loo: r_eff must be finite and > 0");
   const double tl = std::ceil(std::min(0.2 * (double)n, 3.0 * std::sqrt((double)n / r_eff)));
   if (tl > (double)RSF_PSIS_MAX_TAIL)
     return fail(RSF_ERR_UNSUPPORTED, "rsf_predict_psis_loo: a tail of %.0f draws exceeds RSF_PSIS_MAX_TAIL = %d (n = %lld, r_eff = %g)", tl,
                 RSF_PSIS_MAX_TAIL, (long long)n, r_eff);
   static_assert(kPsisMaxTail == RSF_PSIS_MAX_TAIL && kPsisOut == RSF_PSIS_OUT, "csrc/rsf_psis.h and include/rsf_psis.h agree");
-  int rc;
   const size_t nb = (size_t)n * sizeof(double), rowb = (size_t)nout * sizeof(double);
   const double *ds, *dstd2, *ddata;
   // (the largest allocation first: it fails before anything is copied)
-  if ((rc = stage_in(c, SLOT_SERIES, series, nb * (size_t)nout, &ds))) {
-    (void)hipGetLastError();
-    return fail(RSF_ERR_NOMEM, "rsf_predict_psis_loo: cannot allocate the series' device copy (%lld x %lld doubles)", (long long)nout, (long long)n);
-  }
+  if ((rc = stage_series(c, __func__, SLOT_SERIES, series, n, nout, &ds))) return rc;
   if ((rc = stage_in(c, SLOT_STD2, std2, nb, &dstd2))) return rc;
   if ((rc = stage_in(c, SLOT_OBS, data, rowb, &ddata))) return rc;
   // workspace: the draws' constants [2][n] in c->predict, the rows [nout][RSF_PSIS_OUT] in c->poolws

@@ -167,13 +167,9 @@ struct InitGroup {
       }
   }
   // the value lane `SRC` of this lane's group holds.  A group is an aligned pair or quad of lanes, so this is a DPP quad_perm move
-  // (two, for the two halves of a double) in the VALU — no trip through the LDS pipe as a general shuffle (ds_bpermute) takes
   template <int SRC>
   static __device__ __forceinline__ double from_lane(double v) {
-    constexpr int ctrl = G == 4 ? (SRC | SRC << 2 | SRC << 4 | SRC << 6) : (SRC | SRC << 2 | (2 + SRC) << 4 | (2 + SRC) << 6);
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
+    return rsf::dpp_move<G == 4 ? (SRC | SRC << 2 | SRC << 4 | SRC << 6) : (SRC | SRC << 2 | (2 + SRC) << 4 | (2 + SRC) << 6)>(v);
   }
   template <int P>
   __device__ __forceinline__ void gather(double x, double (&xs)[D]) const {
@@ -216,8 +212,6 @@ struct InitGroup {
 template <int D, bool DAMP>
 __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) init_kernel(Consts K, InitArgs A) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int NU = 8;
-  static_assert(rsf::kResync % NU == 0, "the resync test looks at the first step of a trip");
   InitGroup<D> grp;
   grp.select_group(K);
   const bool active = grp.chain < A.C;
@@ -225,60 +219,12 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) init_kernel(Consts K, I
   grp.parameters(K, A, active, pq, inv_den);
   const rsf::Lane L = rsf::make_lane<DAMP>(pq[0], pq[1], pq[2], K);
   rsf::State st = rsf::initial_state(pq[0], L, K);
-  double dsum = 0.0;
   if (active) { const double d0 = K.data[0]; grp.ssq = d0 * d0; }
   const double *ld = lds + rsf::lds_data_offset(K);
-  int phase = 0;  // RK4 steps since the last output sample (wave-uniform)
   for (int k0 = 1; k0 < K.nout; k0 += K.kc) {
     const int kn = min(K.kc, K.nout - k0);
     rsf::stage_chunk(lds, K, k0, kn);
-    const int nsteps = K.S * kn;
-    int ko = 0;
-    auto emit = [&]() {
-      grp.sample(dsum * L.cv, ld[ko], inv_den);
-      dsum = 0.0;
-      ++ko;
-    };
-    // (every lane of the wave integrates — lanes past the last chain carry a harmless Dc = 1000 — so that the shuffles
-    // and the wave-uniform tier decisions see whole waves)
-    int tier = rsf::start_tier(L, K);
-    int r = 0;
-    auto trip = [&](auto tier_tag, auto nu_tag) {  // one trip of tier T, NUT steps; a tripped guard: that lane redoes it in full
-      constexpr int T = decltype(tier_tag)::value, NUT = decltype(nu_tag)::value;
-      const double *v = lds + 2 * r;
-      rsf::Lane Lt = L;
-      rsf::set_tier<T>(Lt);
-      const rsf::State save = st;
-      double dv[NUT];
-      rsf::tier_enter<DAMP, T>(st, Lt);
-      const bool bad = rsf::trip_fast<DAMP, T, NUT>(v, Lt, K, st, dv);
-      rsf::tier_leave<DAMP, T>(st, Lt);
-      const bool any_bad = rsf::ballot(bad) != 0;
-      if (__builtin_expect(any_bad, 0)) {
-        if (bad) {  // back to the trip's start (the plain state: saved before tier_enter) and through it with full evaluations
-          st = save;
-          rsf::trip_cold_plain<DAMP, NUT>(v, L, K, st, dv);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < NUT; ++j) {
-        dsum += dv[j];
-        if (++phase == K.S) { phase = 0; emit(); }
-      }
-      return any_bad;
-    };
-    for (; r + NU <= nsteps; r += NU) {
-      if ((r & (rsf::kResync - 1)) == 0) rsf::eval_full(st.ms, st.x, L, K, st.w, st.rx);
-      bool any_bad;
-      if (tier == rsf::TIGHT) any_bad = trip(std::integral_constant<int, rsf::TIGHT>{}, std::integral_constant<int, NU>{});
-      else if (tier == rsf::NARROW) any_bad = trip(std::integral_constant<int, rsf::NARROW>{}, std::integral_constant<int, NU>{});
-      else any_bad = trip(std::integral_constant<int, rsf::WIDE>{}, std::integral_constant<int, NU>{});
-      if (any_bad && tier < rsf::WIDE) ++tier;
-    }
-    for (; r < nsteps; ++r) {  // fewer than NU steps left in the chunk: one at a time
-      if ((r & (rsf::kResync - 1)) == 0) rsf::eval_full(st.ms, st.x, L, K, st.w, st.rx);
-      trip(std::integral_constant<int, rsf::WIDE>{}, std::integral_constant<int, 1>{});
-    }
+    rsf::integrate_lockstep<DAMP>(lds, K, L, st, kn, [&](double ak, int ko) { grp.sample(ak, ld[ko], inv_den); }, [] {});
   }
   grp.finish(A, active);
 }

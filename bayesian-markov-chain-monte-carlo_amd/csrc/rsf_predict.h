@@ -1,8 +1,8 @@
 // rsf_predict.h — posterior predictive checks of pooled draws (include/rsf_predict.h), the kernels:
-//   predict_kernel         one lane per draw: the float64 RK4 tier code driven exactly as init_kernel drives it, and at every
+//   predict_kernel         one lane per draw: the float64 RK4 tier code driven by rsf::integrate_lockstep, and at every
 //                          completed output sample the wave's 64 values y_ik go through an LDS tile to the lanes that reduce them;
 //   predict_sum_kernel     fixed-order sum of the per-wave partials, in two levels (slabs of waves, then the slabs);
-//   predict_select_kernel  exact order statistics of every row of a materialised series by radix select, then NumPy's _lerp.
+//   predict_select_kernel  exact order statistics of every row of a materialised series by rank_select, then rank_lerp.
 // No float atomics; every sum across lanes, waves and workgroups has a fixed order, so the same draws give the same bits.
 //
 // The per-sample hook.  A wave parks its 64 samples of an output time in one slot of a ring of kPredSlots slots (64 doubles
@@ -44,17 +44,11 @@ struct PredictArgs {
   int32_t tab_doubles; // offset of the wave areas behind the table chunk
 };
 
-template <int CTRL>
-__device__ __forceinline__ double pred_dpp(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
 // the sum over an aligned group of eight lanes, in all eight (a + b == b + a bit for bit, so the butterfly agrees everywhere)
 __device__ __forceinline__ double pred_sum8(double v) {
-  v += pred_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += pred_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += pred_dpp<0x141>(v);  // row_half_mirror: the other quad of the eight
+  v += rsf::dpp_move<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += rsf::dpp_move<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += rsf::dpp_move<0x141>(v);  // row_half_mirror: the other quad of the eight
   return v;
 }
 
@@ -101,9 +95,7 @@ __device__ __forceinline__ void predict_flush(const double *ring, const double *
 template <int D, bool DAMP, bool WANT_SERIES>
 __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) predict_kernel(Consts K, PredictArgs A) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int NU = 8;
-  static_assert(rsf::kResync % NU == 0, "the resync test looks at the first step of a trip");
-  static_assert(NU <= kPredSlots - (kPredTile - 1), "a trip's samples fit the ring behind the left-over ones");
+  static_assert(rsf::kLockstepTrip <= kPredSlots - (kPredTile - 1), "a trip's samples fit the ring behind the left-over ones");
   const unsigned t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + t;
   const int64_t wave_first = i - lane;
@@ -124,7 +116,6 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) predict_kernel(Consts K
   par[192 + lane] = s2;
   const rsf::Lane L = rsf::make_lane<DAMP>(pq[0], pq[1], pq[2], K);
   rsf::State st = rsf::initial_state(pq[0], L, K);
-  double dsum = 0.0;
   // ring of parked samples: `cnt` filled slots from `head`, the first of them output time `kt` (all wave-uniform)
   int head = 0, cnt = 0, kt = 0, kabs = 0;
   auto park = [&](double y) {
@@ -144,52 +135,10 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) predict_kernel(Consts K
     kt += count;
   };
   park(0.0);  // y_i0 = 0
-  int phase = 0;  // RK4 steps since the last output sample (wave-uniform)
   for (int k0 = 1; k0 < K.nout; k0 += K.kc) {
     const int kn = min(K.kc, K.nout - k0);
     rsf::stage_chunk(lds, K, k0, kn);
-    const int nsteps = K.S * kn;
-    // (every lane of the wave integrates, so that the wave-uniform tier decisions see whole waves)
-    int tier = rsf::start_tier(L, K);
-    int r = 0;
-    auto trip = [&](auto tier_tag, auto nu_tag) {  // one trip of tier T, NUT steps; a tripped guard: that lane redoes it in full
-      constexpr int T = decltype(tier_tag)::value, NUT = decltype(nu_tag)::value;
-      const double *v = lds + 2 * r;
-      rsf::Lane Lt = L;
-      rsf::set_tier<T>(Lt);
-      const rsf::State save = st;
-      double dv[NUT];
-      rsf::tier_enter<DAMP, T>(st, Lt);
-      const bool bad = rsf::trip_fast<DAMP, T, NUT>(v, Lt, K, st, dv);
-      rsf::tier_leave<DAMP, T>(st, Lt);
-      const bool any_bad = rsf::ballot(bad) != 0;
-      if (__builtin_expect(any_bad, 0)) {
-        if (bad) {  // back to the trip's start (the plain state: saved before tier_enter) and through it with full evaluations
-          st = save;
-          rsf::trip_cold_plain<DAMP, NUT>(v, L, K, st, dv);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < NUT; ++j) {
-        dsum += dv[j];
-        if (++phase == K.S) { phase = 0; park(dsum * L.cv); dsum = 0.0; }
-      }
-      return any_bad;
-    };
-    for (; r + NU <= nsteps; r += NU) {
-      if ((r & (rsf::kResync - 1)) == 0) rsf::eval_full(st.ms, st.x, L, K, st.w, st.rx);
-      bool any_bad;
-      if (tier == rsf::TIGHT) any_bad = trip(std::integral_constant<int, rsf::TIGHT>{}, std::integral_constant<int, NU>{});
-      else if (tier == rsf::NARROW) any_bad = trip(std::integral_constant<int, rsf::NARROW>{}, std::integral_constant<int, NU>{});
-      else any_bad = trip(std::integral_constant<int, rsf::WIDE>{}, std::integral_constant<int, NU>{});
-      if (any_bad && tier < rsf::WIDE) ++tier;
-      if (cnt >= kPredTile) flush(kPredTile);
-    }
-    for (; r < nsteps; ++r) {  // fewer than NU steps left in the chunk: one at a time
-      if ((r & (rsf::kResync - 1)) == 0) rsf::eval_full(st.ms, st.x, L, K, st.w, st.rx);
-      trip(std::integral_constant<int, rsf::WIDE>{}, std::integral_constant<int, 1>{});
-      if (cnt >= kPredTile) flush(kPredTile);
-    }
+    rsf::integrate_lockstep<DAMP>(lds, K, L, st, kn, [&](double ak, int) { park(ak); }, [&] { if (cnt >= kPredTile) flush(kPredTile); });
   }
   while (cnt > 0) flush(cnt < kPredTile ? cnt : kPredTile);
 }
@@ -213,71 +162,31 @@ struct PredictProbs {
   double p[kPredMaxRanks / 2];
 };
 
-// One workgroup per row of series[nout][n].  Keys are rank_key's order-preserving map; eight passes of eight bits from the
-// top, each a read of the row: per target rank a 256-bin histogram (LDS, integer atomics) of the keys that agree with the
-// rank's prefix so far; one thread per rank then walks its bins to the digit that holds the rank.  Both order statistics of
-// np.quantile's "linear" method are found per probability, then NumPy's _lerp (the operations of rank_quantile).
+// One workgroup per row of series[nout][n]: both order statistics of np.quantile's "linear" method per probability by
+// rank_select on rank_key's order-preserving map (rsf_diag_rank.h), then rank_lerp.
 __global__ void __launch_bounds__(kPredSelectThreads)
 predict_select_kernel(int64_t n, int64_t nout, const double *__restrict__ series, int nprobs, PredictProbs P, double *__restrict__ out) {
-  __shared__ uint32_t hist[kPredMaxRanks][256];
-  __shared__ uint64_t prefix[kPredMaxRanks];
-  __shared__ uint32_t want[kPredMaxRanks];
+  __shared__ RankSelect<kPredMaxRanks> sel;
   __shared__ uint32_t nonfinite;
   const int nr = 2 * nprobs;
   const int64_t k = blockIdx.x;
   const double *row = series + k * n;
   const unsigned t = threadIdx.x;
+  int64_t lo, hi;
+  double g;
   if (t < (unsigned)nr) {
-    const double h = (double)(n - 1) * P.p[t >> 1];
-    int64_t lo = (int64_t)floor(h);
-    lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
-    want[t] = (uint32_t)((t & 1) ? (lo + 1 < n ? lo + 1 : n - 1) : lo);
-    prefix[t] = 0;
+    rank_pair(n, P.p[t >> 1], lo, hi, g);
+    sel.want[t] = (uint32_t)((t & 1) ? hi : lo);
   }
   if (t == 0) nonfinite = 0;
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = 56 - 8 * pass;
-    const uint64_t mask = pass == 0 ? 0ull : ~0ull << (shift + 8);
-    for (int e = t; e < nr * 256; e += kPredSelectThreads) (&hist[0][0])[e] = 0;
-    __syncthreads();
-    bool bad = false;
-    for (int64_t j = t; j < n; j += kPredSelectThreads) {
-      const double v = row[j];
-      bad = bad || !isfinite(v);
-      const uint64_t key = rank_key(v);
-      const unsigned dig = (unsigned)(key >> shift) & 255u;
-      if (pass == 0) {
-        atomicAdd(&hist[0][dig], 1u);  // no prefix yet: every rank shares one histogram
-      } else {
-        for (int q = 0; q < nr; ++q)
-          if ((key & mask) == prefix[q]) atomicAdd(&hist[q][dig], 1u);
-      }
-    }
-    if (pass == 0 && bad) nonfinite = 1;
-    __syncthreads();
-    if (t < (unsigned)nr) {
-      const uint32_t *hq = hist[pass == 0 ? 0 : t];
-      uint32_t below = 0, w = want[t];
-      int dig = 0;
-      for (; dig < 255; ++dig) {
-        const uint32_t c = hq[dig];
-        if (below + c > w) break;
-        below += c;
-      }
-      want[t] = w - below;
-      prefix[t] |= (uint64_t)dig << shift;
-    }
-    __syncthreads();
-  }
+  rank_select(sel, nr, n, [&](int64_t j, int pass) {
+    const double v = row[j];
+    if (pass == 0 && !isfinite(v)) nonfinite = 1;  // (every writer stores the same value; read behind the select's last barrier)
+    return rank_key(v);
+  });
   if (t < (unsigned)nprobs) {
-#pragma clang fp contract(off)  // bit for bit NumPy: no fused multiply-add
-    const double prob = P.p[t];
-    const double h = (double)(n - 1) * prob;
-    const double fl = floor(h);
-    const double g = h - fl;
-    const double a = rank_value(prefix[2 * t]), b = rank_value(prefix[2 * t + 1]);
-    const double diff = b - a;
-    const double v = g < 0.5 ? a + diff * g : b - diff * (1.0 - g);
+    rank_pair(n, P.p[t], lo, hi, g);
+    const double v = rank_lerp(rank_value(sel.prefix[2 * t]), rank_value(sel.prefix[2 * t + 1]), g);
     out[(int64_t)t * nout + k] = nonfinite ? __longlong_as_double(0x7ff8000000000000ll) : v;
   }
 }

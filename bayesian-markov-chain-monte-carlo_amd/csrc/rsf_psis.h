@@ -3,8 +3,7 @@
 //                       operations wherever a row is read (the log-likelihood matrix is never stored);
 //   psis_row_kernel     one workgroup per output time, every step of the definition (tests/psis_reference.py):
 //     1. one read of the row: max_i x_i and the non-finite flag;
-//     2. eight reads: radix select of the order statistic x_(n - tail_len - 1) of x - max, predict_select_kernel's scheme with
-//        one target rank;
+//     2. eight reads: the order statistic x_(n - tail_len - 1) of x - max by rank_select (rsf_diag_rank.h) with one target rank;
 //     3. one read: the members above the cutoff go to LDS (integer atomic for the slot: the tail is sorted next, so the order
 //        of arrival changes nothing), the body's sum exp(x) and sum exp(2 x) are accumulated;
 //     4. LDS bitonic sort of the tail (of the raw x, from which l = -x is exact), then t_j = exp(x_j) - exp(cutoff);
@@ -74,9 +73,8 @@ __global__ void __launch_bounds__(kPsisThreads) psis_row_kernel(PsisArgs A) {
   extern __shared__ __attribute__((aligned(16))) double psis_lds[];
   __shared__ double red[kPsisThreads];
   __shared__ double cb[kPsisMaxCand], cL[kPsisMaxCand], cw[kPsisMaxCand];
-  __shared__ uint32_t hist[256];
-  __shared__ uint64_t prefix;
-  __shared__ uint32_t want, nonfinite, ntail;
+  __shared__ RankSelect<1> sel;
+  __shared__ uint32_t nonfinite, ntail;
   __shared__ double fit[2];  // b, then pareto_k and sigma
   double *xs = psis_lds, *ts = psis_lds + A.cap;  // the tail's raw x, ascending; t_j
   const unsigned t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -91,7 +89,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_row_kernel(PsisArgs A) {
   };
 
   // 1. the maximum, and whether every x is finite
-  if (t == 0) { nonfinite = 0; ntail = 0; prefix = 0; }
+  if (t == 0) { nonfinite = 0; ntail = 0; }
   double mx = -__builtin_huge_val();
   bool bad = false;
   for (int64_t i = t; i < n; i += kPsisThreads) {
@@ -107,36 +105,13 @@ __global__ void __launch_bounds__(kPsisThreads) psis_row_kernel(PsisArgs A) {
     return;
   }
 
-  // 2. x_(j0) of x - max by radix select, eight bits a pass from the top
+  // 2. x_(j0) of x - max by radix select
   if (t == 0) {
     const int64_t j0 = n - A.tail_len - 1;
-    want = (uint32_t)(j0 < 0 ? 0 : j0);
+    sel.want[0] = (uint32_t)(j0 < 0 ? 0 : j0);
   }
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = 56 - 8 * pass;
-    const uint64_t mask = pass == 0 ? 0ull : ~0ull << (shift + 8);
-    hist[t] = 0;  // kPsisThreads == 256 bins
-    __syncthreads();
-    const uint64_t pre = prefix;
-    for (int64_t i = t; i < n; i += kPsisThreads) {
-      const uint64_t key = rank_key(xraw(i) - mx);
-      if ((key & mask) == pre) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (t == 0) {
-      uint32_t below = 0, w = want;
-      int dig = 0;
-      for (; dig < 255; ++dig) {
-        const uint32_t c = hist[dig];
-        if (below + c > w) break;
-        below += c;
-      }
-      want = w - below;
-      prefix = pre | (uint64_t)dig << shift;
-    }
-    __syncthreads();
-  }
-  const double cutoff = fmax(rank_value(prefix), kPsisLogDblMin);
+  rank_select(sel, 1, n, [&](int64_t i, int) { return rank_key(xraw(i) - mx); });
+  const double cutoff = fmax(rank_value(sel.prefix[0]), kPsisLogDblMin);
 
   // 3. the tail to LDS; the body's sums
   double s1 = 0.0, s2 = 0.0;

@@ -19,6 +19,43 @@ else:  # flat layout: this directory on sys.path, the reference's own import sty
     import _abi
 
 
+def _host(x):
+    """A contiguous float64 NumPy array of x (a torch tensor is copied to the host)."""
+    return np.ascontiguousarray(np.asarray(x.cpu() if hasattr(x, "cpu") else x, dtype=np.float64))
+
+
+def _dp(a):
+    """The double* of a float64 NumPy array."""
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _rows_totals(out, tot, row_names, total_names):
+    """Per-row columns of out as arrays and the totals as floats, by name."""
+    res = {name: np.ascontiguousarray(out[:, j]) for j, name in enumerate(row_names)}
+    res.update({name: float(v) for name, v in zip(total_names, tot)})
+    return res
+
+
+def _series_shape(x):
+    """(rows, n) of a materialised series (nout, n)."""
+    if x.ndim != 2 or int(x.shape[0]) < 1 or int(x.shape[1]) < 1:
+        raise ValueError("a series is (nout, n)")
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def _lag_blocks(N, lag_block, partials, finish, complete):
+    """Partials of the lags [0, end), end growing by lag_block, until complete(finish(partials)) (Geyer's truncation reached
+    everywhere) or every lag [0, N) is in → (partials, what finish made of them)."""
+    part = None
+    while True:
+        end = 0 if part is None else part.shape[-1] - _abi.DIAG_HEAD
+        new = partials(end, min(N, end + int(lag_block)))
+        part = new if part is None else np.concatenate([part, new[..., _abi.DIAG_HEAD:]], axis=-1)
+        res = finish(part)
+        if part.shape[-1] - _abi.DIAG_HEAD >= N or complete(res):
+            return part, res
+
+
 def _model_struct(model, substeps):
     m = _abi.Model()
     m.size = ctypes.sizeof(_abi.Model)
@@ -333,7 +370,7 @@ class Engine:
     def _diag_center(x, d, center):
         if center is None:  # the trace's first draw of chain 0
             first = x[0, 0]
-            return np.ascontiguousarray(np.asarray(first.cpu() if hasattr(first, "cpu") else first, dtype=np.float64).reshape(d))
+            return _host(first).reshape(d)
         return np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), (d,)))
 
     def diag_partials(self, trace, superchain_size=None, center=None, lag_begin=0, lag_end=None):
@@ -345,15 +382,14 @@ class Engine:
         c = self._diag_center(x, d, center)
         lag_end = n // 2 if lag_end is None else int(lag_end)
         out = np.empty((d, _abi.DIAG_HEAD + max(lag_end - int(lag_begin), 0)))
-        dbl = ctypes.POINTER(ctypes.c_double)
-        _abi.check(self.lib, self.lib.rsf_diag_partials(self._ctx, n, C, d, self._ptr(x), int(superchain_size or 0), c.ctypes.data_as(dbl),
-                                                        int(lag_begin), lag_end, out.ctypes.data_as(dbl)))
+        _abi.check(self.lib, self.lib.rsf_diag_partials(self._ctx, n, C, d, self._ptr(x), int(superchain_size or 0), _dp(c),
+                                                        int(lag_begin), lag_end, _dp(out)))
         return out
 
     def diag_finish(self, n_iters, partials, center, superchain_size=None, n_lags=None):
         """rsf_diag_finish (host only): the statistics of summed partials whose lags are [0, n_lags) → one dict per parameter
         (split_rhat, nested_rhat, ess, tau, mcse_mean, mean, var_plus, W, B_over_N, K, lags_complete)."""
-        part = np.ascontiguousarray(np.asarray(partials.cpu() if hasattr(partials, "cpu") else partials, dtype=np.float64))
+        part = _host(partials)
         part = part.reshape(-1, part.shape[-1])
         d = int(part.shape[0])
         n_lags = int(part.shape[1]) - _abi.DIAG_HEAD if n_lags is None else int(n_lags)
@@ -361,9 +397,8 @@ class Engine:
             raise ValueError(f"partials have {part.shape[1] - _abi.DIAG_HEAD} lags, not n_lags = {n_lags}")
         c = np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), (d,)))
         out = np.empty((d, len(_abi.DIAG_OUT)))
-        dbl = ctypes.POINTER(ctypes.c_double)
-        _abi.check(self.lib, self.lib.rsf_diag_finish(int(n_iters), d, int(superchain_size or 0), c.ctypes.data_as(dbl),
-                                                      part.ctypes.data_as(dbl), n_lags, out.ctypes.data_as(dbl)))
+        _abi.check(self.lib, self.lib.rsf_diag_finish(int(n_iters), d, int(superchain_size or 0), _dp(c),
+                                                      _dp(part), n_lags, _dp(out)))
         res = []
         for row in out:
             r = dict(zip(_abi.DIAG_OUT, (float(v) for v in row)))
@@ -382,14 +417,8 @@ class Engine:
             return self.diag_finish(n, self.diag_partials(x, superchain_size, c, 0, n_lags), c, superchain_size)
         if int(lag_block) < 2:
             raise ValueError("lag_block must be >= 2")
-        N, end, part = n // 2, 0, None
-        while True:
-            new = self.diag_partials(x, superchain_size, c, end, min(N, end + int(lag_block)))
-            part = new if part is None else np.concatenate([part, new[:, _abi.DIAG_HEAD:]], axis=1)
-            end = part.shape[1] - _abi.DIAG_HEAD
-            res = self.diag_finish(n, part, c, superchain_size)
-            if end >= N or all(r["lags_complete"] for r in res):
-                return res
+        return _lag_blocks(n // 2, lag_block, lambda b, e: self.diag_partials(x, superchain_size, c, b, e),
+                           lambda part: self.diag_finish(n, part, c, superchain_size), lambda res: all(r["lags_complete"] for r in res))[1]
 
     # -- rank-normalised diagnostics and order statistics (include/rsf_diag.h, rsf_diag_rank_*) -----------
     def rank_prepare(self, trace, probs=(), hdi_prob=0.94, series=False):
@@ -400,9 +429,8 @@ class Engine:
         pr = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
         stats = np.empty((d, len(_abi.DIAG_RANK_STATS) + pr.size))
         out = self._empty((4, n, C, d)) if series else None
-        dbl = ctypes.POINTER(ctypes.c_double)
-        _abi.check(self.lib, self.lib.rsf_diag_rank_prepare(self._ctx, n, C, d, self._ptr(x), int(pr.size), pr.ctypes.data_as(dbl),
-                                                            float(hdi_prob), stats.ctypes.data_as(dbl), self._ptr(out)))
+        _abi.check(self.lib, self.lib.rsf_diag_rank_prepare(self._ctx, n, C, d, self._ptr(x), int(pr.size), _dp(pr),
+                                                            float(hdi_prob), _dp(stats), self._ptr(out)))
         self._rank_d = d
         return (stats, out) if series else stats
 
@@ -413,7 +441,7 @@ class Engine:
             raise ValueError("rank_partials before rank_prepare")
         out = np.empty((4, d, _abi.DIAG_HEAD + max(int(lag_end) - int(lag_begin), 0)))
         _abi.check(self.lib, self.lib.rsf_diag_rank_partials(self._ctx, int(lag_begin), int(lag_end),
-                                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+                                                             _dp(out)))
         return out
 
     def rank_finish(self, n_iters, stats, partials, n_lags=None):
@@ -425,9 +453,8 @@ class Engine:
         if part.shape != (4, d, _abi.DIAG_HEAD + n_lags):
             raise ValueError(f"partials must be (4, {d}, DIAG_HEAD + n_lags), not {part.shape}")
         out = np.empty((d, len(_abi.DIAG_RANK_OUT)))
-        dbl = ctypes.POINTER(ctypes.c_double)
-        _abi.check(self.lib, self.lib.rsf_diag_rank_finish(int(n_iters), d, st.ctypes.data_as(dbl), int(st.shape[1]) - len(_abi.DIAG_RANK_STATS),
-                                                           part.ctypes.data_as(dbl), n_lags, out.ctypes.data_as(dbl)))
+        _abi.check(self.lib, self.lib.rsf_diag_rank_finish(int(n_iters), d, _dp(st), int(st.shape[1]) - len(_abi.DIAG_RANK_STATS),
+                                                           _dp(part), n_lags, _dp(out)))
         return out
 
     def rank_release(self):
@@ -446,19 +473,12 @@ class Engine:
             raise ValueError("lag_block must be >= 2")
         stats = self.rank_prepare(x, probs, hdi_prob)
         try:
-            N = n // 2
             if n_lags is not None:
                 part = self.rank_partials(0, int(n_lags))
                 out = self.rank_finish(n, stats, part)
             else:
-                part = None
-                while True:
-                    end = 0 if part is None else part.shape[-1] - _abi.DIAG_HEAD
-                    new = self.rank_partials(end, min(N, end + int(lag_block)))
-                    part = new if part is None else np.concatenate([part, new[:, :, _abi.DIAG_HEAD:]], axis=2)
-                    out = self.rank_finish(n, stats, part)
-                    if part.shape[-1] - _abi.DIAG_HEAD >= N or np.all(out[:, -1] != 0):
-                        break
+                part, out = _lag_blocks(n // 2, lag_block, self.rank_partials, lambda part: self.rank_finish(n, stats, part),
+                                        lambda out: np.all(out[:, -1] != 0))
         finally:
             self.rank_release()
         L = part.shape[-1] - _abi.DIAG_HEAD
@@ -493,7 +513,7 @@ class Engine:
     def _predict_centers(self, center_y, center_l):
         c = []
         for v in (center_y, center_l):
-            v = np.ascontiguousarray(np.asarray(v.cpu() if hasattr(v, "cpu") else v, dtype=np.float64))
+            v = _host(v)
             if v.shape != (self.nout,):
                 raise ValueError(f"a centre has shape {v.shape}, the model produces {self.nout} samples")
             c.append(v)
@@ -514,10 +534,9 @@ class Engine:
                 raise MemoryError(f"cannot allocate the predictive series ({self.nout} x {n} doubles = {8 * self.nout * n} bytes); "
                                   "pass fewer draws (max_draws)") from e
         out = np.empty(_abi.PREDICT_HEAD + self.nout * len(_abi.PREDICT_FIELDS))
-        dbl = ctypes.POINTER(ctypes.c_double)
         try:
             _abi.check(self.lib, self.lib.rsf_predict_partials(self._ctx, n, d, self._ptr(q), self._ptr(std2), self._ptr(data),
-                                                               cy.ctypes.data_as(dbl), cl.ctypes.data_as(dbl), out.ctypes.data_as(dbl),
+                                                               _dp(cy), _dp(cl), _dp(out),
                                                                self._ptr(series)))
         except _abi.RsfError as e:
             if e.code == -4:  # RSF_ERR_NOMEM
@@ -528,7 +547,7 @@ class Engine:
     def predictive_finish(self, partials, center_y, center_l):
         """rsf_predict_finish (host only): the statistics of summed partials → dict of (nout,) arrays mean, var, pit, lpd,
         p_waic_k and the totals mean_std2, elpd_waic, p_waic, elpd_waic_se, n."""
-        part = np.ascontiguousarray(np.asarray(partials.cpu() if hasattr(partials, "cpu") else partials, dtype=np.float64)).reshape(-1)
+        part = _host(partials).reshape(-1)
         nf = len(_abi.PREDICT_FIELDS)
         if part.size <= _abi.PREDICT_HEAD or (part.size - _abi.PREDICT_HEAD) % nf:
             raise ValueError(f"partials have {part.size} entries, not PREDICT_HEAD + rows * {nf}")
@@ -539,11 +558,9 @@ class Engine:
             raise ValueError(f"the centres have shapes {cy.shape}, {cl.shape}, the partials {rows} rows")
         out = np.empty((rows, len(_abi.PREDICT_OUT)))
         tot = np.empty(len(_abi.PREDICT_TOTALS))
-        dbl = ctypes.POINTER(ctypes.c_double)
-        _abi.check(self.lib, self.lib.rsf_predict_finish(rows, part.ctypes.data_as(dbl), cy.ctypes.data_as(dbl), cl.ctypes.data_as(dbl),
-                                                         out.ctypes.data_as(dbl), tot.ctypes.data_as(dbl)))
-        res = {name: np.ascontiguousarray(out[:, j]) for j, name in enumerate(_abi.PREDICT_OUT)}
-        res.update({name: float(v) for name, v in zip(_abi.PREDICT_TOTALS, tot)})
+        _abi.check(self.lib, self.lib.rsf_predict_finish(rows, _dp(part), _dp(cy), _dp(cl),
+                                                         _dp(out), _dp(tot)))
+        res = _rows_totals(out, tot, _abi.PREDICT_OUT, _abi.PREDICT_TOTALS)
         res["n"] = int(part[0])
         return res
 
@@ -556,16 +573,13 @@ class Engine:
         if not np.all((probs >= 0.0) & (probs <= 1.0)):
             raise ValueError("probabilities lie in [0, 1]")
         x = self._in(series)
-        if x.ndim != 2 or int(x.shape[1]) < 1 or int(x.shape[0]) < 1:
-            raise ValueError("a series is (nout, n)")
-        rows, n = int(x.shape[0]), int(x.shape[1])
+        rows, n = _series_shape(x)
         out = np.empty((probs.size, rows))
-        dbl = ctypes.POINTER(ctypes.c_double)
         for j in range(0, probs.size, _abi.PREDICT_MAX_PROBS):
             pj = np.ascontiguousarray(probs[j:j + _abi.PREDICT_MAX_PROBS])
             oj = np.empty((pj.size, rows))
-            _abi.check(self.lib, self.lib.rsf_predict_quantiles(self._ctx, n, rows, self._ptr(x), int(pj.size), pj.ctypes.data_as(dbl),
-                                                                oj.ctypes.data_as(dbl)))
+            _abi.check(self.lib, self.lib.rsf_predict_quantiles(self._ctx, n, rows, self._ptr(x), int(pj.size), _dp(pj),
+                                                                _dp(oj)))
             out[j:j + pj.size] = oj
         return out
 
@@ -579,14 +593,12 @@ class Engine:
         std2 is equal — has pareto_k = +inf and is not smoothed (ArviZ's behaviour).  Ranks of the tail are global over the
         draws: nothing here is additive over shards, a multi-rank pool is gathered first."""
         x, s2, obs = self._in(series), self._in(std2), self._in(data)
-        if x.ndim != 2 or int(x.shape[0]) < 1 or int(x.shape[1]) < 1:
-            raise ValueError("a series is (nout, n)")
-        rows, n = int(x.shape[0]), int(x.shape[1])
+        rows, n = _series_shape(x)
         if s2.ndim != 1 or int(s2.shape[0]) != n:
             raise ValueError(f"std2 has shape {tuple(s2.shape)}, the series has {n} draws")
         if obs.ndim != 1 or int(obs.shape[0]) != rows:
             raise ValueError(f"data has shape {tuple(obs.shape)}, the series has {rows} rows")
-        lpd = np.ascontiguousarray(np.asarray(lpd.cpu() if hasattr(lpd, "cpu") else lpd, dtype=np.float64))
+        lpd = _host(lpd)
         if lpd.shape != (rows,):
             raise ValueError(f"lpd has shape {lpd.shape}, the series has {rows} rows")
         r_eff = float(r_eff)
@@ -594,13 +606,11 @@ class Engine:
             raise ValueError("r_eff is finite and > 0")
         out = np.empty((rows, len(_abi.PSIS_OUT)))
         tot = np.empty(len(_abi.PSIS_TOTALS))
-        dbl = ctypes.POINTER(ctypes.c_double)
         _abi.check(self.lib, self.lib.rsf_predict_psis_loo(self._ctx, n, rows, self._ptr(x), self._ptr(s2), self._ptr(obs), r_eff,
-                                                           out.ctypes.data_as(dbl)))
-        _abi.check(self.lib, self.lib.rsf_predict_psis_finish(rows, n, out.ctypes.data_as(dbl), lpd.ctypes.data_as(dbl),
-                                                              tot.ctypes.data_as(dbl)))
-        res = {name: np.ascontiguousarray(out[:, j]) for j, name in enumerate(_abi.PSIS_OUT)}
-        res.update({name: float(v) for name, v in zip(_abi.PSIS_TOTALS, tot)})
+                                                           _dp(out)))
+        _abi.check(self.lib, self.lib.rsf_predict_psis_finish(rows, n, _dp(out), _dp(lpd),
+                                                              _dp(tot)))
+        res = _rows_totals(out, tot, _abi.PSIS_OUT, _abi.PSIS_TOTALS)
         res["n"] = n
         return res
 
@@ -617,15 +627,12 @@ class Engine:
         if probs.ndim != 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
             raise ValueError("probs is a sequence of probabilities in [0, 1]")
 
-        def host(x):
-            return np.asarray(x.cpu() if hasattr(x, "cpu") else x, dtype=np.float64)
-
         if center is None:
-            qm = host(q.mean(0)).reshape(d)
+            qm = _host(q.mean(0)).reshape(d)
             _, acc = self.forward(qm[:1], a=qm[1:2] if d == 3 else None, b=qm[2:3] if d == 3 else None)
-            cy = host(acc).reshape(self.nout)
-            ms = float(host(std2).mean())
-            cl = -0.5 * np.log(2.0 * np.pi * ms) - (host(data) - cy) ** 2 / (2.0 * ms)
+            cy = _host(acc).reshape(self.nout)
+            ms = float(_host(std2).mean())
+            cl = -0.5 * np.log(2.0 * np.pi * ms) - (_host(data) - cy) ** 2 / (2.0 * ms)
             if not (np.isfinite(cy).all() and np.isfinite(cl).all()):
                 raise ValueError("the series at the draws' mean parameters is not finite; pass center=(center_y, center_l)")
         else:
