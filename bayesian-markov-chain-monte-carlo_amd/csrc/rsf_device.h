@@ -1,4 +1,4 @@
-// rsf_device.h — device-side building blocks of the gfx950 kernels (included by rsf_hip.hip only).
+// rsf_device.h — device-side building blocks of the gfx950 kernels (included by the units of csrc/ through the kernel headers; no kernel is defined here).
 //
 //   Philox4x32-10 counter RNG + Box-Muller normals + Marsaglia-Tsang gamma   (K3)
 //   rate-and-state friction RHS and the classical RK4 step, per lane          (K1 core)
@@ -591,7 +591,7 @@ __device__ __forceinline__ void emit_trip(const double (&dv)[NU], const double (
 // with full evaluations for the lane, which from then on needs the next wider tier), when no alive lane needs a tier this
 // wide any more, or when no lane is alive.  All of that is ONE scalar branch at the end of the trip; the early-rejection
 // compare uses the sum of squares as the PREVIOUS trip left it, so the branch never waits for the trip's last result.
-constexpr int kTightUnroll = 8;  // steps per trip of the TIGHT loop (the one-parameter sampler runs 2 * kTightUnroll, rsf_kernels.h)
+constexpr int kTightUnroll = 8;  // steps per trip of the TIGHT loop (the one-parameter sampler runs 2 * kTightUnroll, rsf_kernels_sampler.h)
 constexpr int kNarrowUnroll = 8, kWiderUnroll = 4;  // NARROW; WIDE
 template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU>
 __device__ __forceinline__ int integrate_multi(const double *lds, const double *ld, const Consts &K, Lane L, int k0, int kn, int r,

@@ -1,5 +1,5 @@
 // rsf_diag.h — convergence diagnostics of a kept trace x[n][C][d] (include/rsf_diag.h): the device passes that produce the
-// additive partials of split R-hat, nested R-hat and the multi-chain ESS.  Included by rsf_hip.hip; the host finish that
+// additive partials of split R-hat, nested R-hat and the multi-chain ESS.  Included by rsf_diag.hip only; the host finish that
 // turns the partials into the statistics is plain C++ there (rsf_diag_finish).
 //
 //   diag_chain_kernel   pass 1a: one lane per chain, all d parameters (a wave reads 64*d contiguous doubles per row).  Split

@@ -1,6 +1,7 @@
 // rsf_diag_rank.h — rank-normalised diagnostics and order statistics of a kept trace x[n][C][d] (include/rsf_diag.h,
 // rsf_diag_rank_*): a device sort of every parameter's n*C draws and the four derived series that the existing diagnostics
-// kernels (rsf_diag.h) then reduce.  Included by rsf_hip.hip, which holds the host orchestration.
+// kernels (rsf_diag.h) then reduce.  Included by rsf_diag.hip only, which holds the host orchestration; the device functions that
+// the predictive kernels use as well are in rsf_rank_device.h.
 //
 // Sort.  A draw becomes an order-preserving uint64 key (-0.0 folded onto +0.0) paired with its 32-bit flat index i*C + c, and the
 // pairs go through an LSD radix sort, 8 bits per pass:
@@ -27,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsf_rank_device.h"
+
 namespace rsfk {
 
 constexpr int kRankThreads = 256;                       // workgroup size of every rank kernel
@@ -38,17 +41,6 @@ constexpr int kRankReduceBlocks = 1024;                 // HDI and range reducti
 constexpr int kRankStatHead = 10;                       // RSF_DIAG_RANK_STATS
 // stats[p][kRankStatHead + n_probs]: fields
 constexpr int kStMedian = 0, kStQ05 = 1, kStQ95 = 2, kStHdiLo = 3, kStHdiHi = 4, kStNonFinite = 5, kStConst = 6;
-
-// ---- keys --------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t rank_key(double v) {
-  uint64_t b = (uint64_t)__double_as_longlong(v);
-  if (b == 0x8000000000000000ull) b = 0;  // -0.0 == +0.0
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double rank_value(uint64_t k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
 
 // Wichura's AS241 (PPND16): the standard normal quantile in float64, relative error about 1e-16.
 __device__ double rank_ndtri(double p) {
@@ -481,80 +473,11 @@ rank_z_kernel(RankShape s, const uint64_t *__restrict__ keys, const uint32_t *__
 }
 
 // ---- order statistics ------------------------------------------------------------------------
-// np.quantile(method="linear") of n sorted values at probability prob: the two order statistics it interpolates between
-// (clamped to the ends) and the weight g of the upper one
-__device__ __forceinline__ void rank_pair(int64_t n, double prob, int64_t &lo, int64_t &hi, double &g) {
-#pragma clang fp contract(off)  // g is the rounded product minus its floor, as NumPy forms it
-  const double h = (double)(n - 1) * prob;
-  const double fl = floor(h);
-  lo = (int64_t)fl;
-  lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
-  hi = lo + 1 < n ? lo + 1 : n - 1;
-  g = h - fl;
-}
-// NumPy's _lerp
-__device__ __forceinline__ double rank_lerp(double a, double b, double g) {
-#pragma clang fp contract(off)  // bit for bit NumPy: no fused multiply-add
-  const double diff = b - a;
-  return g < 0.5 ? a + diff * g : b - diff * (1.0 - g);
-}
 __device__ double rank_quantile(const uint64_t *__restrict__ s, int64_t A, double prob) {
   int64_t lo, hi;
   double g;
   rank_pair(A, prob, lo, hi, g);
   return rank_lerp(rank_value(s[lo]), rank_value(s[hi]), g);
-}
-
-// The MSD radix select of up to MAXR order statistics of one row of n keys, for a workgroup of 256 threads: eight passes of
-// eight bits from the top, each a read of the row; per target rank a 256-bin histogram (LDS, integer atomics) of the keys that
-// agree with the rank's prefix so far, then one thread per rank walks its bins to the digit that holds the rank.  Thread q < nr
-// sets want[q] (the 0-based rank) before the call; after it prefix[q] is that order statistic's key.  key(j, pass): element j's.
-// (The workgroup reductions of these files — diag_block_sum, psis_block_reduce, psis_wave_sum, rank_block_scan, the shfl_xor
-// loops of diag_super_kernel, pred_sum8 — are NOT shared like this on purpose: each fixes its own summation order, and the
-// order is part of the results' bits.)
-template <int MAXR>
-struct RankSelect {
-  uint32_t hist[MAXR][256];
-  uint64_t prefix[MAXR];
-  uint32_t want[MAXR];
-};
-template <int MAXR, typename KEY>
-__device__ __forceinline__ void rank_select(RankSelect<MAXR> &S, int nr, int64_t n, KEY key) {
-  const unsigned t = threadIdx.x;
-  if (t < (unsigned)nr) S.prefix[t] = 0;
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = 56 - 8 * pass;
-    const uint64_t mask = pass == 0 ? 0ull : ~0ull << (shift + 8);
-    for (int e = t; e < nr * 256; e += 256) (&S.hist[0][0])[e] = 0;
-    __syncthreads();
-    const uint64_t pre = S.prefix[0];  // one rank: its prefix waits in a register (in pass 0 mask and prefix are both 0)
-    for (int64_t j = t; j < n; j += 256) {
-      const uint64_t k = key(j, pass);
-      const unsigned dig = (unsigned)(k >> shift) & 255u;
-      if constexpr (MAXR == 1) {
-        if ((k & mask) == pre) atomicAdd(&S.hist[0][dig], 1u);
-      } else if (pass == 0) {
-        atomicAdd(&S.hist[0][dig], 1u);  // no prefix yet: every rank shares one histogram
-      } else {
-        for (int q = 0; q < nr; ++q)
-          if ((k & mask) == S.prefix[q]) atomicAdd(&S.hist[q][dig], 1u);
-      }
-    }
-    __syncthreads();
-    if (t < (unsigned)nr) {
-      const uint32_t *hq = S.hist[pass == 0 ? 0 : t];
-      uint32_t below = 0, w = S.want[t];
-      int dig = 0;
-      for (; dig < 255; ++dig) {
-        const uint32_t c = hq[dig];
-        if (below + c > w) break;
-        below += c;
-      }
-      S.want[t] = w - below;
-      S.prefix[t] = (MAXR == 1 ? pre : S.prefix[t]) | (uint64_t)dig << shift;
-    }
-    __syncthreads();
-  }
 }
 
 // thread 0: median; 1, 2: quantiles 0.05, 0.95; 3 + i: probs[i]

@@ -1,0 +1,189 @@
+// rsf_finish.cpp — the host arithmetic that turns the device partials into the reported statistics: rsf_diag_finish,
+// rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish.  No ctx, no GPU: plain C++, the public headers and the
+// standard library only.
+#include <cmath>
+#include <cstdint>
+#include <algorithm>
+#include <vector>
+
+#include "../../include/rsf_abi.h"
+#include "../../include/rsf_diag.h"
+#include "../../include/rsf_predict.h"
+#include "../../include/rsf_psis.h"
+
+#pragma GCC visibility push(hidden)
+namespace rsfh { int fail(int code, const char *fmt, ...); }  // rsf_hip.hip: formats rsf_last_error()'s message, returns code
+#pragma GCC visibility pop
+using rsfh::fail;
+
+extern "C" {
+
+int rsf_diag_finish(int64_t n, int32_t d, int64_t S, const double *center, const double *partials, int64_t n_lags, double *out) {
+  if (!center || !partials || !out) return fail(RSF_ERR_INVALID, "rsf_diag_finish: NULL argument");
+  if (n < 4 || d < 1 || d > RSF_MAX_PARAMS || S < 0)
+    return fail(RSF_ERR_INVALID, "rsf_diag_finish: need n_iters >= 4, 1 <= n_params <= %d, chains_per_superchain >= 0", RSF_MAX_PARAMS);
+  const int64_t N = n / 2;
+  if (n_lags < 2 || n_lags > N) return fail(RSF_ERR_INVALID, "rsf_diag_finish: n_lags %lld outside [2, %lld]", (long long)n_lags, (long long)N);
+  const double Nd = (double)N;
+  std::vector<double> r((size_t)n_lags);
+  for (int p = 0; p < d; ++p) {
+    const double *q = partials + (int64_t)p * (RSF_DIAG_HEAD + n_lags);
+    double *o = out + (int64_t)p * RSF_DIAG_OUT;
+    for (int f = 0; f < RSF_DIAG_OUT; ++f) o[f] = NAN;
+    o[RSF_DIAG_K] = q[4];
+    o[RSF_DIAG_LAGS_COMPLETE] = 1.0;
+    bool finite = std::isfinite(center[p]);
+    for (int64_t f = 0; f < RSF_DIAG_HEAD + n_lags; ++f) finite = finite && std::isfinite(q[f]);
+    if (!finite) continue;  // a non-finite draw: every statistic of this parameter is NaN
+    const double Mp = q[0], ybar = q[1] / Mp, W = q[3] / Mp;
+    const double BN = (q[2] - q[1] * ybar) / (Mp - 1.0);
+    const double var_plus = (Nd - 1.0) / Nd * W + BN;
+    o[RSF_DIAG_MEAN] = center[p] + ybar;
+    o[RSF_DIAG_VAR_PLUS] = var_plus;
+    o[RSF_DIAG_W] = W;
+    o[RSF_DIAG_B_OVER_N] = BN;
+    const double K = q[4];
+    if (S > 0 && K > 1.0) {
+      const double B_nu = (q[6] - q[5] * q[5] / K) / (K - 1.0), W_nu = (q[7] + q[8]) / K;
+      if (W_nu > 0.0) o[RSF_DIAG_NESTED_RHAT] = std::sqrt(1.0 + B_nu / W_nu);
+    }
+    if (!(W > 0.0)) continue;  // every split chain constant
+    o[RSF_DIAG_SPLIT_RHAT] = std::sqrt(var_plus / W);
+    // ArviZ's _ess on the split chains, step by step (tests/diagnostics_reference.py), with the sequence cut at n_lags
+    auto rho = [&](int64_t t) { return 1.0 - (W - q[RSF_DIAG_HEAD + t] / Mp) / var_plus; };
+    std::fill(r.begin(), r.end(), 0.0);
+    double ev = 1.0, od = rho(1);
+    r[0] = ev; r[1] = od;
+    int64_t t = 1;
+    const int64_t lim = std::min(N - 3, n_lags - 2);  // the pair (t+1, t+2) needs lag t+2 < n_lags
+    while (t < lim && ev + od > 0.0) {  // Geyer's initial positive sequence
+      ev = rho(t + 1);
+      od = rho(t + 2);
+      if (ev + od >= 0.0) { r[t + 1] = ev; r[t + 2] = od; }
+      t += 2;
+    }
+    o[RSF_DIAG_LAGS_COMPLETE] = (ev + od > 0.0 && t < N - 3) ? 0.0 : 1.0;
+    const int64_t max_t = t - 2;
+    if (ev > 0.0) r[max_t + 1] = ev;
+    for (int64_t u = 1; u <= max_t - 2; u += 2)  // Geyer's initial monotone sequence
+      if (r[u + 1] + r[u + 2] > r[u - 1] + r[u]) { r[u + 1] = 0.5 * (r[u - 1] + r[u]); r[u + 2] = r[u + 1]; }
+    double tau = 0.0;
+    for (int64_t u = 0; u <= max_t; ++u) tau += r[u];
+    tau = -1.0 + 2.0 * tau + r[max_t + 1];
+    const double MN = Mp * Nd;
+    tau = std::max(tau, 1.0 / std::log10(MN));
+    o[RSF_DIAG_TAU] = tau;
+    o[RSF_DIAG_ESS] = MN / tau;
+    o[RSF_DIAG_MCSE_MEAN] = std::sqrt(var_plus / o[RSF_DIAG_ESS]);
+  }
+  return RSF_OK;
+}
+
+int rsf_diag_rank_finish(int64_t n, int32_t d, const double *stats, int32_t n_probs, const double *partials, int64_t n_lags, double *out) {
+  if (!stats || !partials || !out) return fail(RSF_ERR_INVALID, "rsf_diag_rank_finish: NULL argument");
+  if (n < 4 || d < 1 || d > RSF_MAX_PARAMS || n_probs < 0)
+    return fail(RSF_ERR_INVALID, "rsf_diag_rank_finish: need n_iters >= 4, 1 <= n_params <= %d, n_probs >= 0", RSF_MAX_PARAMS);
+  const int64_t N = n / 2;
+  if (n_lags < 2 || n_lags > N) return fail(RSF_ERR_INVALID, "rsf_diag_rank_finish: n_lags %lld outside [2, %lld]", (long long)n_lags, (long long)N);
+  const double zero[RSF_MAX_PARAMS] = {0.0, 0.0, 0.0};
+  std::vector<double> o((size_t)(RSF_DIAG_RANK_SERIES * d * RSF_DIAG_OUT));
+  for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
+    const int rc = rsf_diag_finish(n, d, 0, zero, partials + (int64_t)q * d * (RSF_DIAG_HEAD + n_lags), n_lags, o.data() + q * d * RSF_DIAG_OUT);
+    if (rc) return rc;
+  }
+  const int ns = RSF_DIAG_RANK_STATS + n_probs;
+  for (int p = 0; p < d; ++p) {
+    const double *st = stats + (int64_t)p * ns;
+    double *r = out + (int64_t)p * RSF_DIAG_RANK_OUT;
+    double ess[RSF_DIAG_RANK_SERIES], rh[RSF_DIAG_RANK_SERIES];
+    bool complete = true;
+    for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
+      const double *f = o.data() + (q * d + p) * RSF_DIAG_OUT;
+      const double T = partials[((int64_t)q * d + p) * (RSF_DIAG_HEAD + n_lags)] * (double)N;  // M' N
+      ess[q] = st[RSF_DIAG_RANK_CONST + q] != 0.0 ? T : f[RSF_DIAG_ESS];  // ArviZ _ess: a constant series has ess = M'N (tau = 1)
+      rh[q] = f[RSF_DIAG_SPLIT_RHAT];
+      complete = complete && f[RSF_DIAG_LAGS_COMPLETE] != 0.0;
+    }
+    for (int f = 0; f < RSF_DIAG_RANK_OUT; ++f) r[f] = NAN;
+    r[RSF_DIAG_RANK_LAGS_COMPLETE] = complete ? 1.0 : 0.0;
+    if (st[RSF_DIAG_RANK_NONFINITE] != 0.0) continue;
+    auto nanmax = [](double a, double b) { return std::isnan(a) || std::isnan(b) ? NAN : std::max(a, b); };
+    auto nanmin = [](double a, double b) { return std::isnan(a) || std::isnan(b) ? NAN : std::min(a, b); };
+    r[RSF_DIAG_RANK_RHAT_BULK] = rh[0];
+    r[RSF_DIAG_RANK_RHAT_TAIL] = rh[1];
+    r[RSF_DIAG_RANK_RHAT] = nanmax(rh[0], rh[1]);
+    r[RSF_DIAG_RANK_ESS_BULK] = ess[0];
+    r[RSF_DIAG_RANK_ESS_Q05] = ess[2];
+    r[RSF_DIAG_RANK_ESS_Q95] = ess[3];
+    r[RSF_DIAG_RANK_ESS_TAIL] = nanmin(ess[2], ess[3]);
+  }
+  return RSF_OK;
+}
+
+int rsf_predict_finish(int64_t n_rows, const double *partials, const double *center_y, const double *center_l, double *out_rows,
+                       double *out_totals) {
+  if (!partials || !center_y || !center_l || !out_rows || !out_totals) return fail(RSF_ERR_INVALID, "rsf_predict_finish: NULL argument");
+  if (n_rows < 1) return fail(RSF_ERR_INVALID, "rsf_predict_finish: n_rows < 1");
+  const double n = partials[0];
+  double elpd = 0.0, pw = 0.0;
+  for (int64_t k = 0; k < n_rows; ++k) {
+    const double *p = partials + RSF_PREDICT_HEAD + k * RSF_PREDICT_FIELDS;
+    double *o = out_rows + k * RSF_PREDICT_OUT;
+    bool finite = p[RSF_PREDICT_NONFINITE] == 0.0 && std::isfinite(center_y[k]) && std::isfinite(center_l[k]);
+    for (int f = 0; f < RSF_PREDICT_NONFINITE; ++f) finite = finite && std::isfinite(p[f]);
+    if (!finite) {  // a non-finite draw: every statistic of this output time is NaN
+      for (int f = 0; f < RSF_PREDICT_OUT; ++f) o[f] = NAN;
+    } else {
+      const double my = p[RSF_PREDICT_SUM_Y] / n, ml = p[RSF_PREDICT_SUM_L] / n;
+      o[RSF_PREDICT_MEAN] = center_y[k] + my;
+      o[RSF_PREDICT_VAR] = (p[RSF_PREDICT_SUM_Y2] - p[RSF_PREDICT_SUM_Y] * my) / (n - 1.0);
+      o[RSF_PREDICT_PIT] = p[RSF_PREDICT_SUM_PHI] / n;
+      o[RSF_PREDICT_LPD] = center_l[k] + std::log(p[RSF_PREDICT_SUM_EXP] / n);
+      o[RSF_PREDICT_P_WAIC] = (p[RSF_PREDICT_SUM_L2] - p[RSF_PREDICT_SUM_L] * ml) / (n - 1.0);
+    }
+    elpd += o[RSF_PREDICT_LPD] - o[RSF_PREDICT_P_WAIC];
+    pw += o[RSF_PREDICT_P_WAIC];
+  }
+  const double nr = (double)n_rows, me = elpd / nr;
+  double ss = 0.0;
+  for (int64_t k = 0; k < n_rows; ++k) {
+    const double e = out_rows[k * RSF_PREDICT_OUT + RSF_PREDICT_LPD] - out_rows[k * RSF_PREDICT_OUT + RSF_PREDICT_P_WAIC] - me;
+    ss += e * e;
+  }
+  out_totals[RSF_PREDICT_MEAN_STD2] = partials[1] / n;
+  out_totals[RSF_PREDICT_ELPD_WAIC] = elpd;
+  out_totals[RSF_PREDICT_P_WAIC_TOTAL] = pw;
+  out_totals[RSF_PREDICT_ELPD_WAIC_SE] = std::sqrt(nr * (ss / (nr - 1.0)));
+  return RSF_OK;
+}
+
+int rsf_predict_psis_finish(int64_t nout, int64_t n, const double *psis_rows, const double *lpd_rows, double *out_totals) {
+  if (!psis_rows || !lpd_rows || !out_totals) return fail(RSF_ERR_INVALID, "rsf_predict_psis_finish: NULL argument");
+  if (nout < 1 || n < 1) return fail(RSF_ERR_INVALID, "rsf_predict_psis_finish: nout < 1 or n < 1");
+  const double thr = n > 1 ? std::min(1.0 - 1.0 / std::log10((double)n), 0.7) : -INFINITY;
+  double elpd = 0.0, p = 0.0, kmax = -INFINITY, high = 0.0;
+  bool ok = true;
+  for (int64_t k = 0; k < nout; ++k) {
+    const double e = psis_rows[k * RSF_PSIS_OUT + RSF_PSIS_ELPD], pk = psis_rows[k * RSF_PSIS_OUT + RSF_PSIS_PARETO_K];
+    ok = ok && std::isfinite(e) && !std::isnan(pk) && std::isfinite(lpd_rows[k]);
+    elpd += e;
+    p += lpd_rows[k] - e;
+    kmax = std::max(kmax, pk);
+    high += pk > thr ? 1.0 : 0.0;
+  }
+  const double nr = (double)nout, me = elpd / nr;
+  double ss = 0.0;
+  for (int64_t k = 0; k < nout; ++k) {
+    const double e = psis_rows[k * RSF_PSIS_OUT + RSF_PSIS_ELPD] - me;
+    ss += e * e;
+  }
+  out_totals[RSF_PSIS_ELPD_LOO] = ok ? elpd : NAN;
+  out_totals[RSF_PSIS_P_LOO] = ok ? p : NAN;
+  out_totals[RSF_PSIS_ELPD_LOO_SE] = ok ? std::sqrt(nr * (ss / (nr - 1.0))) : NAN;
+  out_totals[RSF_PSIS_K_THRESHOLD] = thr;
+  out_totals[RSF_PSIS_N_HIGH_K] = ok ? high : NAN;
+  out_totals[RSF_PSIS_MAX_PARETO_K] = ok ? kmax : NAN;
+  return RSF_OK;
+}
+
+}  // extern "C"

@@ -1,315 +1,21 @@
-// rsf_kernels.h — the gfx950 kernels of the hot path (included by rsf_hip.hip, and by tools/ that build one kernel alone).
-//
-// One lane = one chain, wave64 = 64 independent chains, fp64 VALU bound; no MFMA — the path is an elementwise ODE
-// recurrence plus per-lane reductions, not a contraction:
-//   forward_kernel  K1  batched RateStateModel.evaluate + SSq        (RateStateModel.py:188-395, MCMC.py:381-387)
-//   init_kernel     K4  compute_initial_covariance + initial SSq     (MCMC.py:244-266, 468)
-//   mcmc_kernel     K2  n_iters fused Metropolis iterations          (MCMC.py:494-527)
-//   pool_*          posterior post-processing of the pooled draws    (RSF.py:717-746)
-//   probe_*         K3  Philox / variate self-test entry points
-// The chain-independent tables (loading velocity V_l at the RK4 stage times, observation) are staged through LDS once per
-// workgroup (or per chunk when they exceed the LDS budget) and read as wave-wide broadcasts; per-chain state lives in
-// registers for the whole launch and touches HBM only at launch start/end plus one coalesced trace row per iteration.
-//
-// Per-chain state in HBM is STRUCTURE OF ARRAYS — q[p][C], V[e][C], window sums likewise — so that lane i of a wave reads
-// element i of a contiguous 512-byte run whatever the number of parameters (the C ABI's [C][d] layout is transposed at
-// rsf_mcmc_init / get_state / set_state, rsf_hip.hip).
+// rsf_kernels_sampler.h — the sampler kernels: mcmc_kernel (float64 RK4, DOP853, and the chain logic alone on supplied sums of
+// squares), mcmc_f32x2_kernel (float32 solve, two chains per lane), and probe_adapt_kernel, the self-test of their window
+// arithmetic.  Included by rsf_sampler.hip only (probe_adapt_kernel is no template), and by tools/ that build one kernel alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
-#include "../../include/rsf_abi.h"
-#include "rsf_device.h"
+#include "rsf_kernel_common.h"
 #include "rsf_device_dop853.h"
 #include "rsf_device_f32.h"
 
 namespace rsfk {
 
-using rsf::Consts;
-
-enum Mode : int { RK4_F64 = 0, RK4_F32 = 1, DOP853 = 2 };  // how the ODE is integrated (rsf_model.flags)
-
-constexpr int kMaxBlock = 256;  // 4 waves: one per SIMD of a CU
-// Register budget of the sampler kernels: at least this many workgroups per CU, i.e. waves per SIMD (2 => at most 256 of
-// the 512 unified registers per lane).  cfg2 runs 4 waves per SIMD worth of chains, so a kernel that drifts above 256
-// registers would run it in four rounds instead of two; the DOP853 sampler is held to the same budget (unbounded it took
-// 300 registers and ran one wave per SIMD whatever the chain count: profiles/r02/dop853_occupancy_ab.log).
-constexpr int kMinBlocks = 2;
 // three-parameter sampler: TIGHT loop trips of kD3Trip * kTightUnroll steps like the one-parameter sampler's 2 * (+2.3 %
 // over 1 at 131 072 chains x nsteps 4000; the few spills it costs all lie outside the loops)
 constexpr int kD3Trip = 2;
-// LDS per workgroup for the loading table + observation chunk.  Two workgroups per CU (kMinBlocks) at 56 KiB each fit the
-// CU's 160 KiB next to the samplers' per-lane slots (up to 24 KiB: Cholesky factors, parked chain state); nsteps 2000
-// (48 KB) stays resident for the whole launch instead of being staged twice per proposal (+1.3 % at cfg2).  The chunk LENGTH
-// kc is sized for tables of doubles (rsf_set_model); the float32 SAMPLER, whose tables are floats, has its own (kc32: nsteps
-// 4000 is one resident chunk of 48 KB there), the other float32 kernels share kc with the float64 init kernel of that mode.
-constexpr size_t kLdsBudget = 56 * 1024;
-// LDS slots (doubles) of a sampler launch behind the table chunk, per lane: d = 3: the Cholesky factor's six per chain; the
-// float64 RK4 sampler adds the chain's point, sigma^2, SSq and log u parked across the forward solve (mcmc_kernel)
-constexpr int factor_slots(int d) { return d == 3 ? 6 : 0; }
-constexpr int park_slots(int d) { return factor_slots(d) + d + 3; }
-
-// ---------------------------------------------------------------------------------------------
-// kernels
-// ---------------------------------------------------------------------------------------------
-template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int MODE>
-__global__ void __launch_bounds__(kMaxBlock)
-forward_kernel(Consts K, int64_t n, const double *__restrict__ dc, const double *__restrict__ a,
-               const double *__restrict__ b, double *__restrict__ ssq_out, double *__restrict__ acc_out) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = i < n;
-  const double dci = active ? dc[i] : 1.0;
-  const double ai = (active && a) ? a[i] : K.a_def;
-  const double bi = (active && b) ? b[i] : K.b_def;
-  double *acc_i = WANT_ACC ? acc_out + i : nullptr;
-  const bool resident = K.nchunks == 1;
-  double ssq;
-  if constexpr (MODE == RK4_F32) {
-    float *lds32 = reinterpret_cast<float *>(lds);
-    if (resident) rsf::f32::stage_chunk32(lds32, K, 1, K.nout - 1);
-    ssq = rsf::f32::solve32<DAMP, WANT_SSQ, WANT_ACC>(lds32, K, resident, active, dci, ai, bi, acc_i, n);
-  } else {
-    if constexpr (MODE == DOP853) {
-      if (resident) rsf::dp::stage_chunk_dp(lds, K, 1, K.nout - 1);
-      ssq = rsf::dp::solve<DAMP, WANT_SSQ, WANT_ACC>(lds, K, resident, active, dci, ai, bi, acc_i, n);
-    } else {
-      if (resident) rsf::stage_chunk(lds, K, 1, K.nout - 1);
-      rsf::Wave W;  // every lane's result is wanted: no early rejection (thr = +inf), statistics unused
-      ssq = rsf::solve<DAMP, WANT_SSQ, WANT_ACC, 2 * rsf::kTightUnroll>(lds, K, resident, active, dci, ai, bi, INFINITY, acc_i, n, W);
-    }
-  }
-  if (WANT_SSQ && active) ssq_out[i] = ssq;
-}
-
-struct InitArgs {
-  int64_t C;
-  double fd;       // forward-difference relative step, MCMC.py:251
-  double inv_dof;  // 1 / (nout - len(qpriors)), MCMC.py:261
-  double width[RSF_MAX_PARAMS];  // hi - lo of the prior box (three-parameter chains: initial_covariance)
-  const double *q0;  // [d][C]
-  double *ssq, *std2, *V;  // [C], [C], [d*d][C]
-};
-
-// The initial proposal covariance from the sensitivities' Gram matrix X^T X and sigma^2_0.
-// One parameter — the reference's sampler: Vstart = sigma^2 (X^T X)^-1, MCMC.py:265-266, as it stands.
-// Three parameters (Dc, a, b) — this build's extension (BASELINE config 5), where that formula does not give a proposal:
-// the series depends on Dc and a almost only through their product (relative sensitivities equal to five digits, correlation
-// eigenvalue 2e-11) and hardly at all on b (3000 times smaller), so (X^T X)^-1 is astronomically wide along a ridge — and
-// what little it says there is forward-difference rounding.  The data do not identify those directions; the PRIOR does.  So
-// the box prior enters the way a Gaussian of the same variance would, in coordinates u_p = (q_p - lo_p) / w_p that make the box a
-// unit cube:        M = W (X^T X) W / sigma^2 + 12 I,      V = W M^-1 W,      W = diag(w_p = hi_p - lo_p)
-// (a uniform variable on a unit interval has variance 1/12).  M is symmetric positive definite with every eigenvalue >= 12
-// (condition number ~4e3 at the BASELINE problem): no guard, no fallback.  Identified directions get their Gauss-Newton
-// width, unidentified ones the width of the box.
-template <int D>
-__device__ __forceinline__ void initial_covariance(const double *xtx, double std2, const double *width, double *V) {
-  if constexpr (D == 1) {
-    V[0] = std2 * (1.0 / xtx[0]);
-  } else {
-    double M[D * D], Mi[D * D];
-    const double is2 = 1.0 / std2;
-#pragma unroll
-    for (int p = 0; p < D; ++p)
-#pragma unroll
-      for (int r = 0; r < D; ++r) M[p * D + r] = (width[p] * xtx[p * D + r] * width[r]) * is2 + (p == r ? 12.0 : 0.0);
-    rsf::sym_inverse<D>(M, Mi);
-#pragma unroll
-    for (int p = 0; p < D; ++p)
-#pragma unroll
-      for (int r = 0; r < D; ++r) V[p * D + r] = width[p] * Mi[p * D + r] * width[r];
-  }
-}
-
-// compute_initial_covariance + the initial SSq (MCMC.py:244-266, 468): ONE LANE PER TRAJECTORY.  A chain owns a group of
-// G = D + 1 adjacent lanes (a pair for one parameter, a quad for three): lane 0 of the group integrates the chain's start
-// point, lane p + 1 the point with parameter p moved by the forward-difference step (MCMC.py:251) — each with the sampler's
-// own straight-line tier code and nothing but the forward kernel's registers.  Where an output sample completes, the
-// group's lanes exchange their acceleration samples by lane shuffles: every lane forms its sensitivity against lane 0's
-// sample (perturbed value in the denominator, MCMC.py:264), lane 0 collects them and accumulates the residual and X^T X,
-// sample by sample, without storing trajectories.  (Until round 4 ONE lane carried all 1 + D trajectories in lockstep: four
-// sets of lane constants and states, 256 VGPRs + 42-120 AGPRs of spills, one wave per SIMD.)
-// The acceleration sample is cv * (sum of the interval's weighted V-derivative sums), like the sampler's (rsf::emit_incr):
-// the initial SSq is the value the sampler computes for the same point to rounding, and the difference of two trajectories'
-// samples — which a relative step of 1e-6 amplifies a million-fold — does not go through two velocities near V_ref.
-template <int D>
-struct InitGroup {
-  static constexpr int G = D + 1;  // lanes per chain: 2 or 4, a power of two, so a group never straddles a wave
-  const unsigned t = threadIdx.x;
-  const int tr = (int)(t & (G - 1));                                              // which trajectory of its chain this lane integrates
-  const int64_t chain = (int64_t)blockIdx.x * (blockDim.x / G) + (t / G);
-  const int lane0 = (int)((t & 63) & ~(unsigned)(G - 1));                         // the group's first lane within the wave
-  double xtx[D * D], ssq = 0.0;
-
-  __device__ __forceinline__ InitGroup() {
-#pragma unroll
-    for (int e = 0; e < D * D; ++e) xtx[e] = 0.0;
-  }
-  // the observation series of the workgroup's chain group (all of a workgroup's chains belong to one)
-  __device__ __forceinline__ void select_group(Consts &K) const {
-    if (K.group_chains > 0) K.data += (((int64_t)blockIdx.x * (blockDim.x / G)) / K.group_chains) * K.nout;
-  }
-  // this lane's parameter vector (Dc, a, b) and, for a perturbed trajectory, 1 / (perturbed value * step)
-  __device__ __forceinline__ void parameters(const Consts &K, const InitArgs &A, bool active, double (&pq)[3], double &inv_den) const {
-    pq[0] = 1000.0; pq[1] = K.a_def; pq[2] = K.b_def;
-    if (active) {
-      pq[0] = A.q0[chain];
-      if (D == 3) { pq[1] = A.q0[A.C + chain]; pq[2] = A.q0[2 * A.C + chain]; }
-    }
-    inv_den = 0.0;
-#pragma unroll
-    for (int p = 0; p < D; ++p)
-      if (tr == p + 1) {
-        pq[p] = pq[p] * (1 + A.fd);
-        inv_den = 1.0 / (pq[p] * A.fd);  // perturbed value in the denominator, MCMC.py:264
-      }
-  }
-  // the value lane `SRC` of this lane's group holds.  A group is an aligned pair or quad of lanes, so this is a DPP quad_perm move
-  template <int SRC>
-  static __device__ __forceinline__ double from_lane(double v) {
-    return rsf::dpp_move<G == 4 ? (SRC | SRC << 2 | SRC << 4 | SRC << 6) : (SRC | SRC << 2 | (2 + SRC) << 4 | (2 + SRC) << 6)>(v);
-  }
-  template <int P>
-  __device__ __forceinline__ void gather(double x, double (&xs)[D]) const {
-    if constexpr (P < D) {
-      xs[P] = from_lane<P + 1>(x);
-      gather<P + 1>(x, xs);
-    }
-  }
-  // an output sample is complete: ak = this lane's acceleration sample, obs the observation (every lane of the group calls, in
-  // converged control flow).  Only the upper triangle of X^T X is accumulated; finish() mirrors it
-  __device__ __forceinline__ void sample(double ak, double obs, double inv_den) {
-    const double ak0 = from_lane<0>(ak);
-    const double x = (ak - ak0) * inv_den;  // lane p + 1: the sensitivity to parameter p; lane 0: 0
-    double xs[D];
-    gather<0>(x, xs);
-    const double r = ak - obs;  // meaningful in lane 0 (the others accumulate values nobody reads)
-    ssq = __builtin_fma(r, r, ssq);
-#pragma unroll
-    for (int p = 0; p < D; ++p)
-#pragma unroll
-      for (int r2 = p; r2 < D; ++r2) xtx[p * D + r2] = __builtin_fma(xs[p], xs[r2], xtx[p * D + r2]);
-  }
-  __device__ __forceinline__ void finish(const InitArgs &A, bool active) const {
-    if (active && tr == 0) {
-      const double std2 = ssq * A.inv_dof;
-      double V[D * D], M[D * D];
-#pragma unroll
-      for (int p = 0; p < D; ++p)
-#pragma unroll
-        for (int r2 = 0; r2 < D; ++r2) M[p * D + r2] = xtx[p <= r2 ? p * D + r2 : r2 * D + p];
-      initial_covariance<D>(M, std2, A.width, V);
-#pragma unroll
-      for (int e = 0; e < D * D; ++e) A.V[e * A.C + chain] = V[e];  // MCMC.py:266
-      A.std2[chain] = std2;
-      A.ssq[chain] = ssq;
-    }
-  }
-};
-
-template <int D, bool DAMP>
-__global__ void __launch_bounds__(kMaxBlock, kMinBlocks) init_kernel(Consts K, InitArgs A) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  InitGroup<D> grp;
-  grp.select_group(K);
-  const bool active = grp.chain < A.C;
-  double pq[3], inv_den;
-  grp.parameters(K, A, active, pq, inv_den);
-  const rsf::Lane L = rsf::make_lane<DAMP>(pq[0], pq[1], pq[2], K);
-  rsf::State st = rsf::initial_state(pq[0], L, K);
-  if (active) { const double d0 = K.data[0]; grp.ssq = d0 * d0; }
-  const double *ld = lds + rsf::lds_data_offset(K);
-  for (int k0 = 1; k0 < K.nout; k0 += K.kc) {
-    const int kn = min(K.kc, K.nout - k0);
-    rsf::stage_chunk(lds, K, k0, kn);
-    rsf::integrate_lockstep<DAMP>(lds, K, L, st, kn, [&](double ak, int ko) { grp.sample(ak, ld[ko], inv_den); }, [] {});
-  }
-  grp.finish(A, active);
-}
-
-// compute_initial_covariance + initial SSq in the reference's DOP853 scheme, one lane per trajectory like init_kernel: every
-// lane takes its own dop853 calls interval by interval (its own carried step size); the group's lanes meet at every
-// output sample.
-template <int D, bool DAMP>
-__global__ void __launch_bounds__(kMaxBlock, kMinBlocks) init_dp_kernel(Consts K, InitArgs A) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  InitGroup<D> grp;
-  grp.select_group(K);
-  const bool active = grp.chain < A.C;
-  double pq[3], inv_den;
-  grp.parameters(K, A, active, pq, inv_den);
-  const rsf::dp::LaneD L = rsf::dp::make_lane_dp(pq[0], pq[1], pq[2]);
-  rsf::dp::Carry cw = rsf::dp::fresh_carry();
-  double y[3] = {K.mu0, pq[0] / K.V_ref, K.V_ref}, x = K.t0, vprev = K.V_ref;
-  bool failed = false;
-  if (active) { const double d0 = K.data[0]; grp.ssq = d0 * d0; }
-  const double *ld = lds + rsf::dp::lds_data_offset_dp(K);
-  const double delta_t = K.dt;
-  for (int k0 = 1; k0 < K.nout; k0 += K.kc) {
-    const int kn = min(K.kc, K.nout - k0);
-    rsf::dp::stage_chunk_dp(lds, K, k0, kn);
-    for (int kk = 0; kk < kn; ++kk) {
-      double ak = 0.0;  // a trajectory whose integrator failed leaves zeros, like the reference (RateStateModel.py:361-366, 381)
-      if (!failed) {
-        failed = !rsf::dp::call<DAMP>(K, L, lds + rsf::dp::kTab * kk, x, x + delta_t, y, cw, true);
-        ak = (y[2] - vprev) * K.inv_dt;
-        vprev = y[2];
-      }
-      grp.sample(ak, ld[kk], inv_den);
-    }
-  }
-  grp.finish(A, active);
-}
-
-// float32 mode: the sampler compares sums of squares from float32 solves, so the initial SSq (computed by the
-// float64 init kernel together with the float64-only sensitivities) is replaced by its float32 value.
-template <int D, bool DAMP>
-__global__ void __launch_bounds__(kMaxBlock) ssq32_kernel(Consts K, int64_t C, const double *q, double *ssq) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  rsf::select_group(K);
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = i < C;
-  const double dc = active ? q[i] : 1.0;
-  const double a = (active && D == 3) ? q[C + i] : K.a_def, b = (active && D == 3) ? q[2 * C + i] : K.b_def;
-  const double s = rsf::f32::solve32<DAMP, true, false>(reinterpret_cast<float *>(lds), K, false, active, dc, a, b, nullptr, 0);
-  if (active) ssq[i] = s;
-}
-
-// The accept test of MCMC.py:327-331: log alpha = clip(0.5 (SSq_prev - SSq_new) / sigma^2, -inf, 0) > log u.  np.clip keeps a
-// NaN, and NaN > log u is False: a proposal whose series blew up (a stiff small-Dc lane under fixed-step RK4: Inf - Inf) is
-// REJECTED.  fmin(x, 0) would not do: IEEE minNum returns the operand that is not NaN, i.e. 0 > log u, accepted — which is
-// what this kernel did until round 4, unnoticed because no test before the wide-proposal ones produced a non-finite sum.
-__device__ __forceinline__ bool accept_test(double ratio, double log_u) {
-  const double logalpha = ratio > 0.0 ? 0.0 : ratio;  // NaN > 0 is false: NaN stays NaN
-  return logalpha > log_u;                             // NaN compares false => reject
-}
-
-// The proposal of MCMC.py:497 from the chain's point, the lower Cholesky factor of its proposal covariance (row-major
-// lower triangle, D (D + 1) / 2 entries) and D standard normals — one definition, so that rsf_mcmc_propose announces
-// exactly the point the sampler kernels will evaluate.
-template <int D, typename F>
-__device__ __forceinline__ void propose(const double (&q)[D], F factor, const double *z, double (&qn)[D]) {
-  int e = 0;
-#pragma unroll
-  for (int p = 0; p < D; ++p) {
-    double s = q[p];
-#pragma unroll
-    for (int r = 0; r <= p; ++r) s = __builtin_fma(factor(e++), z[r], s);
-    qn[p] = s;
-  }
-}
-
-// (ARGS: a kernel-argument struct with lo[] / hi[] members, indexed in place — a pointer INTO the argument block would make
-// these per-lane flat loads, on the vector-memory counter the trace stores sit on, instead of scalar loads)
-template <int D, typename ARGS>
-__device__ __forceinline__ bool in_box(const double (&qn)[D], const ARGS &A) {
-  bool inb = true;
-#pragma unroll
-  for (int p = 0; p < D; ++p) inb = inb && (qn[p] > A.lo[p]) && (qn[p] < A.hi[p]);  // strict box, MCMC.py:318-320
-  return inb;
-}
 
 // Per-wave statistics of a sampler launch: wave-uniform 32-bit accumulators (scalar registers), added to the ctx totals
 // (McmcArgs::stats, 64-bit) by the wave's first lane.  Index = RSF_CNT_* of rsf_abi.h.
@@ -335,28 +41,6 @@ struct WaveCounters {
     reset();
   }
 };
-
-struct McmcArgs {
-  int64_t C, chain_offset, n_iters, iter_base;
-  uint64_t seed;
-  double n0, shape;
-  double gd, gc;  // Marsaglia-Tsang constants of Gamma(shape): d = shape - 1/3, c = 1/sqrt(9 d)
-  double lo[RSF_MAX_PARAMS], hi[RSF_MAX_PARAMS];
-  int32_t adapt_mode, adapt_interval;
-  int32_t lc_off;     // D = 3: offset (in doubles) of the per-lane Cholesky factors behind the table chunk in LDS
-  double dict_scale;  // 2.38^2 / len(qpriors.keys()), MCMC.py:200 (reference_dict mode)
-  double am_eps[RSF_MAX_PARAMS];  // am mode: (1e-6 (hi - lo))^2 added to the history's variances (rsf::window_covariance)
-  double *q, *ssq, *std2, *V;           // per-chain state: q[d][C], ssq[C], std2[C], V[d*d][C]
-  double *wref, *wsum, *wsq;            // adaptation window (shifted sums): [d][C], [d][C], [d*d][C]
-  int32_t *wn;
-  double *wbuf;                         // reference_dict: the window's samples themselves, [adapt_interval][C] (rsf::np_cov_1d)
-  unsigned long long *stats;            // [RSF_CNT_COUNT] totals since rsf_mcmc_init (rsf_abi.h: rsf_mcmc_counters)
-  const double *z, *u, *g;              // replay variates (REPLAY only): z[n][C][d], u[n][C], g[n][C]
-  const double *ssq_new;                // INJECT only: the proposals' sums of squares, [n][C] (rsf_mcmc_replay_ssq)
-  double *tq, *ts;                      // traces, iteration-major: tq[n][C][d] (the ABI's layout), ts[n][C]
-  uint8_t *ta;
-};
-
 
 // Parts of the iteration shared by mcmc_kernel and mcmc_f32x2_kernel (with propose and accept_test above).  A replayed
 // variate is element row0 + lane of its [n][C] array: mcmc_kernel passes its lane's own row and lane 0.
@@ -463,7 +147,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
   // integrator needs — the spills per proposal these kernels had otherwise.
   constexpr bool kPark = MODE == RK4_F64;  // (the DOP853 kernel allocates worse with it: measured, tools/one_kernel.sh)
   constexpr int kSlotQ = factor_slots(D), kSlotStd2 = kSlotQ + D, kSlotSsq = kSlotStd2 + 1, kSlotLu = kSlotSsq + 1;
-  static_assert(kSlotLu + 1 == park_slots(D), "rsf_hip.hip sizes the launch's LDS with park_slots");
+  static_assert(kSlotLu + 1 == park_slots(D), "rsf_sampler.hip sizes the launch's LDS with park_slots");
 
   // Every lane walks its OWN chain through iterations 0 .. n_iters-1 (nl: the lane's next one).  A round of the loop below
   // gives every lane that has no proposal in hand its next one; a proposal outside the prior box is a finished iteration
@@ -668,38 +352,6 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
     at(A.std2, 0)[t] = std2;
   }
   cnt.flush(A.stats);
-}
-
-// rsf_mcmc_propose: the proposal the next iteration of mcmc_kernel will make from z, and whether it is inside the box
-struct ProposeArgs {
-  int64_t C;
-  const double *q, *V;  // [d][C], [d*d][C]
-  const double *z;      // [C][d]
-  double lo[RSF_MAX_PARAMS], hi[RSF_MAX_PARAMS];
-  double *qn;           // [C][d]
-  uint8_t *inb;         // [C]
-};
-
-template <int D>
-__global__ void __launch_bounds__(kMaxBlock) propose_kernel(ProposeArgs A) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.C) return;
-  double q[D], V[D * D], Lf[D * D], z[D], qn[D];
-#pragma unroll
-  for (int p = 0; p < D; ++p) { q[p] = A.q[p * A.C + i]; z[p] = A.z[i * D + p]; }
-#pragma unroll
-  for (int e = 0; e < D * D; ++e) V[e] = A.V[e * A.C + i];
-  rsf::chol_lower<D>(V, Lf);
-  double tri[D * (D + 1) / 2];
-  int e = 0;
-#pragma unroll
-  for (int p = 0; p < D; ++p)
-#pragma unroll
-    for (int r = 0; r <= p; ++r) tri[e++] = Lf[p * D + r];
-  propose<D>(q, [&](int k) { return tri[k]; }, z, qn);
-#pragma unroll
-  for (int p = 0; p < D; ++p) A.qn[i * D + p] = qn[p];
-  A.inb[i] = in_box<D>(qn, A) ? 1 : 0;
 }
 
 // The float32 sampler (RSF_FLAG_FP32_SOLVE): the same iteration as mcmc_kernel, with TWO chains per lane, because its
@@ -985,154 +637,6 @@ __global__ void probe_adapt_kernel(int d, int n, const double *win, int mode, do
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   if (d == 1) adapt_window<1>(n, win, mode, dict_scale, out);
   else adapt_window<3>(n, win, mode, dict_scale, out);
-}
-
-// [n][d] <-> [d][n] between the C ABI's per-chain layout and the kernels' structure of arrays (d = 3 only; for one
-// parameter the two coincide)
-__global__ void __launch_bounds__(kMaxBlock) transpose_kernel(int64_t n, int d, const double *__restrict__ src, double *__restrict__ dst, bool to_soa) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  for (int e = 0; e < d; ++e) {
-    if (to_soa) dst[(int64_t)e * n + i] = src[i * d + e];
-    else dst[i * d + e] = src[(int64_t)e * n + i];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// posterior post-processing on pooled samples (RSF.plot_dist, RSF.py:717-746)
-// ---------------------------------------------------------------------------------------------
-constexpr int kPoolBlocks = 1024;  // 4 workgroups per CU; partials are combined deterministically (no atomics)
-
-struct PoolPartial {
-  double cnt, sum, sumsq, mn, mx;  // sums are taken about a common shift for stability
-};
-
-__global__ void __launch_bounds__(kMaxBlock)
-pool_moments_kernel(int64_t n, const double *__restrict__ x, int64_t stride, double shift, PoolPartial *__restrict__ part) {
-  __shared__ PoolPartial sh[kMaxBlock / 64];
-  double cnt = 0.0, sum = 0.0, sumsq = 0.0, mn = INFINITY, mx = -INFINITY;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const double v = x[i * stride], dlt = v - shift;
-    cnt += 1.0; sum += dlt; sumsq = __builtin_fma(dlt, dlt, sumsq);
-    mn = fmin(mn, v); mx = fmax(mx, v);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off, 64); sum += __shfl_down(sum, off, 64); sumsq += __shfl_down(sumsq, off, 64);
-    mn = fmin(mn, __shfl_down(mn, off, 64)); mx = fmax(mx, __shfl_down(mx, off, 64));
-  }
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = {cnt, sum, sumsq, mn, mx};
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    PoolPartial p = sh[0];
-    for (unsigned w = 1; w < blockDim.x / 64; ++w) {
-      p.cnt += sh[w].cnt; p.sum += sh[w].sum; p.sumsq += sh[w].sumsq; p.mn = fmin(p.mn, sh[w].mn); p.mx = fmax(p.mx, sh[w].mx);
-    }
-    part[blockIdx.x] = p;
-  }
-}
-
-// Fixed-bin histogram (rsf_pool_histogram): HBM-bound, one pass.  Every workgroup counts into an LDS copy of the bins
-// (ds_add_u32), then adds its non-empty bins to the global 64-bit counters — integer atomics, so the result does not
-// depend on the order of arrival.  The bin of a sample is numpy.histogram's, edge cases included: a first guess
-// floor((x - lo) * nbins/(hi - lo)), then numpy's own correction against the bin EDGES np.linspace(lo, hi, nbins + 1)
-// (edge b = b * step + lo, two roundings — formed here with contraction switched off), so that a sample
-// sitting exactly on an edge — a chain that rejects repeats values like q0 — lands where numpy puts it.
-constexpr int kHistMaxBins = 4096;
-
-__device__ __forceinline__ double hist_edge(int b, double lo, double hi, double step, int nbins) {
-#pragma clang fp contract(off)  // numpy's edge is a product rounded, then a sum rounded: no fused multiply-add here
-  const double m = (double)b * step;
-  return b == nbins ? hi : m + lo;
-}
-
-__device__ __forceinline__ int hist_bin(double v, double lo, double hi, double scale, double step, int nbins) {
-  if (v < lo) return 0;
-  if (!(v <= hi)) return nbins + 1;                      // above hi, or NaN
-  int b = (int)((v - lo) * scale);
-  b = b < nbins ? b : nbins - 1;                         // v == hi (or rounding at the upper edge) -> last bin
-  if (v < hist_edge(b, lo, hi, step, nbins)) --b;        // the guess is within one bin of the truth; the edges decide
-  if (b != nbins - 1 && v >= hist_edge(b + 1, lo, hi, step, nbins)) ++b;
-  return 1 + b;
-}
-
-__global__ void __launch_bounds__(kMaxBlock)
-pool_hist_kernel(int64_t n, const double *__restrict__ x, int64_t stride, int nbins, double lo, double hi, double scale, double step,
-                 unsigned long long *__restrict__ counts) {
-  extern __shared__ unsigned int hbins[];
-  for (int b = threadIdx.x; b < nbins + 2; b += blockDim.x) hbins[b] = 0u;
-  __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    atomicAdd(&hbins[hist_bin(x[i * stride], lo, hi, scale, step, nbins)], 1u);
-  __syncthreads();
-  for (int b = threadIdx.x; b < nbins + 2; b += blockDim.x)
-    if (hbins[b]) atomicAdd(&counts[b], (unsigned long long)hbins[b]);
-}
-
-__global__ void __launch_bounds__(kMaxBlock) pool_hist_finish_kernel(int nb, const unsigned long long *__restrict__ counts, double *__restrict__ out) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < nb) out[b] = (double)counts[b];
-}
-
-// Each workgroup owns a contiguous slice of the samples, streamed through LDS in tiles; every thread
-// accumulates the kernel sum of its grid points over the slice (LDS broadcast reads).  partial[block][m].
-constexpr int kKdeTile = 1024;
-
-__global__ void __launch_bounds__(kMaxBlock)
-pool_kde_kernel(int64_t n, const double *__restrict__ x, int64_t stride, int m, const double *__restrict__ grid, double inv2c,
-                double *__restrict__ partial) {
-  __shared__ double tile[kKdeTile];
-  const int64_t per = (n + gridDim.x - 1) / gridDim.x, lo = (int64_t)blockIdx.x * per, hi = min(n, lo + per);
-  for (int j0 = 0; j0 < m; j0 += blockDim.x) {
-    const int j = j0 + threadIdx.x;
-    const double g = j < m ? grid[j] : 0.0;
-    double acc = 0.0;
-    for (int64_t t0 = lo; t0 < hi; t0 += kKdeTile) {
-      const int tn = (int)min((int64_t)kKdeTile, hi - t0);
-      __syncthreads();
-      for (int t = threadIdx.x; t < tn; t += blockDim.x) tile[t] = x[(t0 + t) * stride];
-      __syncthreads();
-      for (int t = 0; t < tn; ++t) {
-        const double dlt = g - tile[t];
-        acc += rsf::fm::exp(-dlt * dlt * inv2c);
-      }
-    }
-    if (j < m) partial[(int64_t)blockIdx.x * m + j] = acc;
-  }
-}
-
-__global__ void __launch_bounds__(kMaxBlock)
-pool_kde_reduce_kernel(int nblocks, int m, const double *__restrict__ partial, double norm, double *__restrict__ density) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
-  double acc = 0.0;
-  for (int b = 0; b < nblocks; ++b) acc += partial[(int64_t)b * m + j];  // fixed order: reproducible
-  density[j] = acc * norm;
-}
-
-// out[0..3] = philox words (as doubles are not used here): layout documented at the call sites
-__global__ void probe_philox_kernel(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                    uint32_t *out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    uint32_t w[4];
-    rsf::philox4x32_10(c0, c1, c2, c3, k0, k1, w);
-    for (int j = 0; j < 4; ++j) out[j] = w[j];
-  }
-}
-
-// out = { z0, z1, z2, u, g }
-__global__ void probe_draws_kernel(uint64_t seed, uint64_t chain, uint32_t iter, int d, double shape, double *out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    uint32_t w[4];
-    double z[4] = {0, 0, 0, 0};
-    rsf::draw_words(seed, chain, iter, rsf::SLOT_Z01, w);
-    rsf::normal_pair(w, z[0], z[1]);
-    if (d > 2) { rsf::draw_words(seed, chain, iter, rsf::SLOT_Z2, w); rsf::normal_pair(w, z[2], z[3]); }
-    rsf::draw_words(seed, chain, iter, rsf::SLOT_U, w);
-    out[0] = z[0]; out[1] = z[1]; out[2] = z[2];
-    out[3] = rsf::u53(w[0], w[1]);
-    out[4] = rsf::gamma_draw(seed, chain, iter, shape - 1.0 / 3.0, 1.0 / sqrt(9.0 * (shape - 1.0 / 3.0)));
-  }
 }
 
 }  // namespace rsfk

@@ -19,8 +19,9 @@
 
 #include <type_traits>
 
-#include "rsf_kernels.h"
-#include "rsf_diag_rank.h"
+#include "rsf_kernel_common.h"
+#include "rsf_device.h"
+#include "rsf_rank_device.h"
 
 namespace rsfk {
 

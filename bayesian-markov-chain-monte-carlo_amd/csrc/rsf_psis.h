@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rsf_diag_rank.h"
+#include "rsf_rank_device.h"
 
 namespace rsfk {
 

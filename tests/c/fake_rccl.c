@@ -4,7 +4,7 @@
  * Real RCCL refuses two ranks on the same device, and the build container has no GPU at all, so the code around the
  * library's collectives (rsf_comm_init / rsf_comm_init_all, the bytes*world staging, the rank-major receive layout, the
  * destroy / re-init order) could otherwise only ever execute on the driver's 8-GPU node.  This file implements the nine
- * nccl* entry points the product binds (csrc/rsf_hip.hip, struct Rccl) with the semantics of the real ones as far as a
+ * nccl* entry points the product binds (csrc/rsf_comm.hip, struct Rccl) with the semantics of the real ones as far as a
  * caller can observe them:
  *   - ncclCommInitRank blocks until all `nranks` ranks holding the same unique id have joined (one thread per rank);
  *   - ncclCommInitAll makes all ranks at once for a single thread;

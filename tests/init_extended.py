@@ -9,7 +9,7 @@ its distance from a float64 init is that init's own rounding, amplified by the f
   X        X_pk = (acc_k(q^(p)) - acc_k(q)) / (q^(p)_p fd), q^(p) = q with parameter p times (1 + fd), formed in float64 as the
            kernel and the restatement form it, then widened exactly (the perturbed value in the denominator, MCMC.py:264)
   V        d = 1: std2_0 / X^T X (MCMC.py:265-266); d = 3: W M^-1 W with M = W X^T X W / std2_0 + 12 I, W = diag(hi - lo)
-           (csrc/rsf_kernels.h initial_covariance)
+           (csrc/rsf_kernels_core.h initial_covariance)
 np.linalg rejects longdouble: the 3x3 inverse is written out by cofactors (inverse3).
 """
 import numpy as np

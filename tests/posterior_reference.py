@@ -2,7 +2,7 @@
 The sampler's exact target, computed by quadrature (a test helper; TEST INFRASTRUCTURE ONLY, no GPU).
 
 With n0 = 0 one sampler iteration — a symmetric Metropolis step on q given sigma^2 inside a strict box, then the Gibbs draw
-sigma^2 = 0.5 SSq / G, G ~ Gamma(shape), shape = 0.5 nout (csrc/rsf_kernels.h: metropolis, gibbs_std2) — is an exact
+sigma^2 = 0.5 SSq / G, G ~ Gamma(shape), shape = 0.5 nout (csrc/rsf_kernels_sampler.h: metropolis, gibbs_std2) — is an exact
 Metropolis-within-Gibbs chain for
 
     pi(q, sigma^2) ~ 1_box(q) sigma^(-2 shape - 2) exp(-SSq(q) / 2 sigma^2)

@@ -783,7 +783,7 @@ def test_observation_groups(gpu_engine, cpu_engine, oracle_mod):
 
 def test_three_parameter_chains(gpu_engine, cpu_engine, oracle_mod):
     """Extension (BASELINE config 5): joint (Dc, a, b).  The init kernel's proposal covariance — prior-regularised, since
-    sigma^2 (X^T X)^-1 alone is astronomically wide along the (Dc, a) ridge (rsf_kernels.h::initial_covariance) — agrees with
+    sigma^2 (X^T X)^-1 alone is astronomically wide along the (Dc, a) ridge (rsf_kernels_core.h::initial_covariance) — agrees with
     the checker's to 1e-4 at a forward-difference step of 1e-4 (condition number ~4e3 times the ~1e-8 the step leaves of the
     trajectories' rounding), from three different start points; then chains from a common explicit state, which must really
     move."""
@@ -1370,7 +1370,7 @@ def test_early_rejection_changes_nothing_observable(pkg, oracle_mod, golden):
             tq_n, ts_n, ta_n = (np.asarray(x) for x in e.mcmc_run(iters))
         ta_o = np.unpackbits(g[f"{case}_accept_bits"], axis=1, count=C).astype(ta_n.dtype)
         # The round-3 build ACCEPTED a proposal whose sum of squares was NaN (fmin(NaN, 0) = 0 > log u: see accept_test in
-        # rsf_kernels.h) — a stiff Dc < 0.35 proposal under fixed-step RK4 — and such a chain then accepts everything.  Those
+        # rsf_kernel_common.h) — a stiff Dc < 0.35 proposal under fixed-step RK4 — and such a chain then accepts everything.  Those
         # chains are that build's bug, not a difference to explain: they show as a non-finite sigma^2 there, are few, are
         # finite here, and are left out of the comparison.
         bugged = np.unpackbits(g[f"{case}_nonfinite_bits"], count=C).astype(bool)

@@ -5,7 +5,7 @@ A/B timing of kernel builds in ONE process with interleaved rounds (same device,
   python tools/ab_bench.py [--chains C] [--nsteps N] [--iters I] [--rounds R] name=path.so ...
 
 Each variant is a build of an edited copy of csrc/ (the kernels' tunables are constexpr values in rsf_device.h /
-rsf_kernels.h: copy the directory, change one, `make`, pass the .so here); "default" is the in-tree librsf_hip.so.  Prints median / min milliseconds per launch and ODE-steps*chains/s.
+rsf_kernel_common.h / rsf_kernels_sampler.h: copy the directory, change one, `make`, pass the .so here); "default" is the in-tree librsf_hip.so.  Prints median / min milliseconds per launch and ODE-steps*chains/s.
 """
 import argparse
 import ctypes

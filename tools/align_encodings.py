@@ -7,13 +7,14 @@ configs[1] +0.65 %, configs[2] 0.0 %, config 5's shard in float64 +1.2 %.  The p
 packed-float32 stream of the float32 sampler's trip (which aligns itself); the float64 kernels' VOP3 instructions do not
 pay it to any extent worth a second build pipeline.  Kept as the record of how that was established:
 
-  hipcc <flags> --cuda-device-only -S -o dev.s rsf_hip.hip
+  hipcc <flags> --cuda-device-only -S -o dev.s rsf_sampler.hip        (one unit of csrc/ at a time: its device code alone)
   python tools/align_encodings.py dev.s dev_al.s --report
   clang -x assembler -target amdgcn-amd-amdhsa -mcpu=gfx950 -c dev_al.s -o dev.o
   lld -flavor gnu -m elf64_amdgpu --no-undefined -shared -o dev.out dev.o
   clang-offload-bundler -type=o -bundle-align=4096 -targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950 \
       -input=/dev/null -input=dev.out -output=dev.hipfb
-  hipcc <flags> --cuda-host-only -Xclang -fcuda-include-gpubinary -Xclang dev.hipfb -shared -o librsf_hip.so rsf_hip.hip
+  hipcc <flags> --cuda-host-only -Xclang -fcuda-include-gpubinary -Xclang dev.hipfb -c -o obj/rsf_sampler.o rsf_sampler.hip
+  make -C csrc          (the other units' objects as usual, then the one link of all of them)
 
   python tools/align_encodings.py in.s out.s [--report]        (in.s: hipcc --cuda-device-only -S; out.s: to be assembled)
 

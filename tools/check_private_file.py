@@ -26,7 +26,7 @@ def main():
     base = int(re.search(r"#define RSF_F32_TRIP_COMPILER_VGPRS (\d+)", inc).group(1))
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "k.hip")
-        open(src, "w").write(f'#include "{CSRC}/rsf_kernels.h"\nnamespace rsfk {{ template __global__ void {inst}(rsf::Consts, McmcArgs); }}\n')
+        open(src, "w").write(f'#include "{CSRC}/rsf_kernels_sampler.h"\nnamespace rsfk {{ template __global__ void {inst}(rsf::Consts, McmcArgs); }}\n')
         p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", os.path.join(d, "k.s"), src],
                            capture_output=True, text=True)
         if p.returncode:

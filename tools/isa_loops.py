@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """List the loops of one kernel in a device ISA listing with their instruction mix (no GPU needed).
 
-  hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o /tmp/rsf.s csrc/rsf_hip.hip
+  hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o /tmp/rsf.s csrc/rsf_sampler.hip     (the unit that holds the kernel: csrc/Makefile, DEVICE_UNITS)
   python tools/isa_loops.py /tmp/rsf.s mcmc_kernelILi1ELb1ELb0ELi0E [min_valu] [max_valu]
 
 A loop = a backward branch to a label; reported: VALU / SALU / LDS instruction counts and the commonest opcodes.  The TIGHT

@@ -3,10 +3,12 @@
 
     tools/kernel_diff.py build/parent/librsf_hip.so bayesian-markov-chain-monte-carlo_amd/csrc/librsf_hip.so
 
-Takes the gfx950 code object out of each library, disassembles it and compares the instruction text of every kernel symbol
-with addresses stripped, so that a different ORDER of the kernels in the object does not count.  The one instruction whose
+Takes the gfx950 code objects out of each library (one offload bundle per translation unit in its .hip_fatbin section),
+disassembles them and compares the instruction text of every kernel symbol across the union, with addresses stripped, so that
+neither the ORDER of the kernels in an object nor the object a kernel lies in counts.  The one instruction whose
 encoding depends on where its kernel lies, the s_add_u32 after an s_getpc_b64 that forms the address of a constant table,
-is compared by the address it forms and by the bytes of .rodata from there to the section's end.  Prints one line per kernel
+is compared by the bytes of its own code object's .rodata from the address it forms to the section's end.  Trailing
+s_nop padding of a listing is dropped: it follows the last kernel of each code object only.  Prints one line per kernel
 that differs or exists on one side only, then a summary; exit status 1 if anything differs.  A host-side refactor must print
 none: anything else means a header was touched or an instantiation was added or dropped.
 """
@@ -19,10 +21,27 @@ LLVM = "/opt/rocm/llvm/bin/"
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
 def kernels(lib, tmp, tag):
-    fat, co = f"{tmp}/{tag}.fatbin", f"{tmp}/{tag}.co"
+    fat = f"{tmp}/{tag}.fatbin"
     subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-    subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fat}", f"--output={co}"])
+    section = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), section)]
+    assert starts, f"{lib}: no offload bundle in .hip_fatbin"
+    out = {}
+    for i, (at, end) in enumerate(zip(starts, starts[1:] + [len(section)])):
+        one, co = f"{tmp}/{tag}{i}.fatbin", f"{tmp}/{tag}{i}.co"
+        open(one, "wb").write(section[at:end])
+        subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={one}", f"--output={co}"])
+        for name, lines in code_object(co).items():
+            assert name not in out, f"{lib}: {name} is in two code objects"
+            out[name] = lines
+    return out
+
+
+def code_object(co):
     text = subprocess.check_output([LLVM + "llvm-objdump", "-d", co], text=True)
     ro_at, ro = rodata(co)
     out, name, getpc = {}, None, False
@@ -37,17 +56,25 @@ def kernels(lib, tmp, tag):
             if getpc and m:  # s_getpc_b64 gave this instruction's address
                 lit = int(m.group(2), 16)
                 at = int(m.group(3), 16) + (lit - (1 << 32) if lit >> 31 else lit)
+                # (equal bytes to the END of .rodata in two code objects: the DOP853 tableau is the tail of .rodata in every unit
+                # that has it; a unit with another table behind it would show as a difference here, not pass unseen)
                 data = ro[at - ro_at:] if ro_at <= at < ro_at + len(ro) else None
-                out[name].append(f"s_add_u32 {m.group(1)}: pc-relative address {at:#x} of {data!r}")
+                out[name].append(f"s_add_u32 {m.group(1)}: pc-relative address of {data!r}")
             else:
                 out[name].append(re.sub(r"//\s*[0-9A-Fa-f]+:", "//", line.strip()))
             getpc = "s_getpc_b64" in line
+    for lines in out.values():  # the padding behind a code object's last kernel (s_nop 0, shown in part as "...") belongs to no kernel
+        while lines and lines[-1].split("//")[0].strip() in ("s_nop 0", "..."):
+            lines.pop()
     return out
 
 
 def rodata(co):
     head = subprocess.check_output([LLVM + "llvm-objdump", "-h", co], text=True)
-    at = int(re.search(r"\.rodata\s+[0-9a-f]+\s+([0-9a-f]+)", head).group(1), 16)
+    m = re.search(r"\.rodata\s+[0-9a-f]+\s+([0-9a-f]+)", head)
+    if not m:  # a unit whose kernels read no constant table
+        return 0, b""
+    at = int(m.group(1), 16)
     dump = subprocess.check_output([LLVM + "llvm-objdump", "-s", "-j", ".rodata", co], text=True)
     rows = [re.match(r" [0-9a-f]+ ((?:[0-9a-f]+ ?)+) ", l) for l in dump.splitlines()]
     data = bytes.fromhex("".join(m.group(1).replace(" ", "") for m in rows if m))

@@ -5,7 +5,8 @@
 INST=$1; shift
 CSRC="$(cd "$(dirname "$0")/../bayesian-markov-chain-monte-carlo_amd/csrc" && pwd)"
 cat > /tmp/one_kernel.hip <<SRC
-#include "$CSRC/rsf_kernels.h"
+#include "$CSRC/rsf_kernels_core.h"
+#include "$CSRC/rsf_kernels_sampler.h"
 namespace rsfk { template __global__ void $INST; }
 SRC
 cd /tmp && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -no-hip-rt "$@" -Rpass-analysis=kernel-resource-usage -save-temps -c -o /tmp/one_kernel.o /tmp/one_kernel.hip 2>&1 \

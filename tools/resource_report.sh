@@ -2,7 +2,13 @@
 # Per-kernel VGPR / AGPR / scratch / occupancy of the product build (compiler remarks; no GPU needed).
 #   tools/resource_report.sh [extra hipcc flags...]
 cd "$(dirname "$0")/../bayesian-markov-chain-monte-carlo_amd/csrc"
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -no-hip-rt "$@" -Rpass-analysis=kernel-resource-usage -c -o /tmp/rsf_hip_report.o rsf_hip.hip 2> /tmp/rsf_report.txt
+# every unit that holds kernels (DEVICE_UNITS of csrc/Makefile), compiled side by side; one list
+UNITS=$(make -s print-device-units)
+for u in $UNITS; do
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 "$@" -Rpass-analysis=kernel-resource-usage -c -o /tmp/${u}_report.o $u.hip 2> /tmp/${u}_report.txt &
+done
+wait
+for u in $UNITS; do cat /tmp/${u}_report.txt; done > /tmp/rsf_report.txt
 python3 - <<'PY'
 import re
 txt = open('/tmp/rsf_report.txt').read()

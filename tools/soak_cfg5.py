@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Statistical validation of the joint (Dc, a, b) inference (BASELINE config 5) — the three-parameter analogue of
 tools/soak_tier3.py.  Chains start AWAY from the truth, with the proposal covariance the init kernel itself provides
-(prior-regularised Gauss-Newton, csrc/rsf_kernels.h::initial_covariance) — nothing hand-set.
+(prior-regularised Gauss-Newton, csrc/rsf_kernels_core.h::initial_covariance) — nothing hand-set.
 
   1. GPU pool vs independent chains of the CPU oracle (other seed, same lengths), for the fixed initial covariance ("none":
      plain Metropolis) and for "am": pooled means of Dc, a, b and of the one combination the data identify, Dc*a, must agree
