@@ -67,13 +67,17 @@ class PosteriorPool:
         from rank_diagnostics).  Ranks of the tail are global: a multi-rank pool is gathered first."""
         return self.predictive(model, data, probs=(), max_draws=max_draws, engine=engine, substeps=substeps, loo=True, r_eff=r_eff)
 
-    def predictive(self, model, data, probs=(0.05, 0.5, 0.95), max_draws=None, engine=None, substeps=None, loo=False, r_eff=1.0):
+    def predictive(self, model, data, probs=(0.05, 0.5, 0.95), max_draws=None, engine=None, substeps=None, loo=False, r_eff=1.0,
+                   noise_probs=()):
         """Posterior predictive checks of the kept draws against the observation `data`, computed on the GPU (Engine.predictive):
         the draws are mapped back through `model`'s ODE (float64 RK4, `substeps` steps per output interval — by default the
         model's own) → dict with, per output time, mean, var, pit, lpd, p_waic_k and the quantiles `probs` of the model series
         (the credible band), and the totals elpd_waic, p_waic, elpd_waic_se, mean_std2.  max_draws: use an evenly strided subset
         of at most that many draws (deterministic; the band materialises n * nout * 8 bytes).  engine: an Engine to run on (its
-        model is set here); by default a host-memory engine made for the call.  loo=True adds the PSIS-LOO entries (see loo)."""
+        model is set here); by default a host-memory engine made for the call.  loo=True adds the PSIS-LOO entries (see loo).
+        `quantiles` is the credible band of the clean model series; it does not contain the noise, and most observations lie
+        outside it when the posterior is tight.  noise_probs (each strictly inside (0, 1)) adds `noise_quantiles`, the posterior
+        predictive band of an observation — the quantiles of mean_i N(y_ik, std2_i) — which is the band to overlay on the data."""
         n, C, d = self.samples.shape
         q = np.asarray(self.samples.cpu() if hasattr(self.samples, "cpu") else self.samples, dtype=np.float64).reshape(n * C, d)
         s2 = np.asarray(self.std2.cpu() if hasattr(self.std2, "cpu") else self.std2, dtype=np.float64).reshape(n * C)
@@ -84,7 +88,9 @@ class PosteriorPool:
                 idx = (np.arange(int(max_draws), dtype=np.int64) * (n * C)) // int(max_draws)  # evenly strided, no RNG
                 q, s2 = q[idx], s2[idx]
         S = int(getattr(model, "substeps", 1) if substeps is None else substeps)
-        extra = dict(loo=True, r_eff=r_eff) if loo else {}  # without loo the engine is called as it always was
+        extra = dict(loo=True, r_eff=r_eff) if loo else {}  # without loo or noise_probs the engine is called as it always was
+        if np.size(noise_probs):
+            extra["noise_probs"] = noise_probs
         if engine is not None:
             engine.set_model(model, S)
             return engine.predictive(q, s2, data, probs=probs, **extra)

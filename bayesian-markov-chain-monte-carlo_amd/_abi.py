@@ -170,6 +170,14 @@ PSIS_TOTALS = ("elpd_loo", "p_loo", "elpd_loo_se", "k_threshold", "n_high_k", "m
 PSIS_MAX_TAIL = 8192  # RSF_PSIS_MAX_TAIL: largest ceil(min(0.2 n, 3 sqrt(n / r_eff)))
 
 
+# include/rsf_predict_noise.h: the predictive band that includes the noise; exported by librsf_hip.so only, bound by load()
+PREDICT_NOISE_PROTOTYPES = {
+    "rsf_predict_noise_quantiles": (c_int, [c_void_p, c_int64, c_int64, _P, _P, c_int32, POINTER(c_double), POINTER(c_double),
+                                            POINTER(c_int32)]),
+}
+PREDICT_NOISE_MAX_PASSES = 129  # RSF_PREDICT_NOISE_MAX_PASSES: pass 0, at most 64 bisections and 64 Newton steps
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -213,7 +221,7 @@ def load():
                                "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
-        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES):
+        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -1,6 +1,7 @@
-// rsf_predict.hip — posterior predictive checks and PSIS-LOO on the device (include/rsf_predict.h, include/rsf_psis.h):
-// rsf_predict_partials / _quantiles / _psis_loo (kernels: rsf_predict.h, rsf_psis.h).  The host arithmetic that finishes
-// their results is rsf_finish.cpp.
+// rsf_predict.hip — posterior predictive checks, PSIS-LOO and the predictive band with noise on the device
+// (include/rsf_predict.h, include/rsf_psis.h, include/rsf_predict_noise.h): rsf_predict_partials / _quantiles / _psis_loo /
+// _noise_quantiles (kernels: rsf_predict.h, rsf_psis.h, rsf_predict_noise.h).  The host arithmetic that finishes their results
+// is rsf_finish.cpp.
 #include <climits>
 #include <cmath>
 #include <algorithm>
@@ -10,6 +11,7 @@
 #include "rsf_host.h"
 #include "rsf_predict.h"
 #include "rsf_psis.h"
+#include "rsf_predict_noise.h"
 
 using namespace rsfk;
 using namespace rsfh;
@@ -147,6 +149,42 @@ int rsf_predict_psis_loo(rsf_ctx *c, int64_t n, int64_t nout, const double *seri
   if ((rc = launch(c, psis_row_kernel, (unsigned)nout, kPsisThreads, lds, A))) return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_rows, c->poolws.p, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RSF_OK;
+}
+
+int rsf_predict_noise_quantiles(rsf_ctx *c, int64_t n, int64_t nout, const double *series, const double *std2, int32_t n_probs,
+                                const double *probs, double *out, int32_t *passes_out) {
+  RSF_ENTER(c, NEED_NOTHING, series && std2 && probs && out, "NULL argument");
+  int rc;
+  if ((rc = check_series_shape(__func__, n, nout))) return rc;
+  if (n_probs < 1 || n_probs > RSF_PREDICT_MAX_PROBS)
+    return fail(RSF_ERR_INVALID, "rsf_predict_noise_quantiles: n_probs outside 1..%d", RSF_PREDICT_MAX_PROBS);
+  static_assert(kNoiseMaxProbs == RSF_PREDICT_MAX_PROBS && kNoiseMaxPasses == RSF_PREDICT_NOISE_MAX_PASSES,
+                "csrc/rsf_predict_noise.h and include/rsf_predict_noise.h agree");
+  for (int i = 0; i < n_probs; ++i)
+    if (!(probs[i] > 0.0 && probs[i] < 1.0))
+      return fail(RSF_ERR_INVALID, "rsf_predict_noise_quantiles: probs[%d] is not strictly inside (0, 1)", i);
+  const size_t nb = (size_t)n * sizeof(double);
+  const double *ds, *dstd2;
+  // (the largest allocation first: it fails before anything is copied)
+  if ((rc = stage_series(c, __func__, SLOT_SERIES, series, n, nout, &ds))) return rc;
+  if ((rc = stage_in(c, SLOT_STD2, std2, nb, &dstd2))) return rc;
+  // workspace: the draws' constants [2][n] and the std2 flag in c->predict; out [n_probs][nout], then the passes [nout], in c->poolws
+  const size_t ob = (size_t)n_probs * (size_t)nout * sizeof(double), pb = (size_t)nout * sizeof(int32_t);
+  if ((rc = ensure(c->predict, 2 * nb + sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(c->poolws, ob + pb))) return rc;
+  NoiseArgs A{};
+  A.n = n; A.nout = nout; A.series = ds; A.par = (const double *)c->predict.p; A.bad = (const uint32_t *)((const char *)c->predict.p + 2 * nb);
+  A.out = (double *)c->poolws.p; A.passes = (int32_t *)((char *)c->poolws.p + ob); A.nprobs = n_probs;
+  std::copy(probs, probs + n_probs, A.p);
+  HIP_TRY(hipMemsetAsync((void *)A.bad, 0, sizeof(uint32_t), c->stream));
+  if ((rc = launch(c, noise_params_kernel, (unsigned)((n + 255) / 256), 256, 0, n, dstd2, (double *)c->predict.p, (uint32_t *)A.bad))) return rc;
+  // the row kernel unrolls its loops over the targets: few probabilities take the short one (a target's arithmetic is the same in both)
+  if ((rc = launch(c, n_probs <= 4 ? noise_quantile_row_kernel<4> : noise_quantile_row_kernel<kNoiseMaxProbs>, (unsigned)nout, kNoiseThreads, 0, A))) return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, A.out, ob, hipMemcpyDeviceToHost, c->stream));
+  if (passes_out) HIP_TRY(hipMemcpyAsync(passes_out, A.passes, pb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RSF_OK;
 }

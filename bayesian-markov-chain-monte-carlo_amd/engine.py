@@ -614,18 +614,55 @@ class Engine:
         res["n"] = n
         return res
 
-    def predictive(self, q, std2, data, probs=(), center=None, return_series=False, loo=False, r_eff=1.0):
+    def predictive_noise_quantiles(self, series, std2, probs, return_passes=False):
+        """rsf_predict_noise_quantiles: the quantiles `probs` of the posterior predictive distribution of an OBSERVATION at
+        every output time, the mixture mean_i N(y_ki, std2_i), of a series (nout, n) in this engine's memory space (as
+        predictive_partials(return_series=True) leaves it) with the draws' noise variances std2 (n,) → (len(probs), nout)
+        float64 on the host: the posterior predictive band, in which the data are expected to lie.  (predictive_quantiles is
+        the credible band of the clean model series, which says where the ODE solution lies and is narrower by the noise.)
+        Probabilities lie strictly inside (0, 1).  return_passes: also the passes the kernel made over each row (nout,) int32,
+        at most PREDICT_NOISE_MAX_PASSES (the largest over the batches of PREDICT_MAX_PROBS probabilities).  A probability's
+        result does not depend on which others are asked with it.  F is a mean over all draws: a multi-rank pool is gathered first."""
+        probs = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if probs.ndim != 1 or probs.size < 1:
+            raise ValueError("probs is a non-empty sequence of probabilities")
+        if not np.all((probs > 0.0) & (probs < 1.0)):
+            raise ValueError("probabilities lie strictly inside (0, 1)")
+        x, s2 = self._in(series), self._in(std2)
+        rows, n = _series_shape(x)
+        if s2.ndim != 1 or int(s2.shape[0]) != n:
+            raise ValueError(f"std2 has shape {tuple(s2.shape)}, the series has {n} draws")
+        out = np.empty((probs.size, rows))
+        passes = np.zeros(rows, dtype=np.int32)
+        for j in range(0, probs.size, _abi.PREDICT_MAX_PROBS):
+            pj = np.ascontiguousarray(probs[j:j + _abi.PREDICT_MAX_PROBS])
+            oj = np.empty((pj.size, rows))
+            ps = np.empty(rows, dtype=np.int32)
+            _abi.check(self.lib, self.lib.rsf_predict_noise_quantiles(self._ctx, n, rows, self._ptr(x), self._ptr(s2), int(pj.size), _dp(pj),
+                                                                      _dp(oj), ps.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+            out[j:j + pj.size] = oj
+            np.maximum(passes, ps, out=passes)
+        return (out, passes) if return_passes else out
+
+    def predictive(self, q, std2, data, probs=(), center=None, return_series=False, loo=False, r_eff=1.0, noise_probs=()):
         """Posterior predictive checks of n draws against the observation `data`: per output time the model series' mean and
         variance over the draws, the probability integral transform of the observation (pit), the log pointwise predictive
         density (lpd) and the WAIC penalty (p_waic_k); the totals mean_std2, elpd_waic, p_waic, elpd_waic_se; with `probs` the
         exact quantiles (len(probs), nout) of the series over the draws, the credible band.  center = (center_y, center_l)
         (default: the series at the draws' mean parameter vector, and its log density with the mean sigma^2).  With probs or
         return_series the series (nout, n) is materialised: n * nout * 8 bytes.  loo=True materialises it as well and adds
-        psis_loo's entries (with r_eff) to the result; the default leaves the result as it is without."""
+        psis_loo's entries (with r_eff) to the result; the default leaves the result as it is without.
+        Two bands: `quantiles` (from probs) is the CREDIBLE band of the model series — where the clean ODE solution lies;
+        `noise_quantiles` (from noise_probs, each strictly inside (0, 1); see predictive_noise_quantiles) is the POSTERIOR
+        PREDICTIVE band — where an observation lies, the inferred noise included: the one to overlay on the data.  A non-empty
+        noise_probs materialises the series and adds the keys noise_probs and noise_quantiles; the default adds nothing."""
         q, std2, data, n, d = self._predict_args(q, std2, data)
         probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
         if probs.ndim != 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
             raise ValueError("probs is a sequence of probabilities in [0, 1]")
+        noise_probs = np.atleast_1d(np.asarray(noise_probs, dtype=np.float64))
+        if noise_probs.ndim != 1 or not np.all((noise_probs > 0.0) & (noise_probs < 1.0)):
+            raise ValueError("noise_probs is a sequence of probabilities strictly inside (0, 1)")
 
         if center is None:
             qm = _host(q.mean(0)).reshape(d)
@@ -638,7 +675,7 @@ class Engine:
         else:
             cy, cl = center
         cy, cl = self._predict_centers(cy, cl)
-        want_series = bool(return_series) or probs.size > 0 or bool(loo)
+        want_series = bool(return_series) or probs.size > 0 or bool(loo) or noise_probs.size > 0
         part = self.predictive_partials(q, std2, data, cy, cl, return_series=want_series)
         series = None
         if want_series:
@@ -649,6 +686,8 @@ class Engine:
             res["probs"], res["quantiles"] = probs, self.predictive_quantiles(series, probs)
         if loo:
             res.update({name: v for name, v in self.psis_loo(series, std2, data, res["lpd"], r_eff=r_eff).items() if name != "n"})
+        if noise_probs.size:
+            res["noise_probs"], res["noise_quantiles"] = noise_probs, self.predictive_noise_quantiles(series, std2, noise_probs)
         if return_series:
             res["series"] = series
         return res

@@ -1,7 +1,8 @@
 /*
  * rsf_predict.h — posterior predictive checks of pooled draws: the model series' credible spread, the probability
  * integral transform of the observation, the log pointwise predictive density and WAIC, exact credible bands, and PSIS-LOO
- * with the Pareto shape per output time (rsf_psis.h, included at the end).
+ * with the Pareto shape per output time (rsf_psis.h, included at the end), and the predictive band of an observation, noise
+ * included (rsf_predict_noise.h, included at the end).
  *
  * Exported by librsf_hip.so only (the CPU checker implements rsf_abi.h alone; tests/predictive_reference.py is the
  * specification these entry points are tested against).  Same conventions as rsf_abi.h: int status, rsf_last_error(),
@@ -90,5 +91,7 @@ int rsf_predict_quantiles(rsf_ctx *ctx, int64_t n, int64_t nout, const double *s
 
 /* PSIS-LOO and the Pareto shape per output time, on the series this header's entry points leave: declared in rsf_psis.h */
 #include "rsf_psis.h"
+/* The predictive band that includes the noise (quantiles of the mixture mean_i N(y_ik, s2_i)): declared in rsf_predict_noise.h */
+#include "rsf_predict_noise.h"
 
 #endif /* RSF_PREDICT_H */
