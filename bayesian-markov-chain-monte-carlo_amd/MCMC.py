@@ -24,11 +24,11 @@ import numpy as np
 if __package__:
     from . import _figures
     from ._abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from .engine import Engine
+    from .engine import Engine, _host
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     from _abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from engine import Engine
+    from engine import Engine, _host
 
 
 class PosteriorPool:
@@ -97,6 +97,46 @@ class PosteriorPool:
         with Engine(mem="host") as eng:
             eng.set_model(model, S)
             return eng.predictive(q, s2, data, probs=probs, **extra)
+
+    def joint(self, engine=None):
+        """Mean, covariance (ddof = 1) and correlation matrix of the kept draws over all parameters, computed on the GPU
+        (Engine.pool_joint) → dict(n, nonfinite, mean (d,), cov (d, d), corr (d, d))."""
+        if engine is not None:
+            return engine.pool_joint(self.samples)
+        with Engine(mem="host") as eng:
+            return eng.pool_joint(self.samples)
+
+    def corner(self, nbins=40, grid=32, probs=(0.5, 0.9), ranges=None, engine=None):
+        """Everything a corner plot of the kept draws needs, computed on the GPU; drawing is the caller's.  → dict with
+        joint (see joint), ranges (d, 2), probs,
+        marginals: per parameter p dict(counts (nbins,) and edges (nbins + 1,) of the 1-D histogram on ranges[p], grid (grid,) and
+        density (grid,) of the 1-D Gaussian KDE), and
+        pairs: {(i, j): dict(counts (nbins, nbins) with xedges and yedges as numpy.histogram2d returns them for (x_i, x_j),
+        x (grid,), y (grid,) and density (grid, grid) — density[k, l] at (x[k], y[l]), the 2-D Gaussian KDE — and levels, the
+        highest-density contour levels of `counts` at `probs`)} for i < j.
+        ranges: (d, 2) of (lo, hi) per parameter; by default each parameter's min and max, so that every draw is counted."""
+        if engine is None:
+            with Engine(mem="host") as eng:
+                return self.corner(nbins, grid, probs, ranges, eng)
+        x = self.samples
+        d, nbins, grid = int(x.shape[-1]), int(nbins), int(grid)
+        if ranges is None:
+            ranges = [(s["min"], s["max"]) for s in (engine.pool_summary(x, p) for p in range(d))]
+        ranges = np.asarray(ranges, dtype=np.float64).reshape(d, 2)
+        axes = [np.linspace(lo, hi, grid) for lo, hi in ranges]
+        edges = [np.linspace(lo, hi, nbins + 1) for lo, hi in ranges]
+        res = {"joint": engine.pool_joint(x), "ranges": ranges, "probs": np.asarray(probs, dtype=np.float64), "marginals": [], "pairs": {}}
+        for p in range(d):
+            res["marginals"].append({"counts": _host(engine.pool_histogram(x, nbins, ranges[p, 0], ranges[p, 1], param=p))[1:-1],
+                                     "edges": edges[p], "grid": axes[p], "density": _host(engine.pool_kde(x, axes[p], param=p))})
+        for i in range(d):
+            for j in range(i + 1, d):
+                counts = _host(engine.pool_histogram2d(x, nbins, (ranges[i], ranges[j]), params=(i, j)))[1:-1, 1:-1]
+                mesh = np.stack(np.meshgrid(axes[i], axes[j], indexing="ij"), axis=-1).reshape(grid * grid, 2)
+                res["pairs"][i, j] = {"counts": counts, "xedges": edges[i], "yedges": edges[j], "x": axes[i], "y": axes[j],
+                                      "density": _host(engine.pool_kde2d(x, mesh, params=(i, j))).reshape(grid, grid),
+                                      "levels": engine.pool_hpd_levels(counts, probs)}
+        return res
 
     def pooled(self):
         """(d, n_keep*C): every kept draw of every chain, the reference's (d, n) layout."""

@@ -178,6 +178,21 @@ PREDICT_NOISE_PROTOTYPES = {
 PREDICT_NOISE_MAX_PASSES = 129  # RSF_PREDICT_NOISE_MAX_PASSES: pass 0, at most 64 bisections and 64 Newton steps
 
 
+# include/rsf_joint.h: the joint posterior of the pooled draws; exported by librsf_hip.so only, bound by load()
+JOINT_PROTOTYPES = {
+    "rsf_pool_joint_partials": (c_int, [c_void_p, c_int64, c_int32, _P, POINTER(c_double), POINTER(c_double)]),
+    "rsf_pool_joint_finish": (c_int, [c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+    "rsf_pool_kde2d": (c_int, [c_void_p, c_int64, c_int32, _P, c_int32, c_int32, c_int32, _P, c_double, POINTER(c_double), c_int64, _P]),
+    "rsf_pool_histogram2d": (c_int, [c_void_p, c_int64, c_int32, _P, c_int32, c_int32, c_int32, c_double, c_double, c_int32, c_double,
+                                     c_double, _P]),
+    "rsf_pool_hpd_levels": (c_int, [c_int64, POINTER(c_double), c_int32, POINTER(c_double), POINTER(c_double)]),
+}
+JOINT_HEAD = 2  # RSF_JOINT_HEAD: n_finite, nonfinite; then d sums and d (d + 1) / 2 sums of products (upper triangle, row-major)
+JOINT_MAX_PARAMS = 8  # RSF_JOINT_MAX_PARAMS
+HIST2D_MAX_CELLS = 16384  # RSF_HIST2D_MAX_CELLS: (nbx + 2) (nby + 2)
+JOINT_OUT = ("mean", "cov", "corr")  # rsf_pool_joint_finish's out: d, d * d and d * d doubles (RSF_JOINT_OUT(d) in all)
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -221,7 +236,7 @@ def load():
                                "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
-        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES):
+        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

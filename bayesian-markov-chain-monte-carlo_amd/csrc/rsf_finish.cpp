@@ -1,6 +1,6 @@
 // rsf_finish.cpp — the host arithmetic that turns the device partials into the reported statistics: rsf_diag_finish,
-// rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish.  No ctx, no GPU: plain C++, the public headers and the
-// standard library only.
+// rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish, rsf_pool_joint_finish, rsf_pool_hpd_levels.  No ctx, no GPU:
+// plain C++, the public headers and the standard library only.
 #include <cmath>
 #include <cstdint>
 #include <algorithm>
@@ -8,6 +8,7 @@
 
 #include "../../include/rsf_abi.h"
 #include "../../include/rsf_diag.h"
+#include "../../include/rsf_joint.h"
 #include "../../include/rsf_predict.h"
 #include "../../include/rsf_psis.h"
 
@@ -183,6 +184,49 @@ int rsf_predict_psis_finish(int64_t nout, int64_t n, const double *psis_rows, co
   out_totals[RSF_PSIS_K_THRESHOLD] = thr;
   out_totals[RSF_PSIS_N_HIGH_K] = ok ? high : NAN;
   out_totals[RSF_PSIS_MAX_PARETO_K] = ok ? kmax : NAN;
+  return RSF_OK;
+}
+
+
+int rsf_pool_joint_finish(int32_t d, const double *partials, const double *center, double *out) {
+  if (!partials || !center || !out) return fail(RSF_ERR_INVALID, "rsf_pool_joint_finish: NULL argument");
+  if (d < 1 || d > RSF_JOINT_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_pool_joint_finish: need 1 <= d <= %d", RSF_JOINT_MAX_PARAMS);
+  const double n = partials[0], *s1 = partials + RSF_JOINT_HEAD, *s2 = s1 + d;
+  double *mean = out, *cov = out + d, *corr = cov + d * d, sd[RSF_JOINT_MAX_PARAMS];
+  for (int p = 0; p < d; ++p) mean[p] = center[p] + s1[p] / n;
+  int e = 0;
+  for (int p = 0; p < d; ++p)
+    for (int q = p; q < d; ++q, ++e)
+      cov[p * d + q] = cov[q * d + p] = n >= 2.0 ? (s2[e] - s1[p] * (s1[q] / n)) / (n - 1.0) : NAN;
+  for (int p = 0; p < d; ++p) sd[p] = cov[p * d + p] > 0.0 ? std::sqrt(cov[p * d + p]) : NAN;  // zero variance: NaN row and column
+  for (int p = 0; p < d; ++p)
+    for (int q = 0; q < d; ++q) {
+      const double r = cov[p * d + q] / (sd[p] * sd[q]);
+      corr[p * d + q] = p == q && !std::isnan(r) ? 1.0 : std::fmax(-1.0, std::fmin(1.0, r));  // numpy.corrcoef clips too
+      if (std::isnan(r)) corr[p * d + q] = NAN;  // (fmin and fmax drop a NaN)
+    }
+  return RSF_OK;
+}
+
+int rsf_pool_hpd_levels(int64_t m, const double *weights, int32_t n_probs, const double *probs, double *levels) {
+  if (!weights || !probs || !levels) return fail(RSF_ERR_INVALID, "rsf_pool_hpd_levels: NULL argument");
+  if (m < 1 || n_probs < 1) return fail(RSF_ERR_INVALID, "rsf_pool_hpd_levels: need m >= 1 and n_probs >= 1");
+  for (int k = 0; k < n_probs; ++k)
+    if (!(probs[k] > 0.0 && probs[k] < 1.0)) return fail(RSF_ERR_INVALID, "rsf_pool_hpd_levels: probs[%d] is not strictly inside (0, 1)", k);
+  std::vector<double> w(weights, weights + m);
+  for (int64_t i = 0; i < m; ++i)
+    if (!(w[(size_t)i] >= 0.0) || !std::isfinite(w[(size_t)i]))
+      return fail(RSF_ERR_INVALID, "rsf_pool_hpd_levels: weights[%lld] is negative or not finite", (long long)i);
+  std::sort(w.begin(), w.end(), [](double a, double b) { return a > b; });
+  std::vector<double> cum(w.size());
+  double total = 0.0;
+  for (size_t i = 0; i < w.size(); ++i) cum[i] = total += w[i];  // descending: the mass of {weight >= w[i]} once i is the last of its ties
+  if (!(total > 0.0) || !std::isfinite(total)) return fail(RSF_ERR_INVALID, "rsf_pool_hpd_levels: the weights sum to 0 (or overflow)");
+  for (int k = 0; k < n_probs; ++k) {
+    // the first index whose running mass reaches p total: its value's ties reach it too, and no larger value does
+    const size_t i = (size_t)(std::lower_bound(cum.begin(), cum.end(), probs[k] * total) - cum.begin());
+    levels[k] = w[std::min(i, w.size() - 1)];
+  }
   return RSF_OK;
 }
 

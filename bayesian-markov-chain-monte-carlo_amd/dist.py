@@ -128,6 +128,12 @@ def allreduce_predictive_partials(partials, group=None, device=None):
     return allreduce_diag_partials(partials, group=group, device=device)
 
 
+def allreduce_joint_partials(partials, group=None, device=None):
+    """Per-rank `Engine.pool_joint_partials` (every rank's own shard of the pooled draws, the same centre) → the partials of all
+    ranks' draws: one all-reduce SUM of JOINT_HEAD + d + d (d + 1) / 2 doubles.  Feed the result to `Engine.pool_joint_finish`."""
+    return allreduce_diag_partials(partials, group=group, device=device)
+
+
 def pool_to_chain_major(pool):
     """(G, n_keep, C_local, d) → (n_keep, G*C_local, d): global chain id = g*C_local + c."""
     G, n, C, d = pool.shape

@@ -357,6 +357,104 @@ class Engine:
                                                          self._ptr(counts)))
         return counts
 
+    # -- the joint posterior of the pooled draws (include/rsf_joint.h) ---------------------------
+    def _block(self, samples):
+        """samples: (n,) or a trace block (..., d) in this engine's memory space → (array, n, d)."""
+        x = self._in(samples)
+        d = int(x.shape[-1]) if x.ndim > 1 else 1
+        return x, int(np.prod(x.shape)) // d, d
+
+    @staticmethod
+    def _pair(params, d):
+        pa, pb = (int(p) for p in params)
+        if not (0 <= pa < d and 0 <= pb < d and pa != pb):
+            raise ValueError(f"params = {tuple(params)!r}: two different column indices in [0, {d})")
+        return pa, pb
+
+    def pool_joint_partials(self, samples, center=None):
+        """rsf_pool_joint_partials: the additive partials of the joint moments of all d <= JOINT_MAX_PARAMS columns of the pooled
+        draws (..., d) about `center` (d,) (default: the first row, as pool_summary shifts by the first sample) →
+        (JOINT_HEAD + d + d (d + 1) / 2,) float64 on the host: n_finite, nonfinite (rows with a non-finite entry, left out), the
+        sums and the upper triangle of the sums of products.  Partials of shards about the same centre add
+        (pool_allreduce_sum, dist.allreduce_joint_partials).  With the default centre, pass samples[0] to pool_joint_finish."""
+        x, n, d = self._block(samples)
+        if not 1 <= d <= _abi.JOINT_MAX_PARAMS:
+            raise ValueError(f"the joint moments take 1 to {_abi.JOINT_MAX_PARAMS} columns, not {d}")
+        c = _host(x.reshape(n, d)[0] if center is None else center).reshape(-1)
+        if c.shape != (d,):
+            raise ValueError(f"center has {c.size} entries, the draws have {d} columns")
+        out = np.empty(_abi.JOINT_HEAD + d + d * (d + 1) // 2)
+        _abi.check(self.lib, self.lib.rsf_pool_joint_partials(self._ctx, n, d, self._ptr(x), _dp(c), _dp(out)))
+        return out
+
+    def pool_joint_finish(self, partials, center):
+        """rsf_pool_joint_finish (host only): summed partials and their centre → dict(n, nonfinite, mean (d,), cov (d, d) with
+        ddof = 1 as np.cov, corr (d, d) as np.corrcoef).  Fewer than two finite rows: cov and corr are NaN; a column of zero
+        variance has NaN in its row and column of corr."""
+        part, c = _host(partials).reshape(-1), _host(center).reshape(-1)
+        d = int(c.size)
+        if part.size != _abi.JOINT_HEAD + d + d * (d + 1) // 2:
+            raise ValueError(f"{part.size} partials do not belong to a centre of {d} columns")
+        out = np.empty(d + 2 * d * d)
+        _abi.check(self.lib, self.lib.rsf_pool_joint_finish(d, _dp(part), _dp(c), _dp(out)))
+        return {"n": int(part[0]), "nonfinite": int(part[1]), "mean": out[:d].copy(), "cov": out[d:d + d * d].reshape(d, d).copy(),
+                "corr": out[d + d * d:].reshape(d, d).copy()}
+
+    def pool_joint(self, samples, center=None):
+        """Mean, covariance and correlation matrix of all columns of the pooled draws (..., d) → dict(n, nonfinite, mean (d,),
+        cov (d, d), corr (d, d)); see pool_joint_partials and pool_joint_finish."""
+        x, n, d = self._block(samples)
+        c = _host(x.reshape(n, d)[0] if center is None else center).reshape(-1)
+        return self.pool_joint_finish(self.pool_joint_partials(x, c), c)
+
+    def pool_kde2d(self, samples, points, params=(0, 1), bw_factor=0.0, cov=None, n_total=None):
+        """scipy.stats.gaussian_kde(samples[:, params].T).pdf(points.T) at the m points (m, 2) (Scott bandwidth n^(-1/6) unless
+        bw_factor > 0) → density[m] in this engine's memory space.  cov (2, 2) and n_total evaluate a shard of a larger pool with
+        the pool's covariance and size: the results of disjoint shards then add to the density of the whole pool."""
+        x, n, d = self._block(samples)
+        pa, pb = self._pair(params, d)
+        pts = self._in(points)
+        if pts.ndim != 2 or int(pts.shape[1]) != 2 or int(pts.shape[0]) < 1:
+            raise ValueError("points is (m, 2)")
+        m = int(pts.shape[0])
+        cv = None
+        if cov is not None:
+            cv = _host(cov)
+            if cv.shape != (2, 2):
+                raise ValueError("cov is the (2, 2) covariance of the two columns")
+        dens = self._empty((m,))
+        _abi.check(self.lib, self.lib.rsf_pool_kde2d(self._ctx, n, d, self._ptr(x), pa, pb, m, self._ptr(pts), float(bw_factor),
+                                                     None if cv is None else _dp(cv), int(n_total or 0), self._ptr(dens)))
+        return dens
+
+    def pool_histogram2d(self, samples, nbins, ranges, params=(0, 1)):
+        """numpy.histogram2d(samples[:, pa], samples[:, pb], nbins, ranges) over all pooled draws, plus the out-of-range counts:
+        nbins an int or (nbx, nby), ranges ((lo_a, hi_a), (lo_b, hi_b)) → counts[nbx + 2, nby + 2] (float64 holding exact
+        integers) in this engine's memory space; per axis index 0 is below lo, nb + 1 above hi or NaN, and [1:-1, 1:-1] is
+        numpy's result.  (nbx + 2) (nby + 2) <= HIST2D_MAX_CELLS.  Counts of shards add (pool_allreduce_sum)."""
+        x, n, d = self._block(samples)
+        pa, pb = self._pair(params, d)
+        nbx, nby = (int(nbins), int(nbins)) if np.ndim(nbins) == 0 else (int(b) for b in nbins)
+        (lo_a, hi_a), (lo_b, hi_b) = ranges
+        if nbx < 1 or nby < 1:
+            raise ValueError("at least one bin on each axis")
+        counts = self._empty((nbx + 2, nby + 2))
+        _abi.check(self.lib, self.lib.rsf_pool_histogram2d(self._ctx, n, d, self._ptr(x), pa, pb, nbx, float(lo_a), float(hi_a), nby,
+                                                           float(lo_b), float(hi_b), self._ptr(counts)))
+        return counts
+
+    def pool_hpd_levels(self, weights, probs):
+        """rsf_pool_hpd_levels (host only): the contour levels of a corner plot.  weights >= 0 (histogram counts, or densities on
+        a regular grid; any shape) and probabilities strictly inside (0, 1) → levels[len(probs)]: levels[k] is the largest of
+        the weights w for which the weights >= w hold at least probs[k] of the total."""
+        w = _host(weights).reshape(-1)
+        p = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if p.ndim != 1 or p.size < 1 or w.size < 1:
+            raise ValueError("weights and probs are non-empty")
+        out = np.empty(p.size)
+        _abi.check(self.lib, self.lib.rsf_pool_hpd_levels(int(w.size), _dp(w), int(p.size), _dp(p), _dp(out)))
+        return out
+
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
         x = self._in(trace)
