@@ -193,6 +193,25 @@ HIST2D_MAX_CELLS = 16384  # RSF_HIST2D_MAX_CELLS: (nbx + 2) (nby + 2)
 JOINT_OUT = ("mean", "cov", "corr")  # rsf_pool_joint_finish's out: d, d * d and d * d doubles (RSF_JOINT_OUT(d) in all)
 
 
+# include/rsf_evidence.h: the marginal likelihood of the pooled draws by bridge sampling; exported by librsf_hip.so only, bound by load()
+EVIDENCE_PROTOTYPES = {
+    "rsf_evidence_propose": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double),
+                                     POINTER(c_double), c_uint64, c_int64, _P, _P, _P]),
+    "rsf_evidence_logg": (c_int, [c_void_p, c_int64, c_int32, _P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), _P]),
+    "rsf_evidence_logtarget": (c_int, [c_void_p, c_int64, c_int32, _P, _P, c_double, POINTER(c_double), POINTER(c_double), POINTER(c_int32),
+                                       _P, _P]),
+    "rsf_evidence_partials": (c_int, [c_void_p, c_int64, _P, c_int64, _P, c_double, c_double, c_double, c_double, POINTER(c_double)]),
+    "rsf_evidence_finish": (c_int, [POINTER(c_double), c_double, c_double, c_double, c_double, c_int32, POINTER(c_double), POINTER(c_double),
+                                    POINTER(c_double)]),
+}
+EVIDENCE_MAX_PARAMS = 3  # RSF_EVIDENCE_MAX_PARAMS
+# rsf_evidence_partials' partials and rsf_evidence_finish's out, in index order
+EVIDENCE_PARTIALS = ("n1", "n2", "n2_finite", "sum_num", "sum_den", "sum_f1", "sum_f1_sq", "sum_f2", "sum_f2_sq")
+EVIDENCE_OUT = ("r_next", "log_integral", "log_evidence", "re")
+EVIDENCE_MAX_ITER = 1000  # Engine.evidence_bridge: iterations at most
+EVIDENCE_RTOL = 1e-10     # ... and the relative change of r below which it has converged
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -236,7 +255,7 @@ def load():
                                "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
-        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES):
+        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -1,5 +1,5 @@
 // rsf_finish.cpp — the host arithmetic that turns the device partials into the reported statistics: rsf_diag_finish,
-// rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish, rsf_pool_joint_finish, rsf_pool_hpd_levels.  No ctx, no GPU:
+// rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish, rsf_pool_joint_finish, rsf_pool_hpd_levels, rsf_evidence_finish.  No ctx, no GPU:
 // plain C++, the public headers and the standard library only.
 #include <cmath>
 #include <cstdint>
@@ -8,6 +8,7 @@
 
 #include "../../include/rsf_abi.h"
 #include "../../include/rsf_diag.h"
+#include "../../include/rsf_evidence.h"
 #include "../../include/rsf_joint.h"
 #include "../../include/rsf_predict.h"
 #include "../../include/rsf_psis.h"
@@ -226,6 +227,35 @@ int rsf_pool_hpd_levels(int64_t m, const double *weights, int32_t n_probs, const
     // the first index whose running mass reaches p total: its value's ties reach it too, and no larger value does
     const size_t i = (size_t)(std::lower_bound(cum.begin(), cum.end(), probs[k] * total) - cum.begin());
     levels[k] = w[std::min(i, w.size() - 1)];
+  }
+  return RSF_OK;
+}
+
+int rsf_evidence_finish(const double *partials, double r, double lstar, double ess_factor, double shape, int32_t d, const double *lo,
+                        const double *hi, double *out) {
+  if (!partials || !out || (d > 0 && (!lo || !hi))) return fail(RSF_ERR_INVALID, "rsf_evidence_finish: NULL argument");
+  const double n1 = partials[0], n2 = partials[1], n2f = partials[2];
+  if (!(n1 >= 1.0) || !(n2 >= 1.0)) return fail(RSF_ERR_INVALID, "rsf_evidence_finish: need n1 >= 1 and n2 >= 1 draws in the summed partials");
+  if (!std::isfinite(lstar) || !std::isfinite(r) || !(r > 0.0)) return fail(RSF_ERR_INVALID, "rsf_evidence_finish: need finite lstar and finite r > 0");
+  if (!(ess_factor > 0.0 && ess_factor <= 1.0)) return fail(RSF_ERR_INVALID, "rsf_evidence_finish: ess_factor outside (0, 1]");
+  if (!std::isfinite(shape) || !(shape > 0.0)) return fail(RSF_ERR_INVALID, "rsf_evidence_finish: shape must be finite and > 0");
+  if (d < 0 || d > RSF_EVIDENCE_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_evidence_finish: d outside 0..%d", RSF_EVIDENCE_MAX_PARAMS);
+  double logvol = 0.0;
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "rsf_evidence_finish: need finite lo[%d] < hi[%d]", p, p);
+    logvol += std::log(hi[p] - lo[p]);
+  }
+  const double rn = n2f > 0.0 ? (partials[3] / n2) / (partials[4] / n1) : 0.0;
+  out[0] = rn;
+  out[1] = rn > 0.0 ? std::log(rn) + lstar : -INFINITY;
+  out[2] = out[1] - logvol + std::lgamma(shape) - shape * std::log(3.14159265358979323846);
+  if (n1 < 2.0 || n2 < 2.0 || !(n2f > 0.0)) {
+    out[3] = INFINITY;  // no error estimate
+  } else {
+    const double e1 = partials[5] / n2, v1 = (partials[6] - partials[5] * e1) / (n2 - 1.0);
+    const double e2 = partials[7] / n1, v2 = (partials[8] - partials[7] * e2) / (n1 - 1.0);
+    const double re2 = std::fmax(v1, 0.0) / (n2 * e1 * e1) + std::fmax(v2, 0.0) / (ess_factor * n1 * e2 * e2);
+    out[3] = std::sqrt(re2);
   }
   return RSF_OK;
 }

@@ -66,6 +66,9 @@ enum Slot : int {
   // rsf_predict_partials (std2 in SLOT_U), rsf_predict_quantiles (the series in SLOT_X)
   // rsf_predict_psis_loo: the series in SLOT_SERIES, std2 in SLOT_STD2, the observation in SLOT_OBS
   SLOT_STD2 = SLOT_U, SLOT_OBS = SLOT_G, SLOT_SERIES = SLOT_TQ,
+  // rsf_evidence_propose (theta, logg, inbox out), rsf_evidence_logg (theta in, logg out), rsf_evidence_logtarget (theta, the
+  // observation and logg in, l out), rsf_evidence_partials (l1 in SLOT_EV_L, l2 in SLOT_EV_L2)
+  SLOT_EV_THETA = SLOT_Z, SLOT_EV_LOGG = SLOT_U, SLOT_EV_OBS = SLOT_G, SLOT_EV_L = SLOT_TQ, SLOT_EV_L2 = SLOT_TS, SLOT_EV_INBOX = SLOT_TA,
   // rsf_pool_allgather[_all] / _allreduce_sum[_all] (the reduction is in place in SLOT_SEND)
   SLOT_SEND = SLOT_Z, SLOT_RECV = SLOT_U,
 };

@@ -134,6 +134,13 @@ def allreduce_joint_partials(partials, group=None, device=None):
     return allreduce_diag_partials(partials, group=group, device=device)
 
 
+def allreduce_evidence_partials(partials, group=None, device=None):
+    """Per-rank `Engine.evidence_partials` (every rank's own shard of l1 and l2, with the POOL's s1, s2 and the same lstar and r) →
+    the partials of all ranks' draws: one all-reduce SUM of len(EVIDENCE_PARTIALS) doubles.  Feed the result to
+    `Engine.evidence_finish`."""
+    return allreduce_diag_partials(partials, group=group, device=device)
+
+
 def pool_to_chain_major(pool):
     """(G, n_keep, C_local, d) → (n_keep, G*C_local, d): global chain id = g*C_local + c."""
     G, n, C, d = pool.shape

@@ -90,6 +90,19 @@ def _model_struct(model, substeps):
     return m
 
 
+def bayes_factor(ev_a, ev_b):
+    """The log Bayes factor of two results of Engine.evidence / evidence_from_ssq / PosteriorPool.evidence, model a against model
+    b, for the SAME observation → dict(log_bf = log_evidence_a - log_evidence_b, re = sqrt(re_a^2 + re_b^2), the approximate
+    relative error of the ratio of the two marginal likelihoods, i.e. the absolute error of log_bf).  Two results whose `shape`
+    or data length `n_data` differ do not belong to one data set and are refused."""
+    for key in ("shape", "n_data"):
+        if ev_a[key] != ev_b[key]:
+            raise ValueError(f"the two results differ in {key} ({ev_a[key]!r} against {ev_b[key]!r}): not the same observation")
+    if ev_a["log_evidence"] is None or ev_b["log_evidence"] is None:
+        raise ValueError("a result without log_evidence (no box given)")
+    return {"log_bf": float(ev_a["log_evidence"] - ev_b["log_evidence"]), "re": float(np.hypot(ev_a["re"], ev_b["re"]))}
+
+
 class Engine:
     def __init__(self, lib=None, mem="host", device=-1, block_threads=0, cpu_threads=0, stream=None, checker=False):
         if lib is None:
@@ -454,6 +467,222 @@ class Engine:
         out = np.empty(p.size)
         _abi.check(self.lib, self.lib.rsf_pool_hpd_levels(int(w.size), _dp(w), int(p.size), _dp(p), _dp(out)))
         return out
+
+    # -- the marginal likelihood of the pooled draws by bridge sampling (include/rsf_evidence.h) -----------
+    @staticmethod
+    def _ev_flags(transform, d):
+        """transform: None (identity), or per parameter a truthy value / "log" for phi_p = log q_p → int32 (d,)."""
+        if transform is None:
+            return np.zeros(d, dtype=np.int32)
+        if isinstance(transform, np.ndarray) and transform.dtype == np.int32 and transform.shape == (d,):
+            return transform
+        t = [1 if (x == "log" or x is True or x == 1) else 0 if (x in ("identity", None) or x is False or x == 0) else -1
+             for x in (transform if np.ndim(transform) else [transform] * d)]
+        if len(t) != d or -1 in t:
+            raise ValueError(f"transform is None or {d} entries of 'identity' / 'log' (0 / 1)")
+        return np.asarray(t, dtype=np.int32)
+
+    @staticmethod
+    def _ev_gauss(mean, chol):
+        m = _host(mean).reshape(-1)
+        d = int(m.size)
+        L = _host(chol).reshape(-1)
+        if not 1 <= d <= _abi.EVIDENCE_MAX_PARAMS or L.size != d * d:
+            raise ValueError(f"mean is (d,) and chol (d, d) with 1 <= d <= {_abi.EVIDENCE_MAX_PARAMS}")
+        return m, L, d
+
+    @staticmethod
+    def _ev_box(lo, hi, d):
+        return (np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (d,))),
+                np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (d,))))
+
+    def evidence_propose(self, mean, chol, lo, hi, n2, transform=None, seed=0, offset=0):
+        """rsf_evidence_propose: n2 draws of the Gaussian proposal N(mean, chol chol^T) in the working coordinates (phi_p = q_p, or
+        log q_p where transform[p] is "log") → (theta (n2, d) in natural coordinates, logg (n2,), inbox (n2,) uint8) in this
+        engine's memory space.  Draw j uses the normals of draws(seed, offset + j, 0, d): shards with offsets form one stream."""
+        m, L, d = self._ev_gauss(mean, chol)
+        tr = self._ev_flags(transform, d)
+        lo, hi = self._ev_box(lo, hi, d)
+        n2 = int(n2)
+        theta, logg, inbox = self._empty((max(n2, 0), d)), self._empty((max(n2, 0),)), self._empty((max(n2, 0),), np.uint8)
+        _abi.check(self.lib, self.lib.rsf_evidence_propose(self._ctx, n2, d, _dp(m), _dp(L), tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                           _dp(lo), _dp(hi), int(seed), int(offset), self._ptr(theta), self._ptr(logg),
+                                                           self._ptr(inbox)))
+        return theta, logg, inbox
+
+    def evidence_logg(self, theta, mean, chol, transform=None):
+        """rsf_evidence_logg: log g at the points theta (n, d) (natural coordinates) → (n,) in this engine's memory space."""
+        m, L, d = self._ev_gauss(mean, chol)
+        tr = self._ev_flags(transform, d)
+        x = self._in(theta)
+        n = int(np.prod(x.shape)) // d
+        if int(np.prod(x.shape)) != n * d:
+            raise ValueError(f"theta is (n, {d})")
+        logg = self._empty((n,))
+        _abi.check(self.lib, self.lib.rsf_evidence_logg(self._ctx, n, d, self._ptr(x), _dp(m), _dp(L),
+                                                        tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._ptr(logg)))
+        return logg
+
+    def evidence_logtarget(self, theta, data, lo, hi, logg, shape=None, transform=None):
+        """rsf_evidence_logtarget, the fused hot path: one float64 RK4 solve per point theta (n,) or (n, d), d = 1 or 3, and
+        l = -shape log SSq + sum of log theta_p over the logged parameters - logg → (n,) in this engine's memory space; -inf
+        outside the strict box (lo, hi) and where SSq is not finite.  shape defaults to nout / 2, the sampler's at n0 = 0."""
+        self._need_model()
+        x, g, obs = self._in(theta), self._in(logg), self._in(data)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        n, d = int(x.shape[0]), int(x.shape[1])
+        if int(np.prod(g.shape)) != n:
+            raise ValueError(f"logg holds {int(np.prod(g.shape))} values, theta {n} points")
+        if obs.ndim != 1 or int(obs.shape[0]) != self.nout:
+            raise ValueError(f"data has shape {tuple(obs.shape)}, the model produces {self.nout} samples")
+        tr = self._ev_flags(transform, d)
+        lo, hi = self._ev_box(lo, hi, d)
+        l = self._empty((n,))
+        _abi.check(self.lib, self.lib.rsf_evidence_logtarget(self._ctx, n, d, self._ptr(x), self._ptr(obs),
+                                                             float(0.5 * self.nout if shape is None else shape), _dp(lo), _dp(hi),
+                                                             tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._ptr(g), self._ptr(l)))
+        return l
+
+    def evidence_partials(self, l1, l2, lstar, r, s1=None, s2=None):
+        """rsf_evidence_partials: the additive partials of one bridge iteration at (r, lstar) over the posterior draws' l1 and the
+        proposal draws' l2 (either may be empty) → (len(EVIDENCE_PARTIALS),) float64 on the host.  s1, s2 default to
+        N1 / (N1 + N2) and N2 / (N1 + N2) of these arrays; a shard of a larger pool passes the pool's, and the partials of
+        disjoint shards add (pool_allreduce_sum, dist.allreduce_evidence_partials)."""
+        a, b = self._in(l1), self._in(l2)
+        n1, n2 = int(np.prod(a.shape)), int(np.prod(b.shape))
+        if s1 is None or s2 is None:
+            if n1 + n2 == 0:
+                raise ValueError("both sets are empty")
+            s1, s2 = n1 / (n1 + n2), n2 / (n1 + n2)
+        out = np.empty(len(_abi.EVIDENCE_PARTIALS))
+        _abi.check(self.lib, self.lib.rsf_evidence_partials(self._ctx, n1, self._ptr(a) if n1 else None, n2, self._ptr(b) if n2 else None,
+                                                            float(lstar), float(r), float(s1), float(s2), _dp(out)))
+        return out
+
+    def evidence_finish(self, partials, r, lstar, ess_factor=1.0, shape=None, lo=None, hi=None):
+        """rsf_evidence_finish (host only): summed partials taken at (r, lstar) → dict(r_next, log_integral, log_evidence, re).
+        Without shape, lo and hi the constants of log_evidence are unknown and it is None."""
+        part = _host(partials).reshape(-1)
+        if part.size != len(_abi.EVIDENCE_PARTIALS):
+            raise ValueError(f"{part.size} partials, not {len(_abi.EVIDENCE_PARTIALS)}")
+        full = shape is not None and lo is not None and hi is not None
+        d = int(np.size(lo)) if full else 0
+        lo, hi = self._ev_box(lo, hi, d) if full else (None, None)
+        out = np.empty(len(_abi.EVIDENCE_OUT))
+        _abi.check(self.lib, self.lib.rsf_evidence_finish(_dp(part), float(r), float(lstar), float(ess_factor), float(shape) if full else 1.0,
+                                                          d, _dp(lo) if full else None, _dp(hi) if full else None, _dp(out)))
+        res = dict(zip(_abi.EVIDENCE_OUT, (float(v) for v in out)))
+        if not full:
+            res["log_evidence"] = None
+        return res
+
+    def evidence_bridge(self, l1, l2, ess_factor=1.0, lstar=None, shape=None, lo=None, hi=None, return_state=False):
+        """The bridge iteration on l = log target - log proposal of the N1 posterior draws (l1) and the N2 proposal draws (l2, -inf
+        for a draw outside the support), from r = 1: until |r_next - r| / r_next < EVIDENCE_RTOL, EVIDENCE_MAX_ITER iterations at
+        most → dict(log_integral = log r + lstar, log_evidence (None without shape, lo, hi), re, iterations, n2_in_box (the
+        finite l2), converged).  lstar defaults to the median of l1.  No proposal draw inside the support: r = 0, log_integral
+        -inf, re +inf, converged False."""
+        a, b = self._in(l1), self._in(l2)
+        if lstar is None:
+            lstar = float(np.median(_host(a)))
+        r, it, conv = 1.0, 0, False
+        while it < _abi.EVIDENCE_MAX_ITER:
+            part = self.evidence_partials(a, b, lstar, r)
+            res = self.evidence_finish(part, r, lstar, ess_factor, shape, lo, hi)
+            it += 1
+            rn = res["r_next"]
+            if not rn > 0.0:
+                r = 0.0
+                break
+            conv = abs(rn - r) < _abi.EVIDENCE_RTOL * rn
+            r = rn
+            if conv:
+                break
+        out = {"log_integral": res["log_integral"], "log_evidence": res["log_evidence"], "re": res["re"], "iterations": it,
+               "n2_in_box": int(part[2]), "converged": bool(conv)}
+        if return_state:
+            out.update(r=r, lstar=lstar, partials=part)
+        return out
+
+    def _evidence(self, samples, ltarget, lo, hi, shape, n_data, transform, n_proposal, fit_fraction, seed, ess_factor):
+        """What evidence and evidence_from_ssq share.  ltarget(theta (n, d), logg (n,)) → l (n,)."""
+        x = self._in(samples)
+        trace = x.ndim == 3
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        d = int(x.shape[-1])
+        rows = int(x.shape[0])  # iterations of a kept trace (n, C, d), draws of a flat pool (n, d)
+        k = int(round(float(fit_fraction) * rows))
+        if not 0.0 < float(fit_fraction) < 1.0 or k < d + 1 or rows - k < 1:
+            raise ValueError(f"fit_fraction = {fit_fraction!r} leaves {k} rows to fit the proposal and {rows - k} for the estimator")
+        tr = self._ev_flags(transform, d)
+        lo, hi = self._ev_box(lo, hi, d)
+        fit, est = x[:k].reshape(-1, d), x[k:].reshape(-1, d)
+        n1 = int(est.shape[0])
+        # the proposal's moments: pool_joint of the first part in the working coordinates
+        phi = fit.clone() if hasattr(fit, "clone") else fit.copy()
+        for p in np.flatnonzero(tr):
+            phi[:, p] = phi[:, p].log() if hasattr(phi, "log") else np.log(phi[:, p])
+        mom = self.pool_joint(phi)
+        if mom["nonfinite"] or not np.isfinite(mom["cov"]).all():
+            raise ValueError("the first part of the draws is not finite in the working coordinates (a logged parameter <= 0?)")
+        mean, chol = mom["mean"], np.linalg.cholesky(mom["cov"])
+        n2 = n1 if n_proposal is None else int(n_proposal)
+        theta, logg2, _ = self.evidence_propose(mean, chol, lo, hi, n2, tr, seed=seed)
+        l2 = ltarget(theta, logg2)
+        l1 = ltarget(est, self.evidence_logg(est, mean, chol, tr))
+        res = self.evidence_bridge(l1, l2, 1.0 if ess_factor is None else float(ess_factor), None, shape, lo, hi, return_state=True)
+        r, lstar, part = res.pop("r"), res.pop("lstar"), res.pop("partials")
+        if ess_factor is None and trace and r > 0.0:
+            # the effective number of posterior draws, from the existing diagnostics' ESS of the series f2 = 1 / (s1 p + s2)
+            s1, s2 = n1 / (n1 + n2), n2 / (n1 + n2)
+            f2 = 1.0 / (s1 * np.exp(np.minimum(_host(l1) - (np.log(r) + lstar), 700.0)) + s2)
+            f2 = f2.reshape(rows - k, -1)
+            ess = self.diagnostics(f2)[0]["ess"] if f2.shape[0] >= 4 and f2.std() > 0 else float(n1)
+            ess_factor = float(min(1.0, ess / n1)) if np.isfinite(ess) and ess > 0 else 1.0
+            res["re"] = self.evidence_finish(part, r, lstar, ess_factor, shape, lo, hi)["re"]
+        res.update(shape=float(shape), n_data=int(n_data), n1=n1, n2=n2, d=d, ess_factor=1.0 if ess_factor is None else float(ess_factor),
+                   transform=tuple(int(t) for t in tr), lstar=lstar, mean=mean, chol=chol)
+        return res
+
+    def evidence(self, samples, data, lo, hi, shape=None, transform=None, n_proposal=None, fit_fraction=0.5, seed=0, ess_factor=None):
+        """The marginal likelihood of the device model (set_model) for the observation `data` from posterior draws `samples` — a
+        kept trace (n, C, d) or a flat pool (n, d) / (n,), d = 1 (Dc) or 3 (Dc, a, b), sampled with n0 = 0 inside the box (lo, hi)
+        — by bridge sampling: the first fit_fraction of the rows fit a Gaussian proposal (pool_joint, in the coordinates of
+        `transform`), the rest enter the estimator with n_proposal (default: as many) proposal draws; one more forward solve
+        per draw (evidence_logtarget).  → dict(log_integral, log_evidence, re, iterations, n2_in_box, converged, shape, n_data,
+        n1, n2, d, ess_factor, transform, lstar, mean, chol).  ess_factor (effective over actual number of posterior draws): by
+        default, for a kept trace, from diagnostics' ESS of the series f2; for a flat pool 1."""
+        self._need_model()
+        shape = 0.5 * self.nout if shape is None else float(shape)
+        obs = self._in(data)
+        return self._evidence(samples, lambda theta, logg: self.evidence_logtarget(theta, obs, lo, hi, logg, shape, transform), lo, hi,
+                              shape, self.nout, transform, n_proposal, fit_fraction, seed, ess_factor)
+
+    def evidence_from_ssq(self, samples, ssq_fn, lo, hi, shape, transform=None, n_proposal=None, fit_fraction=0.5, seed=0, ess_factor=None,
+                          n_data=None):
+        """evidence with the caller's sum of squares: ssq_fn(q (m, d) float64 on the host) → SSq (m,), called for points strictly
+        inside the box only — any object under the project's model contract, or a closed form.  shape is the sampler's
+        (n_data / 2 at n0 = 0; n_data defaults to 2 shape).  The proposal, its density and the bridge run on the GPU."""
+        shape = float(shape)
+        d = int(np.shape(samples)[-1]) if np.ndim(samples) > 1 else 1
+        tr = self._ev_flags(transform, d)
+        blo, bhi = self._ev_box(lo, hi, d)
+
+        def ltarget(theta, logg):
+            q, g = _host(theta).reshape(-1, d), _host(logg).reshape(-1)
+            inb = np.all((q > blo) & (q < bhi), axis=1)
+            l = np.full(q.shape[0], -np.inf)
+            if inb.any():
+                ssq = np.asarray(ssq_fn(q[inb]), dtype=np.float64).reshape(-1)
+                ok = np.isfinite(ssq) & (ssq > 0)
+                jac = np.log(q[inb][:, tr == 1]).sum(axis=1)
+                l[inb] = np.where(ok, -shape * np.log(np.where(ok, ssq, 1.0)) + jac - g[inb], -np.inf)
+            return l
+
+        return self._evidence(samples, ltarget, lo, hi, shape, int(round(2 * shape)) if n_data is None else n_data, transform, n_proposal,
+                              fit_fraction, seed, ess_factor)
 
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
