@@ -976,11 +976,4 @@ __device__ __forceinline__ double np_cov_1d(F a, int n) {
   return c * (1.0 / (double)(n - 1));
 }
 
-// wave64 sum via DPP-free shuffles; result valid in lane 0
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 }  // namespace rsf

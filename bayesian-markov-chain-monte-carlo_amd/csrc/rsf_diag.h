@@ -13,10 +13,13 @@
 //                       draws and a window of 2*kLagTile lagged draws, all indexed by constants of unrolled loops (ScratchSize
 //                       0).  A tile re-reads the trace twice; the tiles and parameters of one chain block are dispatched next
 //                       to each other so that they stream the same rows through L2 together.
-//   diag_sum_kernel     fixed-order sum of the per-workgroup partials: every reduction is deterministic, no float atomics.
+// The per-workgroup partials of all three are summed in index order by rsfh::sum_in_order (rsf_host.h): every reduction is
+// deterministic, no float atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "rsf_kernel_common.h"
 
 namespace rsfk {
 
@@ -41,8 +44,7 @@ struct DiagShape {
 
 // fixed-order workgroup sum of one double per thread; every thread gets the total (blockDim.x = kDiagBlock)
 __device__ __forceinline__ double diag_block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -138,16 +140,14 @@ diag_super_kernel(int64_t C, int d, int64_t S, DiagCenter center, const double *
       const int64_t c0 = k * S;
       double sm = 0.0, sv = 0.0;
       for (int64_t j = lane; j < S; j += 64) { sm += m[c0 + j] - cp; sv += v[c0 + j]; }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) { sm += __shfl_xor(sm, off, 64); sv += __shfl_xor(sv, off, 64); }
+      sm = wave_all_descending(sm); sv = wave_all_descending(sv);
       const double yk = sm * rS;  // xbar_k - c, identical in every lane (butterfly)
       double sb = 0.0, eb = 0.0;
       for (int64_t j = lane; j < S; j += 64) {
         const double r = (m[c0 + j] - cp) - yk;
         eb += r; sb = __builtin_fma(r, r, sb);
       }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) { sb += __shfl_xor(sb, off, 64); eb += __shfl_xor(eb, off, 64); }
+      sb = wave_all_descending(sb); eb = wave_all_descending(eb);
       const double bt = S > 1 ? (sb - eb * eb * rS) / (double)(S - 1) : 0.0;
       acc[0] += yk; acc[1] += yk * yk; acc[2] += bt; acc[3] += sv * rS;
     }
@@ -155,11 +155,7 @@ diag_super_kernel(int64_t C, int d, int64_t S, DiagCenter center, const double *
     if (lane == 0)
       for (int f = 0; f < kDiagSuperFields; ++f) sh[wave][f] = acc[f];
     __syncthreads();
-    if (threadIdx.x < kDiagSuperFields) {
-      double t = sh[0][threadIdx.x];
-      for (unsigned w = 1; w < blockDim.x / 64; ++w) t += sh[w][threadIdx.x];
-      part[((int64_t)blockIdx.x * d + p) * kDiagSuperFields + threadIdx.x] = t;
-    }
+    block_fields_store(sh, kDiagSuperFields, part, ((int64_t)blockIdx.x * d + p) * kDiagSuperFields);
   }
 }
 
@@ -217,15 +213,6 @@ diag_lag_kernel(DiagShape s, const double *__restrict__ x, const double *__restr
     const double t = diag_block_sum(acc[j] * rN, sh);  // acov_m(t) = (1/N) sum_i y_i y_(i+t), summed over the block's chains
     if (threadIdx.x == 0 && t0 + j < lag_end) part[(cblock * s.d + p) * L + (t0 - lag0) + j] = t;
   }
-}
-
-// out[f] = sum over b of part[b][f], b in order: the last, fixed-order step of every reduction above
-__global__ void __launch_bounds__(kDiagBlock) diag_sum_kernel(int64_t nblocks, int64_t nf, const double *__restrict__ part, double *__restrict__ out) {
-  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= nf) return;
-  double t = 0.0;
-  for (int64_t b = 0; b < nblocks; ++b) t += part[b * nf + f];
-  out[f] = t;
 }
 
 }  // namespace rsfk

@@ -52,17 +52,13 @@ int diag_partials_dev(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const double 
   double *w = (double *)c->diag.p;
   const rsfk::DiagShape sh{n, C, d, N, n - N};
   if ((rc = launch(c, diag_chain_fn(d), (unsigned)nbc, kDiagBlock, 0, sh, x, cen, w, w + o_fm, w + o_fv, w + o_p1))) return rc;
-  if (S) hipLaunchKernelGGL(diag_super_kernel, dim3((unsigned)nbs), dim3(kDiagBlock), 0, c->stream, C, (int)d, S, cen, (const double *)(w + o_fm),
-                            (const double *)(w + o_fv), w + o_p2);
-  hipLaunchKernelGGL(diag_lag_kernel, dim3((unsigned)(nbc * d * lg.ntiles)), dim3(kDiagBlock), 0, c->stream, sh, x, (const double *)w,
-                     lg.lag_begin, lg.lag_end, w + o_p3);
-  const int64_t sum_blocks = (std::max<int64_t>(nf1, std::max(nf2, nf3)) + kDiagBlock - 1) / kDiagBlock;
-  hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbc, nf1, (const double *)(w + o_p1), w + o_sum);
-  if (S) hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbs, nf2, (const double *)(w + o_p2),
-                            w + o_sum + nf1);
-  hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)sum_blocks), dim3(kDiagBlock), 0, c->stream, nbc, nf3, (const double *)(w + o_p3),
-                     w + o_sum + nf1 + nf2);
-  HIP_TRY(hipGetLastError());
+  if (S && (rc = launch(c, diag_super_kernel, (unsigned)nbs, kDiagBlock, 0, C, d, S, cen, w + o_fm, w + o_fv, w + o_p2))) return rc;
+  if ((rc = launch(c, diag_lag_kernel, (unsigned)(nbc * d * lg.ntiles), kDiagBlock, 0, sh, x, w, lg.lag_begin, lg.lag_end, w + o_p3))) return rc;
+  // the three sums share the grid that covers the longest of them
+  const unsigned sum_blocks = (unsigned)((std::max<int64_t>(nf1, std::max(nf2, nf3)) + kDiagBlock - 1) / kDiagBlock);
+  if ((rc = sum_in_order(c, nbc, nbc, nf1, w + o_p1, 1.0, w + o_sum, sum_blocks))) return rc;
+  if (S && (rc = sum_in_order(c, nbs, nbs, nf2, w + o_p2, 1.0, w + o_sum + nf1, sum_blocks))) return rc;
+  if ((rc = sum_in_order(c, nbc, nbc, nf3, w + o_p3, 1.0, w + o_sum + nf1 + nf2, sum_blocks))) return rc;
   std::vector<double> h((size_t)(nf1 + nf2 + nf3), 0.0);
   HIP_TRY(hipMemcpyAsync(h.data(), w + o_sum, sizeof(double) * (size_t)(nf1 + (S ? nf2 : 0)), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(h.data() + nf1 + nf2, w + o_sum + nf1 + nf2, sizeof(double) * (size_t)nf3, hipMemcpyDeviceToHost, c->stream));
@@ -142,10 +138,9 @@ size_t rank_ws_layout(int64_t A, int d, int np, char *base, RankWs *w) {
 int rank_sort(rsf_ctx *c, RankWs &w, int64_t A, int d, int p, const double *x, bool folded, const double *st, int *cur, bool *bad) {
   const int64_t ntiles = (A + kRankTile - 1) / kRankTile;
   const int nkb = (int)std::min<int64_t>(kRankKeyBlocks, ntiles);
-  hipLaunchKernelGGL(rank_key_kernel, dim3((unsigned)nkb), dim3(kRankThreads), 0, c->stream, A, d, p, x, folded, st, w.keys[0], w.idx[0], w.hpart);
-  hipLaunchKernelGGL(rank_hist_kernel, dim3((kRankHist + kRankThreads - 1) / kRankThreads), dim3(kRankThreads), 0, c->stream, nkb,
-                     (const uint32_t *)w.hpart, w.hist);
-  HIP_TRY(hipGetLastError());
+  int rc;
+  if ((rc = launch(c, rank_key_kernel, nkb, kRankThreads, 0, A, d, p, x, folded, st, w.keys[0], w.idx[0], w.hpart))) return rc;
+  if ((rc = launch(c, rank_hist_kernel, (kRankHist + kRankThreads - 1) / kRankThreads, kRankThreads, 0, nkb, w.hpart, w.hist))) return rc;
   std::vector<uint32_t> h(kRankHist);
   HIP_TRY(hipMemcpyAsync(h.data(), w.hist, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -157,14 +152,11 @@ int rank_sort(rsf_ctx *c, RankWs &w, int64_t A, int d, int p, const double *x, b
     for (int b = 0; b < 256; ++b) one = one || (int64_t)h[g * 256 + b] == A;
     if (one) continue;
     const int s = *cur;
-    hipLaunchKernelGGL(rank_upsweep_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, A, 8 * g, (const uint64_t *)w.keys[s],
-                       w.th, ntiles);
-    hipLaunchKernelGGL(rank_offsets_kernel, dim3(256), dim3(kRankThreads), 0, c->stream, (const uint32_t *)(w.hist + g * 256), w.th, ntiles);
-    hipLaunchKernelGGL(rank_scatter_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, A, 8 * g, (const uint64_t *)w.keys[s],
-                       (const uint32_t *)w.idx[s], w.keys[1 - s], w.idx[1 - s], (const uint32_t *)w.th, ntiles);
+    if ((rc = launch(c, rank_upsweep_kernel, (unsigned)ntiles, kRankThreads, 0, A, 8 * g, w.keys[s], w.th, ntiles))) return rc;
+    if ((rc = launch(c, rank_offsets_kernel, 256, kRankThreads, 0, w.hist + g * 256, w.th, ntiles))) return rc;
+    if ((rc = launch(c, rank_scatter_kernel, (unsigned)ntiles, kRankThreads, 0, A, 8 * g, w.keys[s], w.idx[s], w.keys[1 - s], w.idx[1 - s], w.th, ntiles))) return rc;
     *cur = 1 - s;
   }
-  HIP_TRY(hipGetLastError());
   return RSF_OK;
 }
 
@@ -174,13 +166,11 @@ int rank_scores(rsf_ctx *c, RankWs &w, const RankShape &rs, int s, double *out) 
   const uint64_t *k = w.keys[s];
   const uint32_t *ix = w.idx[s];
   uint32_t *P = w.idx[1 - s];
-  hipLaunchKernelGGL(rank_tile_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, rs, k, ix, w.tm, w.tlast, w.tfirst);
-  hipLaunchKernelGGL(rank_carry_kernel, dim3(1), dim3(kRankThreads), 0, c->stream, ntiles, (uint32_t)rs.A, w.tm, w.tlast, w.tfirst);
-  hipLaunchKernelGGL(rank_prefix_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, rs, k, ix, (const uint32_t *)w.tm, P);
-  hipLaunchKernelGGL(rank_z_kernel, dim3((unsigned)ntiles), dim3(kRankThreads), 0, c->stream, rs, k, ix, (const uint32_t *)w.tlast,
-                     (const uint32_t *)w.tfirst, (const uint32_t *)P, out);
-  HIP_TRY(hipGetLastError());
-  return RSF_OK;
+  int rc;
+  if ((rc = launch(c, rank_tile_kernel, (unsigned)ntiles, kRankThreads, 0, rs, k, ix, w.tm, w.tlast, w.tfirst))) return rc;
+  if ((rc = launch(c, rank_carry_kernel, 1, kRankThreads, 0, ntiles, rs.A, w.tm, w.tlast, w.tfirst))) return rc;
+  if ((rc = launch(c, rank_prefix_kernel, (unsigned)ntiles, kRankThreads, 0, rs, k, ix, w.tm, P))) return rc;
+  return launch(c, rank_z_kernel, (unsigned)ntiles, kRankThreads, 0, rs, k, ix, w.tlast, w.tfirst, P, out);
 }
 
 int rank_grid(int64_t work, int64_t cap) { return (int)std::max<int64_t>(1, std::min<int64_t>(cap, (work + kRankThreads - 1) / kRankThreads)); }
@@ -223,27 +213,23 @@ int rsf_diag_rank_prepare(rsf_ctx *c, int64_t n, int64_t C, int32_t d, const dou
     if ((rc = rank_sort(c, w, A, d, p, x, false, st, &cur, &nonfinite))) return rc;
     if (nonfinite) {  // every output of this parameter is NaN
       bad[(size_t)p] = 1;
-      hipLaunchKernelGGL(rank_fill_kernel, dim3((unsigned)rank_grid(A, 4096)), dim3(kRankThreads), 0, c->stream, rs, w.series, stride, (double)NAN);
-      HIP_TRY(hipGetLastError());
+      if ((rc = launch(c, rank_fill_kernel, rank_grid(A, 4096), kRankThreads, 0, rs, w.series, stride, NAN))) return rc;
       continue;
     }
     const uint64_t *sorted = w.keys[cur];
-    hipLaunchKernelGGL(rank_order_kernel, dim3(1), dim3(kRankThreads), 0, c->stream, sorted, A, (int)n_probs, (const double *)w.probs, st);
+    if ((rc = launch(c, rank_order_kernel, 1, kRankThreads, 0, sorted, A, n_probs, w.probs, st))) return rc;
     const int nh = rank_grid(A - khdi, kRankReduceBlocks);
-    hipLaunchKernelGGL(rank_hdi_kernel, dim3((unsigned)nh), dim3(kRankThreads), 0, c->stream, sorted, A, khdi, (RankArg *)w.part);
-    hipLaunchKernelGGL(rank_hdi_final_kernel, dim3(1), dim3(kRankThreads), 0, c->stream, sorted, A, khdi, nh, (const RankArg *)w.part, st);
+    if ((rc = launch(c, rank_hdi_kernel, nh, kRankThreads, 0, sorted, A, khdi, (RankArg *)w.part))) return rc;
+    if ((rc = launch(c, rank_hdi_final_kernel, 1, kRankThreads, 0, sorted, A, khdi, nh, (RankArg *)w.part, st))) return rc;
     if ((rc = rank_scores(c, w, rs, cur, w.series))) return rc;                        // bulk: z(x)
     if ((rc = rank_sort(c, w, A, d, p, x, true, st, &cur, &nonfinite))) return rc;    // folded: z(|x - median|)
     if ((rc = rank_scores(c, w, rs, cur, w.series + stride))) return rc;
-    hipLaunchKernelGGL(rank_indicator_kernel, dim3((unsigned)rank_grid(A, 4096)), dim3(kRankThreads), 0, c->stream, rs, x, (const double *)st,
-                       w.series + 2 * stride, w.series + 3 * stride);
+    if ((rc = launch(c, rank_indicator_kernel, rank_grid(A, 4096), kRankThreads, 0, rs, x, st, w.series + 2 * stride, w.series + 3 * stride))) return rc;
     const int nr = rank_grid(A, kRankReduceBlocks);
     for (int q = 0; q < RSF_DIAG_RANK_SERIES; ++q) {
-      hipLaunchKernelGGL(rank_range_kernel, dim3((unsigned)nr), dim3(kRankThreads), 0, c->stream, rs, (const double *)(w.series + q * stride),
-                         (double *)w.part);
-      hipLaunchKernelGGL(rank_range_final_kernel, dim3(1), dim3(64), 0, c->stream, nr, (const double *)w.part, st + kStConst + q);
+      if ((rc = launch(c, rank_range_kernel, nr, kRankThreads, 0, rs, w.series + q * stride, (double *)w.part))) return rc;
+      if ((rc = launch(c, rank_range_final_kernel, 1, 64, 0, nr, (double *)w.part, st + kStConst + q))) return rc;
     }
-    HIP_TRY(hipGetLastError());
   }
   std::vector<double> h((size_t)(d * ns));
   HIP_TRY(hipMemcpyAsync(h.data(), w.stats, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));

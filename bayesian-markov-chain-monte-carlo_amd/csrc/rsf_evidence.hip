@@ -60,7 +60,7 @@ int terms(rsf_ctx *c, int64_t n, const double *dl, double lstar, double s1, doub
   int rc;
   const int blocks = (int)std::min<int64_t>(kEvBlocks, (n + kMaxBlock - 1) / kMaxBlock);
   if ((rc = launch(c, evidence_terms_kernel<NUM>, blocks, kMaxBlock, 0, n, dl, lstar, s1, s2r, ws + kEvFields))) return rc;
-  if ((rc = launch(c, evidence_combine_kernel, kEvFields, kMaxBlock, 0, blocks, ws + kEvFields, ws))) return rc;
+  if ((rc = sum_strided_tree(c, blocks, kEvFields, ws + kEvFields, ws))) return rc;
   HIP_TRY(hipMemcpyAsync(h, ws, kEvFields * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RSF_OK;

@@ -146,8 +146,7 @@ int transpose(rsf_ctx *c, int64_t n, int d, const double *src, double *dst, bool
     if (src != dst) HIP_TRY(hipMemcpyAsync(dst, src, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return RSF_OK;
   }
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((n + kMaxBlock - 1) / kMaxBlock)), dim3(kMaxBlock), 0, c->stream, n, d, src, dst, to_soa);
-  return RSF_OK;
+  return launch(c, transpose_kernel, (unsigned)((n + kMaxBlock - 1) / kMaxBlock), kMaxBlock, 0, n, d, src, dst, to_soa);
 }
 
 // the caller's q [C][d] and V [C][d*d] into the chain state; a NULL one stays as it is
@@ -431,7 +430,6 @@ int rsf_mcmc_init(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q0, cons
   c->iters_done = 0;
   c->have_chains = true;
   c->external_chains = false;
-  HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));  // q0/data may be host buffers the caller reuses
   return RSF_OK;
 }
@@ -482,7 +480,6 @@ int rsf_mcmc_init_state(rsf_ctx *c, const rsf_mcmc_config *cfg, const double *q,
   c->iters_done = 0;
   c->have_chains = true;
   c->external_chains = true;
-  HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));  // the arguments may be host buffers the caller reuses
   return RSF_OK;
 }
@@ -531,6 +528,7 @@ int rsf_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out
   if (!ctr || !key || !out) return fail(RSF_ERR_INVALID, "rsf_philox4x32_10: NULL argument");
   uint32_t *d = nullptr;
   HIP_TRY(hipMalloc(&d, 4 * sizeof(uint32_t)));
+  // no ctx: the null stream, so not rsfh::launch; the copy that follows reports a failure
   hipLaunchKernelGGL(probe_philox_kernel, dim3(1), dim3(64), 0, nullptr, ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], d);
   hipError_t e = hipMemcpy(out, d, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost);
   (void)hipFree(d);
@@ -543,6 +541,7 @@ int rsf_mcmc_draws(uint64_t seed, int64_t chain, int64_t iteration, int32_t d, d
   if (d < 1 || d > 3) return fail(RSF_ERR_INVALID, "rsf_mcmc_draws: n_params out of range");
   double *dev = nullptr, h[5];
   HIP_TRY(hipMalloc(&dev, sizeof h));
+  // no ctx: the null stream, so not rsfh::launch; the copy that follows reports a failure
   hipLaunchKernelGGL(probe_draws_kernel, dim3(1), dim3(64), 0, nullptr, seed, (uint64_t)chain, (uint32_t)iteration, d, shape, dev);
   hipError_t e = hipMemcpy(h, dev, sizeof h, hipMemcpyDeviceToHost);
   (void)hipFree(dev);

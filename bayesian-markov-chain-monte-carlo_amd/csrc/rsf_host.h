@@ -194,16 +194,27 @@ template <auto V0, auto... Vs, class F> auto with(int v, F f) {
   else return v == (int)V0 ? f(std::integral_constant<decltype(V0), V0>{}) : with<Vs...>(v, f);
 }
 
-// One launch on the ctx stream.  The parameter types come from the kernel's pointer alone, and the call's arguments are
-// converted to them before their addresses are taken: a wrong count, order or type does not compile.
+// One launch on the ctx stream: EVERY launch of a kernel on it, and its return code is the launch's check.  The parameter types
+// come from the kernel's pointer alone, and the call's arguments are converted to them before their addresses are taken: a
+// wrong count, order or type does not compile.  grid: a plain count converts to dim3.
 template <class T> struct as_declared { using type = T; };
 
 template <class... P>
-int launch(rsf_ctx *c, void (*fn)(P...), unsigned grid, unsigned block, size_t lds, typename as_declared<P>::type... a) {
+int launch(rsf_ctx *c, void (*fn)(P...), dim3 grid, unsigned block, size_t lds, typename as_declared<P>::type... a) {
   void *args[] = {(void *)&a...};
-  HIP_TRY(hipLaunchKernel((const void *)fn, dim3(grid), dim3(block), args, lds, c->stream));
+  HIP_TRY(hipLaunchKernel((const void *)fn, grid, dim3(block), args, lds, c->stream));
   return RSF_OK;
 }
+
+// ---- the last step of a reduction (rsf_pool.hip; kernels: rsf_kernels_pool.h) -----------------------------------------
+// The workgroups' partials part[b][nf] of any unit, device pointers, summed on the ctx stream.  Each is named by the order of
+// its additions, which is its contract: the results' bits depend on it.
+// In index order: out[s][f] = scale * (0.0 + part[s per][f] + part[s per + 1][f] + ...), slab s of `per` partials, the last slab
+// up to nblocks; ceil(nblocks / per) slabs.  One thread per field in grid_x workgroups of 256 (0: as many as cover nf).
+int sum_in_order(rsf_ctx *c, int64_t nblocks, int64_t per, int64_t nf, const double *part, double scale, double *out, unsigned grid_x = 0);
+// Strided, then a tree: out[f] from one workgroup of 256 per field; thread t adds part[t][f], part[t + 256][f], ... in that order
+// from 0.0, then the descending shuffle tree of each wave (wave_sum), then the four waves in index order.
+int sum_strided_tree(rsf_ctx *c, int nblocks, int nf, const double *part, double *out);
 
 }  // namespace rsfh
 

@@ -1,6 +1,6 @@
 // rsf_kernel_common.h — what the kernel headers (rsf_kernels_core.h, rsf_kernels_sampler.h, rsf_kernels_pool.h, rsf_predict.h)
-// and the host units (through rsf_host.h) share: constants, the sampler's argument block and the proposal's three device
-// functions.  NO KERNEL lives here, so any unit may include it (a header that defines a non-template
+// and the host units (through rsf_host.h) share: constants, the sampler's argument block, the proposal's three device
+// functions and the fixed-order sums over a wave's lanes and a workgroup's waves.  NO KERNEL lives here, so any unit may include it (a header that defines a non-template
 // __global__ function belongs to exactly one unit).
 //
 // One lane = one chain, wave64 = 64 independent chains, fp64 VALU bound; no MFMA — the path is an elementwise ODE
@@ -80,6 +80,46 @@ __device__ __forceinline__ bool in_box(const double (&qn)[D], const ARGS &A) {
 #pragma unroll
   for (int p = 0; p < D; ++p) inb = inb && (qn[p] > A.lo[p]) && (qn[p] < A.hi[p]);  // strict box, MCMC.py:318-320
   return inb;
+}
+
+// ---- fixed-order sums over lanes and waves --------------------------------------------------------------------------
+// The order of the additions is part of a result's bits: each helper below IS one order, and a reduction that adds in
+// another order keeps its own code (pred_sum8, psis_block_reduce, the rank kernels' scans and min/max trees).
+
+// descending shuffle tree, off = 32 .. 1: the wave's sum, valid in lane 0
+template <class T> __device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// ascending xor butterfly, s = 1 .. 32: the wave's sum (or maximum) in every lane (a + b == b + a bit for bit, so the lanes agree)
+template <bool MAX> __device__ __forceinline__ double wave_all_ascending(double v) {
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const double o = __shfl_xor(v, s, 64);
+    v = MAX ? fmax(v, o) : v + o;
+  }
+  return v;
+}
+
+// descending xor butterfly, off = 32 .. 1: the wave's sum in every lane.  Not wave_all_ascending<false>: it pairs the lanes in
+// the opposite sequence, which rounds differently
+__device__ __forceinline__ double wave_all_descending(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// The tail of a workgroup's per-field sums.  sh[w][f] is wave w's sum of field f, stored by its lead lane, and the caller's
+// barrier lies between those stores and this call; thread f < nf (nf <= blockDim.x) adds the waves in index order from
+// sh[0][f] and writes part[row + f], row = nf * the workgroup's index in part[block][nf].
+template <int NF> __device__ __forceinline__ void block_fields_store(const double (*sh)[NF], int nf, double *part, int64_t row) {
+  if (threadIdx.x < (unsigned)nf) {
+    double s = sh[0][threadIdx.x];
+    for (unsigned w = 1; w < blockDim.x / 64; ++w) s += sh[w][threadIdx.x];
+    part[row + threadIdx.x] = s;
+  }
 }
 
 struct McmcArgs {

@@ -1,6 +1,6 @@
 // rsf_kernels_evidence.h — the marginal likelihood of the pooled draws by bridge sampling (include/rsf_evidence.h):
-// evidence_propose_kernel, evidence_logg_kernel, evidence_logtarget_kernel, evidence_terms_kernel, evidence_combine_kernel.
-// Included by rsf_evidence.hip only (evidence_combine_kernel is not a template: DESIGN.md 4a).
+// evidence_propose_kernel, evidence_logg_kernel, evidence_logtarget_kernel, evidence_terms_kernel.  Included by rsf_evidence.hip
+// only.  The last step of the sums, over the workgroups' partials, is rsfh::sum_strided_tree (rsf_host.h).
 //
 // Reproducibility: every sum below has an order fixed by the shape of the input and the launch geometry, which the host derives
 // from n alone — per thread in index order, per wave by the shuffle tree, the waves of a workgroup and the workgroups' partials in
@@ -164,34 +164,11 @@ evidence_terms_kernel(int64_t n, const double *__restrict__ l, double lstar, dou
   const int wave = threadIdx.x >> 6;
 #pragma unroll
   for (int f = 0; f < kEvFields; ++f) {
-    double v = s[f];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    const double v = wave_sum(s[f]);
     if ((threadIdx.x & 63) == 0) sh[wave][f] = v;
   }
   __syncthreads();
-  if (threadIdx.x < kEvFields) {
-    double v = sh[0][threadIdx.x];
-    for (unsigned w = 1; w < blockDim.x / 64; ++w) v += sh[w][threadIdx.x];
-    part[(int64_t)blockIdx.x * kEvFields + threadIdx.x] = v;
-  }
-}
-
-// out[f] = the workgroups' partials of field f = blockIdx.x: thread t takes t, t + 256, ... in that order, then the shuffle tree
-// and the waves in index order
-__global__ void __launch_bounds__(kMaxBlock) evidence_combine_kernel(int nblocks, const double *__restrict__ part, double *__restrict__ out) {
-  __shared__ double sh[kMaxBlock / 64];
-  const int f = blockIdx.x;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += part[(int64_t)b * kEvFields + f];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (unsigned w = 1; w < blockDim.x / 64; ++w) s += sh[w];
-    out[f] = s;
-  }
+  block_fields_store(sh, kEvFields, part, (int64_t)blockIdx.x * kEvFields);
 }
 
 }  // namespace rsfk

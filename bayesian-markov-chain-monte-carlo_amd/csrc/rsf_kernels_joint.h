@@ -1,6 +1,6 @@
 // rsf_kernels_joint.h — the joint posterior of the pooled draws (include/rsf_joint.h): pool_joint_moments_kernel,
-// pool_joint_combine_kernel, pool_hist2d_kernel, pool_kde2d_kernel.  Included by rsf_pool.hip only, after rsf_kernels_pool.h,
-// whose hist_bin, pool_hist_finish_kernel and pool_kde_reduce_kernel these share.
+// pool_hist2d_kernel, pool_kde2d_kernel.  Included by rsf_pool.hip only, after rsf_kernels_pool.h, whose hist_bin,
+// pool_hist_finish_kernel, sum_strided_tree_kernel (the moments' last step) and sum_in_order_kernel (the KDE's) these share.
 //
 // Reproducibility: every sum below has an order fixed by the shape of the input and the launch geometry (grid and block sizes,
 // which the host derives from n, d and m alone) — per thread in row order, per wave by the shuffle tree, the waves of a
@@ -63,8 +63,7 @@ pool_joint_moments_kernel(int64_t n, int d, const double *__restrict__ x, JointC
   const int nd = EXACT ? D : d, wave = threadIdx.x >> 6;
   const bool lead = (threadIdx.x & 63) == 0;
   auto emit = [&](double s, int f) {  // the wave's sum of s into field f of its LDS row
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    s = wave_sum(s);
     if (lead) sh[wave][f] = s;
   };
   emit(cnt, 0);
@@ -79,28 +78,7 @@ pool_joint_moments_kernel(int64_t n, int d, const double *__restrict__ x, JointC
   }
   __syncthreads();
   const int nf = joint_fields(nd);
-  for (int f = threadIdx.x; f < nf; f += blockDim.x) {
-    double s = sh[0][f];
-    for (unsigned w = 1; w < blockDim.x / 64; ++w) s += sh[w][f];
-    part[(int64_t)blockIdx.x * nf + f] = s;
-  }
-}
-
-// Field blockIdx.x of the result: thread t takes the workgroups' partials t, t + 256, ... in that order, then the shuffle tree
-// and the waves in index order.  (One thread per field walking all 1024 partials took longer than the pass over the pool.)
-__global__ void __launch_bounds__(kMaxBlock) pool_joint_combine_kernel(int nblocks, int nf, const double *__restrict__ part, double *__restrict__ out) {
-  __shared__ double sh[kMaxBlock / 64];
-  const int f = blockIdx.x;
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += part[(int64_t)b * nf + f];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (unsigned w = 1; w < blockDim.x / 64; ++w) s += sh[w];
-    out[f] = s;
-  }
+  block_fields_store(sh, nf, part, (int64_t)blockIdx.x * nf);
 }
 
 // 2-D fixed-bin histogram (rsf_pool_histogram2d), pool_hist_kernel with a cell per pair of bins: one pass, HBM-bound, both
@@ -134,7 +112,7 @@ pool_hist2d_kernel(int64_t n, const double *__restrict__ x, int64_t ld, Hist2dAx
 // keeps kKde2dPoints whitened points in registers, so one LDS broadcast read of (u, v), 16 bytes, serves that many pairs; per pair:
 // two subtractions, a multiply, a fused multiply-add, rsf::fm::exp and an add.
 // Grid: x = chunks of kMaxBlock * kKde2dPoints points, y = slices of the samples (a 64 x 64 mesh fills the part when n is small,
-// 3e7 draws fill it when m is small).  partial[slice][m] is summed over the slices in index order by pool_kde_reduce_kernel: the
+// 3e7 draws fill it when m is small).  partial[slice][m] is summed over the slices in index order by sum_in_order_kernel: the
 // result depends on the inputs and on this geometry, which the host derives from (n, m) alone, and on nothing else.
 // kKde2dPoints = 4, chosen by measurement among {1, 2, 4} (97.0, 100.4 and 95.3 ms for 33.6 M draws x 4096 points): DESIGN.md 4f.
 constexpr int kKde2dPoints = 4;

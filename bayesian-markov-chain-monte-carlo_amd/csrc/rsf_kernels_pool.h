@@ -1,4 +1,6 @@
-// rsf_kernels_pool.h — posterior post-processing of the pooled draws: pool_moments_kernel, pool_hist_*, pool_kde_*.
+// rsf_kernels_pool.h — posterior post-processing of the pooled draws: pool_moments_kernel, pool_hist_kernel,
+// pool_hist_finish_kernel, pool_kde_kernel; and the last step of every unit's reductions, sum_in_order_kernel and
+// sum_strided_tree_kernel, which the other units reach through rsfh::sum_in_order / sum_strided_tree (rsf_host.h).
 // Included by rsf_pool.hip only (none of these kernels is a template).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,11 +29,9 @@ pool_moments_kernel(int64_t n, const double *__restrict__ x, int64_t stride, dou
     cnt += 1.0; sum += dlt; sumsq = __builtin_fma(dlt, dlt, sumsq);
     mn = fmin(mn, v); mx = fmax(mx, v);
   }
+  cnt = wave_sum(cnt); sum = wave_sum(sum); sumsq = wave_sum(sumsq);
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off, 64); sum += __shfl_down(sum, off, 64); sumsq += __shfl_down(sumsq, off, 64);
-    mn = fmin(mn, __shfl_down(mn, off, 64)); mx = fmax(mx, __shfl_down(mx, off, 64));
-  }
+  for (int off = 32; off > 0; off >>= 1) { mn = fmin(mn, __shfl_down(mn, off, 64)); mx = fmax(mx, __shfl_down(mx, off, 64)); }
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = {cnt, sum, sumsq, mn, mx};
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -112,13 +112,35 @@ pool_kde_kernel(int64_t n, const double *__restrict__ x, int64_t stride, int m, 
   }
 }
 
+// ---- the last step of a reduction: the workgroups' partials part[b][nf], summed in one of two fixed orders --------------
+// In index order, one thread per field f = blockIdx.x * 256 + threadIdx.x, slab s = blockIdx.y of `per` partials:
+// out[s][f] = scale * (0.0 + part[s per][f] + part[s per + 1][f] + ...) up to the slab's or the partials' end.  A scale of 1.0
+// changes no bit.
 __global__ void __launch_bounds__(kMaxBlock)
-pool_kde_reduce_kernel(int nblocks, int m, const double *__restrict__ partial, double norm, double *__restrict__ density) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
-  double acc = 0.0;
-  for (int b = 0; b < nblocks; ++b) acc += partial[(int64_t)b * m + j];  // fixed order: reproducible
-  density[j] = acc * norm;
+sum_in_order_kernel(int64_t nblocks, int64_t per, int64_t nf, const double *__restrict__ part, double scale, double *__restrict__ out) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t b0 = (int64_t)blockIdx.y * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
+  double t = 0.0;
+  for (int64_t b = b0; b < b1; ++b) t += part[b * nf + f];
+  out[(int64_t)blockIdx.y * nf + f] = t * scale;
+}
+
+// Strided, then a tree, one workgroup per field f = blockIdx.x: thread t takes the partials t, t + 256, ... in that order from
+// 0.0, then wave_sum and the waves in index order.  (One thread per field walking all 1024 partials of a few fields took longer
+// than the pass over the pool that made them.)
+__global__ void __launch_bounds__(kMaxBlock) sum_strided_tree_kernel(int nblocks, int nf, const double *__restrict__ part, double *__restrict__ out) {
+  __shared__ double sh[kMaxBlock / 64];
+  const int f = blockIdx.x;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += blockDim.x) s += part[(int64_t)b * nf + f];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (unsigned w = 1; w < blockDim.x / 64; ++w) s += sh[w];
+    out[f] = s;
+  }
 }
 
 }  // namespace rsfk

@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
 // rather than a chains-per-lane parameter of mcmc_kernel: written that way, the float64 kernels — which sit at 252-256
 // registers — came out with 12-44 B of scratch per lane.)  The sampler logic itself stays float64, with mcmc_kernel's
 // propose, metropolis and gibbs_std2.  Only here: the uniform is drawn after the solve, the one-parameter window stays in
-// registers, counters are reduced once (rsf::wave_sum).  The draws, box test, trace row and adaptation are still written
+// registers, counters are reduced once (wave_sum).  The draws, box test, trace row and adaptation are still written
 // out in both kernels: as helpers they grew this kernel's spills (d = 3: 512 -> 528-1008 B, the adaptation's partly inside
 // the trip loop) or mcmc_kernel's SGPR spills in its solve loops (HISTORY.md: one definition of the chain logic).
 // Per-chain sampler state of one slot:
@@ -588,7 +588,8 @@ mcmc_f32x2_kernel(Consts K, McmcArgs A) {  // (the registers above that count: t
     }
   }
   // statistics: wave shuffle reduction, one atomic per wave and counter
-  const unsigned long long s0 = rsf::wave_sum(n_acc), s1 = rsf::wave_sum(n_eval), s2 = rsf::wave_sum(n_nonfinite), s3 = rsf::wave_sum(n_oob);
+  const unsigned long long s0 = wave_sum<unsigned long long>(n_acc), s1 = wave_sum<unsigned long long>(n_eval),
+                           s2 = wave_sum<unsigned long long>(n_nonfinite), s3 = wave_sum<unsigned long long>(n_oob);  // 64-bit sums of the 32-bit counters
   if ((threadIdx.x & 63) == 0) {
     if (s0) atomicAdd(&A.stats[RSF_CNT_ACCEPTED], s0);
     if (s1) atomicAdd(&A.stats[RSF_CNT_EVALUATED], s1);

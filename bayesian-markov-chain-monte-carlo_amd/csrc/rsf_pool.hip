@@ -1,5 +1,6 @@
 // rsf_pool.hip — posterior post-processing of the pooled draws: rsf_pool_summary / _kde / _histogram (kernels: rsf_kernels_pool.h)
-// and their joint posterior, rsf_pool_joint_partials / _kde2d / _histogram2d (include/rsf_joint.h, kernels: rsf_kernels_joint.h).
+// and their joint posterior, rsf_pool_joint_partials / _kde2d / _histogram2d (include/rsf_joint.h, kernels: rsf_kernels_joint.h);
+// and rsfh::sum_in_order / sum_strided_tree, the last step of every unit's reductions (rsf_host.h).
 #include <cmath>
 #include <algorithm>
 #include <vector>
@@ -10,6 +11,19 @@
 
 using namespace rsfk;
 using namespace rsfh;
+
+namespace rsfh {
+
+int sum_in_order(rsf_ctx *c, int64_t nblocks, int64_t per, int64_t nf, const double *part, double scale, double *out, unsigned grid_x) {
+  if (!grid_x) grid_x = (unsigned)((nf + kMaxBlock - 1) / kMaxBlock);
+  return launch(c, sum_in_order_kernel, dim3(grid_x, (unsigned)((nblocks + per - 1) / per)), kMaxBlock, 0, nblocks, per, nf, part, scale, out);
+}
+
+int sum_strided_tree(rsf_ctx *c, int nblocks, int nf, const double *part, double *out) {
+  return launch(c, sum_strided_tree_kernel, nf, kMaxBlock, 0, nblocks, nf, part, out);
+}
+
+}  // namespace rsfh
 
 extern "C" {
 
@@ -23,7 +37,7 @@ int pool_moments(rsf_ctx *c, int64_t n, const double *dx, int64_t stride, double
   HIP_TRY(hipMemcpyAsync(&shift, dx, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const int blocks = (int)std::min<int64_t>(kPoolBlocks, (n + kMaxBlock - 1) / kMaxBlock);
-  hipLaunchKernelGGL(pool_moments_kernel, dim3(blocks), dim3(kMaxBlock), 0, c->stream, n, dx, stride, shift, (PoolPartial *)c->pool.p);
+  if ((rc = launch(c, pool_moments_kernel, blocks, kMaxBlock, 0, n, dx, stride, shift, (PoolPartial *)c->pool.p))) return rc;
   std::vector<PoolPartial> h(blocks);
   HIP_TRY(hipMemcpyAsync(h.data(), c->pool.p, sizeof(PoolPartial) * blocks, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -63,10 +77,8 @@ int rsf_pool_kde(rsf_ctx *c, int64_t n, const double *x, int64_t stride, int32_t
   const int blocks = (int)std::min<int64_t>(kPoolBlocks, (n + kKdeTile - 1) / kKdeTile);
   DevBuf &ws = c->poolws;
   if ((rc = ensure(ws, (size_t)blocks * (size_t)m * sizeof(double)))) return rc;
-  hipLaunchKernelGGL(pool_kde_kernel, dim3(blocks), dim3(kMaxBlock), 0, c->stream, n, dx, stride, (int)m, dg, 0.5 / cov,
-                     (double *)ws.p);
-  hipLaunchKernelGGL(pool_kde_reduce_kernel, dim3((m + kMaxBlock - 1) / kMaxBlock), dim3(kMaxBlock), 0, c->stream, blocks, (int)m,
-                     (const double *)ws.p, 1.0 / ((double)n * std::sqrt(2.0 * 3.14159265358979323846 * cov)), dd);
+  if ((rc = launch(c, pool_kde_kernel, blocks, kMaxBlock, 0, n, dx, stride, m, dg, 0.5 / cov, (double *)ws.p))) return rc;
+  if ((rc = sum_in_order(c, blocks, blocks, m, (const double *)ws.p, 1.0 / ((double)n * std::sqrt(2.0 * 3.14159265358979323846 * cov)), dd))) return rc;
   if ((rc = copy_back(c, SLOT_POOL_OUT, density, (size_t)m * sizeof(double)))) return rc;
   return finish(c);
 }
@@ -85,10 +97,9 @@ int rsf_pool_histogram(rsf_ctx *c, int64_t n, const double *x, int64_t stride, i
   if ((rc = ensure(ws, (size_t)nb * sizeof(unsigned long long)))) return rc;
   HIP_TRY(hipMemsetAsync(ws.p, 0, (size_t)nb * sizeof(unsigned long long), c->stream));
   const int blocks = (int)std::min<int64_t>(kPoolBlocks, (n + kMaxBlock - 1) / kMaxBlock);
-  hipLaunchKernelGGL(pool_hist_kernel, dim3(blocks), dim3(kMaxBlock), (size_t)nb * sizeof(unsigned int), c->stream, n, dx, stride,
-                     (int)nbins, lo, hi, (double)nbins / (hi - lo), (hi - lo) / (double)nbins, (unsigned long long *)ws.p);
-  hipLaunchKernelGGL(pool_hist_finish_kernel, dim3((nb + kMaxBlock - 1) / kMaxBlock), dim3(kMaxBlock), 0, c->stream, nb,
-                     (const unsigned long long *)ws.p, dout);
+  if ((rc = launch(c, pool_hist_kernel, blocks, kMaxBlock, (size_t)nb * sizeof(unsigned int), n, dx, stride, nbins, lo, hi,
+                   (double)nbins / (hi - lo), (hi - lo) / (double)nbins, (unsigned long long *)ws.p))) return rc;
+  if ((rc = launch(c, pool_hist_finish_kernel, (nb + kMaxBlock - 1) / kMaxBlock, kMaxBlock, 0, nb, (const unsigned long long *)ws.p, dout))) return rc;
   if ((rc = copy_back(c, SLOT_POOL_OUT, counts, (size_t)nb * sizeof(double)))) return rc;
   return finish(c);
 }
@@ -99,6 +110,7 @@ namespace {
 
 // joint partials of the columns A.col[0..d) of x (a device pointer) about A.c; result on the host in the layout of rsf_joint.h
 static int joint_moments(rsf_ctx *c, int64_t n, int d, const double *dx, const JointCols &A, double *partials) {
+  static_assert(joint_fields(RSF_JOINT_MAX_PARAMS) <= kMaxBlock, "block_fields_store: one thread per field");
   const int nf = joint_fields(d);
   const int blocks = (int)std::min<int64_t>(kPoolBlocks, (n + kMaxBlock - 1) / kMaxBlock);
   int rc = ensure(c->pool, sizeof(double) * (size_t)nf * (size_t)(blocks + 1));
@@ -107,7 +119,7 @@ static int joint_moments(rsf_ctx *c, int64_t n, int d, const double *dx, const J
   auto fn = d == 1 ? pool_joint_moments_kernel<1, true> : d == 2 ? pool_joint_moments_kernel<2, true>
           : d == 3 ? pool_joint_moments_kernel<3, true> : pool_joint_moments_kernel<RSF_JOINT_MAX_PARAMS, false>;
   if ((rc = launch(c, fn, blocks, kMaxBlock, 0, n, d, dx, A, part))) return rc;
-  if ((rc = launch(c, pool_joint_combine_kernel, nf, kMaxBlock, 0, blocks, nf, part, sum))) return rc;
+  if ((rc = sum_strided_tree(c, blocks, nf, part, sum))) return rc;
   HIP_TRY(hipMemcpyAsync(partials, sum, sizeof(double) * nf, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RSF_OK;
@@ -169,9 +181,8 @@ int rsf_pool_kde2d(rsf_ctx *c, int64_t n, int32_t d, const double *x, int32_t pa
   const int slices = (int)std::max<int64_t>(1, std::min<int64_t>((n + kKdeTile - 1) / kKdeTile, (kPoolBlocks + chunks - 1) / chunks));
   DevBuf &ws = c->poolws;
   if ((rc = ensure(ws, (size_t)slices * (size_t)m * sizeof(double)))) return rc;
-  hipLaunchKernelGGL(pool_kde2d_kernel, dim3((unsigned)chunks, (unsigned)slices), dim3(kMaxBlock), 0, c->stream, A, dx, dp, (double *)ws.p);
-  hipLaunchKernelGGL(pool_kde_reduce_kernel, dim3((m + kMaxBlock - 1) / kMaxBlock), dim3(kMaxBlock), 0, c->stream, slices, (int)m,
-                     (const double *)ws.p, 1.0 / (nt * 2.0 * 3.14159265358979323846 * l00 * l11), dd);
+  if ((rc = launch(c, pool_kde2d_kernel, dim3((unsigned)chunks, (unsigned)slices), kMaxBlock, 0, A, dx, dp, (double *)ws.p))) return rc;
+  if ((rc = sum_in_order(c, slices, slices, m, (const double *)ws.p, 1.0 / (nt * 2.0 * 3.14159265358979323846 * l00 * l11), dd))) return rc;
   if ((rc = copy_back(c, SLOT_POOL_OUT, density, (size_t)m * sizeof(double)))) return rc;
   return finish(c);
 }
@@ -201,9 +212,8 @@ int rsf_pool_histogram2d(rsf_ctx *c, int64_t n, int32_t d, const double *x, int3
   const Hist2dAxis B{pb, nby, lo_b, hi_b, (double)nby / (hi_b - lo_b), (hi_b - lo_b) / (double)nby};
   const size_t lds = (size_t)nb * sizeof(unsigned int);
   if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)pool_hist2d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(pool_hist2d_kernel, dim3(blocks), dim3(kMaxBlock), lds, c->stream, n, dx, (int64_t)d, A, B, (unsigned long long *)ws.p);
-  hipLaunchKernelGGL(pool_hist_finish_kernel, dim3((nb + kMaxBlock - 1) / kMaxBlock), dim3(kMaxBlock), 0, c->stream, nb,
-                     (const unsigned long long *)ws.p, dout);
+  if ((rc = launch(c, pool_hist2d_kernel, blocks, kMaxBlock, lds, n, dx, d, A, B, (unsigned long long *)ws.p))) return rc;
+  if ((rc = launch(c, pool_hist_finish_kernel, (nb + kMaxBlock - 1) / kMaxBlock, kMaxBlock, 0, nb, (const unsigned long long *)ws.p, dout))) return rc;
   if ((rc = copy_back(c, SLOT_POOL_OUT, counts, (size_t)nb * sizeof(double)))) return rc;
   return finish(c);
 }

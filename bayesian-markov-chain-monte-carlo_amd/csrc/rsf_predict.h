@@ -1,9 +1,9 @@
 // rsf_predict.h — posterior predictive checks of pooled draws (include/rsf_predict.h), the kernels:
 //   predict_kernel         one lane per draw: the float64 RK4 tier code driven by rsf::integrate_lockstep, and at every
 //                          completed output sample the wave's 64 values y_ik go through an LDS tile to the lanes that reduce them;
-//   predict_sum_kernel     fixed-order sum of the per-wave partials, in two levels (slabs of waves, then the slabs);
 //   predict_select_kernel  exact order statistics of every row of a materialised series by rank_select, then rank_lerp.
-// No float atomics; every sum across lanes, waves and workgroups has a fixed order, so the same draws give the same bits.
+// The per-wave partials are summed in index order by rsfh::sum_in_order (rsf_host.h), in two levels: slabs of kPredSlab waves,
+// then the slabs.  No float atomics; every sum across lanes, waves and workgroups has a fixed order, so the same draws give the same bits.
 //
 // The per-sample hook.  A wave parks its 64 samples of an output time in one slot of a ring of kPredSlots slots (64 doubles
 // each) — a conflict-free store, lane = bank.  Once a trip of RK4 steps is done and at least kPredTile slots are filled, the
@@ -33,7 +33,7 @@ constexpr int kPredWaveDoubles = kPredSlots * 64 + kPredParams * 64;  // 10 KiB 
 // LDS of a predict launch: the loading table chunk, then kPredWaveDoubles per wave.  Two workgroups of four waves per CU
 // (160 KiB): 40 KiB of wave areas + at most this much table; nsteps 2000 (32 KB of loading values) stays resident.
 constexpr size_t kPredTableBudget = 38 * 1024;
-constexpr int kPredSlab = 64;    // waves per slab of the first level of predict_sum_kernel
+constexpr int kPredSlab = 64;    // waves per slab of the first level of the partials' sum
 
 struct PredictArgs {
   int64_t n;
@@ -142,17 +142,6 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) predict_kernel(Consts K
     rsf::integrate_lockstep<DAMP>(lds, K, L, st, kn, [&](double ak, int) { park(ak); }, [&] { if (cnt >= kPredTile) flush(kPredTile); });
   }
   while (cnt > 0) flush(cnt < kPredTile ? cnt : kPredTile);
-}
-
-// out[s][f] = sum over the blocks b of slab s (b = s * per .. min(nblocks, (s + 1) * per) - 1, in order) of part[b][f]
-__global__ void __launch_bounds__(256) predict_sum_kernel(int64_t nblocks, int64_t per, int64_t nf, const double *__restrict__ part,
-                                                          double *__restrict__ out) {
-  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= nf) return;
-  const int64_t b0 = (int64_t)blockIdx.y * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
-  double t = 0.0;
-  for (int64_t b = b0; b < b1; ++b) t += part[b * nf + f];
-  out[(int64_t)blockIdx.y * nf + f] = t;
 }
 
 // ---- exact quantiles of every row ---------------------------------------------------------------------------------------

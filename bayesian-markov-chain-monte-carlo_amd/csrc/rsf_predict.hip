@@ -82,10 +82,8 @@ int rsf_predict_partials(rsf_ctx *c, int64_t n, int32_t d, const double *q, cons
   A.tab_doubles = (int32_t)((2 * S * kc + 1 + 1) & ~(int64_t)1);
   const size_t lds = ((size_t)A.tab_doubles + (size_t)wpb * kPredWaveDoubles) * sizeof(double);
   if ((rc = launch(c, predict_fn(c, d, dser != nullptr), (unsigned)grid, c->block, lds, K, A))) return rc;
-  const unsigned fb = (unsigned)((nf + 255) / 256);
-  hipLaunchKernelGGL(predict_sum_kernel, dim3(fb, (unsigned)nslabs), dim3(256), 0, c->stream, nwaves, (int64_t)kPredSlab, nf, (const double *)w, w + o_slab);
-  hipLaunchKernelGGL(predict_sum_kernel, dim3(fb, 1), dim3(256), 0, c->stream, nslabs, nslabs, nf, (const double *)(w + o_slab), w + o_sum);
-  HIP_TRY(hipGetLastError());
+  if ((rc = sum_in_order(c, nwaves, kPredSlab, nf, w, 1.0, w + o_slab))) return rc;
+  if ((rc = sum_in_order(c, nslabs, nslabs, nf, w + o_slab, 1.0, w + o_sum))) return rc;
   std::vector<double> h((size_t)nf);
   HIP_TRY(hipMemcpyAsync(h.data(), w + o_sum, (size_t)nf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if ((rc = copy_back(c, SLOT_SERIES, series_out, nb * (size_t)nout))) return rc;
@@ -110,8 +108,7 @@ int rsf_predict_quantiles(rsf_ctx *c, int64_t n, int64_t nout, const double *ser
   if ((rc = stage_series(c, __func__, SLOT_X, series, n, nout, &ds))) return rc;
   const size_t ob = (size_t)n_probs * (size_t)nout * sizeof(double);
   if ((rc = ensure(c->poolws, ob))) return rc;
-  hipLaunchKernelGGL(predict_select_kernel, dim3((unsigned)nout), dim3(kPredSelectThreads), 0, c->stream, n, nout, ds, (int)n_probs, P, (double *)c->poolws.p);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch(c, predict_select_kernel, (unsigned)nout, kPredSelectThreads, 0, n, nout, ds, n_probs, P, (double *)c->poolws.p))) return rc;
   HIP_TRY(hipMemcpyAsync(out, c->poolws.p, ob, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RSF_OK;
@@ -147,7 +144,6 @@ int rsf_predict_psis_loo(rsf_ctx *c, int64_t n, int64_t nout, const double *seri
   if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)psis_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   if ((rc = launch(c, psis_params_kernel, (unsigned)((n + 255) / 256), 256, 0, n, dstd2, (double *)c->predict.p))) return rc;
   if ((rc = launch(c, psis_row_kernel, (unsigned)nout, kPsisThreads, lds, A))) return rc;
-  HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_rows, c->poolws.p, ob, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RSF_OK;
@@ -182,7 +178,6 @@ int rsf_predict_noise_quantiles(rsf_ctx *c, int64_t n, int64_t nout, const doubl
   if ((rc = launch(c, noise_params_kernel, (unsigned)((n + 255) / 256), 256, 0, n, dstd2, (double *)c->predict.p, (uint32_t *)A.bad))) return rc;
   // the row kernel unrolls its loops over the targets: few probabilities take the short one (a target's arithmetic is the same in both)
   if ((rc = launch(c, n_probs <= 4 ? noise_quantile_row_kernel<4> : noise_quantile_row_kernel<kNoiseMaxProbs>, (unsigned)nout, kNoiseThreads, 0, A))) return rc;
-  HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, A.out, ob, hipMemcpyDeviceToHost, c->stream));
   if (passes_out) HIP_TRY(hipMemcpyAsync(passes_out, A.passes, pb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

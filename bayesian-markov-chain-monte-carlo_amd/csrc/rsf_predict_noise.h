@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsf_kernel_common.h"
 #include "rsf_rank_device.h"
 
 namespace rsfk {
@@ -69,16 +70,6 @@ __device__ __forceinline__ double noise_uniform(double v) {
   return __longlong_as_double((long long)((uint64_t)hi << 32 | lo));
 }
 
-template <bool MAX>
-__device__ __forceinline__ double noise_wave_reduce(double v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const double o = __shfl_xor(v, s, 64);
-    v = MAX ? fmax(v, o) : v + o;  // (a + b == b + a bit for bit: every lane holds the same result)
-  }
-  return v;
-}
-
 // NP: the targets the unrolled loops provide for (4 or 16); the arithmetic of a target is the same in both
 template <int NP>
 __global__ void __launch_bounds__(kNoiseThreads) noise_quantile_row_kernel(NoiseArgs A) {
@@ -118,7 +109,7 @@ __global__ void __launch_bounds__(kNoiseThreads) noise_quantile_row_kernel(Noise
 #pragma unroll
   for (int j = 0; j < 2 * NP; ++j) {
     if (j < 2 * np) {
-      const double w = noise_wave_reduce<true>(a[j]);
+      const double w = wave_all_ascending<true>(a[j]);
       if (lane == 0) red[j][wave] = w;
     }
   }
@@ -176,7 +167,7 @@ __global__ void __launch_bounds__(kNoiseThreads) noise_quantile_row_kernel(Noise
 #pragma unroll
     for (int j = 0; j < 2 * NP; ++j) {
       if (run >> (j >> 1) & 1u) {
-        const double w = noise_wave_reduce<false>(a[j]);
+        const double w = wave_all_ascending<false>(a[j]);
         if (lane == 0) red[j][wave] = w;
       }
     }

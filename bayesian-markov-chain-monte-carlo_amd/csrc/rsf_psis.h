@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsf_kernel_common.h"
 #include "rsf_rank_device.h"
 
 namespace rsfk {
@@ -35,13 +36,6 @@ __global__ void __launch_bounds__(256) psis_params_kernel(int64_t n, const doubl
   const double s2 = std2[i];
   par[i] = 0.5 * log(6.283185307179586476925 * s2);
   par[n + i] = 0.5 / s2;
-}
-
-// the sum over the wave's 64 lanes, in all of them (a + b == b + a bit for bit, so the butterfly agrees everywhere)
-__device__ __forceinline__ double psis_wave_sum(double v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s, 64);
-  return v;
 }
 
 // fixed tree over the workgroup's per-thread values; the result in every thread.  red: kPsisThreads doubles of LDS
@@ -166,7 +160,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_row_kernel(PsisArgs A) {
       b += 1.0 / tmax;
       double s = 0.0;
       for (int i = lane; i < N; i += 64) s += log1p(-b * ts[i]);
-      const double kj = psis_wave_sum(s) / dN;
+      const double kj = wave_all_ascending<false>(s) / dN;
       if (lane == 0) {
         cb[j] = b;
         cL[j] = dN * (log(-b / kj) - kj - 1.0);

@@ -78,9 +78,9 @@ __device__ __forceinline__ double rank_lerp(double a, double b, double g) {
 // eight bits from the top, each a read of the row; per target rank a 256-bin histogram (LDS, integer atomics) of the keys that
 // agree with the rank's prefix so far, then one thread per rank walks its bins to the digit that holds the rank.  Thread q < nr
 // sets want[q] (the 0-based rank) before the call; after it prefix[q] is that order statistic's key.  key(j, pass): element j's.
-// (The workgroup reductions of these files — diag_block_sum, psis_block_reduce, psis_wave_sum, rank_block_scan, the shfl_xor
-// loops of diag_super_kernel, pred_sum8 — are NOT shared like this on purpose: each fixes its own summation order, and the
-// order is part of the results' bits.)
+// (The workgroup reductions of these files — diag_block_sum, psis_block_reduce, rank_block_scan, pred_sum8 — are NOT shared
+// like this on purpose: each fixes its own summation order, and the order is part of the results' bits.  The orders that
+// more than one kernel uses are the helpers of rsf_kernel_common.h.)
 template <int MAXR>
 struct RankSelect {
   uint32_t hist[MAXR][256];

@@ -287,6 +287,7 @@ int rsf_mcmc_adapt(int32_t d, int32_t n, const double *window, int32_t adapt_mod
   HIP_TRY(hipMalloc(&dev, wb + sizeof h));
   hipError_t e = hipMemcpy(dev + 10, window, wb, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
+    // no ctx: the null stream, so not rsfh::launch; the copy that follows reports a failure
     hipLaunchKernelGGL(probe_adapt_kernel, dim3(1), dim3(64), 0, nullptr, (int)d, (int)n, (const double *)(dev + 10), (int)adapt_mode,
                        2.38 * 2.38 / (double)(prior_len > 0 ? prior_len : 2), dev);
     e = hipMemcpy(h, dev, sizeof h, hipMemcpyDeviceToHost);
