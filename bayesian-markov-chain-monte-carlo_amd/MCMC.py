@@ -19,6 +19,8 @@ on the device inside the fused kernel; for any other model the host calls `model
 reference would and the device runs the chain step on the sum of squares it is handed
 (rsf_mcmc_init_state / rsf_mcmc_propose / rsf_mcmc_replay_ssq).
 """
+import contextlib
+
 import numpy as np
 
 if __package__:
@@ -29,6 +31,16 @@ else:  # flat layout: this directory on sys.path, the reference's own import sty
     import _figures
     from _abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
     from engine import Engine, _host, bayes_factor  # noqa: F401
+
+
+@contextlib.contextmanager
+def _engine_for(engine, model=None, substeps=None):
+    """`engine`, or a host-memory Engine made for the block and closed after it; `model` is set on whichever it is, with
+    `substeps` RK4 steps per output interval (by default the model's own)."""
+    with Engine(mem="host") if engine is None else contextlib.nullcontext(engine) as eng:
+        if model is not None:
+            eng.set_model(model, int(getattr(model, "substeps", 1) if substeps is None else substeps))
+        yield eng
 
 
 class PosteriorPool:
@@ -46,17 +58,13 @@ class PosteriorPool:
         """Split R-hat, nested R-hat and multi-chain ESS of the kept draws, computed on the GPU (Engine.diagnostics) → one dict
         per parameter.  Nested R-hat uses superchains of `superchain_size` chains, by default the sampler's own."""
         S = self.superchain_size if superchain_size is None else superchain_size
-        if engine is not None:
-            return engine.diagnostics(self.samples, superchain_size=S, **kw)
-        with Engine(mem="host") as eng:
+        with _engine_for(engine) as eng:
             return eng.diagnostics(self.samples, superchain_size=S, **kw)
 
     def rank_diagnostics(self, engine=None, **kw):
         """Rank-normalised R-hat, bulk and tail ESS, median, quantiles and HDI of the kept draws, computed on the GPU
         (Engine.rank_diagnostics) → one dict per parameter.  Ranks are global: a multi-rank pool is gathered first."""
-        if engine is not None:
-            return engine.rank_diagnostics(self.samples, **kw)
-        with Engine(mem="host") as eng:
+        with _engine_for(engine) as eng:
             return eng.rank_diagnostics(self.samples, **kw)
 
     def loo(self, model, data, max_draws=None, engine=None, substeps=None, r_eff=1.0):
@@ -79,31 +87,23 @@ class PosteriorPool:
         outside it when the posterior is tight.  noise_probs (each strictly inside (0, 1)) adds `noise_quantiles`, the posterior
         predictive band of an observation — the quantiles of mean_i N(y_ik, std2_i) — which is the band to overlay on the data."""
         n, C, d = self.samples.shape
-        q = np.asarray(self.samples.cpu() if hasattr(self.samples, "cpu") else self.samples, dtype=np.float64).reshape(n * C, d)
-        s2 = np.asarray(self.std2.cpu() if hasattr(self.std2, "cpu") else self.std2, dtype=np.float64).reshape(n * C)
+        q, s2 = _host(self.samples).reshape(n * C, d), _host(self.std2).reshape(n * C)
         if max_draws is not None:
             if int(max_draws) < 1:
                 raise ValueError("max_draws must be >= 1")
             if int(max_draws) < n * C:
                 idx = (np.arange(int(max_draws), dtype=np.int64) * (n * C)) // int(max_draws)  # evenly strided, no RNG
                 q, s2 = q[idx], s2[idx]
-        S = int(getattr(model, "substeps", 1) if substeps is None else substeps)
         extra = dict(loo=True, r_eff=r_eff) if loo else {}  # without loo or noise_probs the engine is called as it always was
         if np.size(noise_probs):
             extra["noise_probs"] = noise_probs
-        if engine is not None:
-            engine.set_model(model, S)
-            return engine.predictive(q, s2, data, probs=probs, **extra)
-        with Engine(mem="host") as eng:
-            eng.set_model(model, S)
+        with _engine_for(engine, model, substeps) as eng:
             return eng.predictive(q, s2, data, probs=probs, **extra)
 
     def joint(self, engine=None):
         """Mean, covariance (ddof = 1) and correlation matrix of the kept draws over all parameters, computed on the GPU
         (Engine.pool_joint) → dict(n, nonfinite, mean (d,), cov (d, d), corr (d, d))."""
-        if engine is not None:
-            return engine.pool_joint(self.samples)
-        with Engine(mem="host") as eng:
+        with _engine_for(engine) as eng:
             return eng.pool_joint(self.samples)
 
     def corner(self, nbins=40, grid=32, probs=(0.5, 0.9), ranges=None, engine=None):
@@ -115,27 +115,25 @@ class PosteriorPool:
         x (grid,), y (grid,) and density (grid, grid) — density[k, l] at (x[k], y[l]), the 2-D Gaussian KDE — and levels, the
         highest-density contour levels of `counts` at `probs`)} for i < j.
         ranges: (d, 2) of (lo, hi) per parameter; by default each parameter's min and max, so that every draw is counted."""
-        if engine is None:
-            with Engine(mem="host") as eng:
-                return self.corner(nbins, grid, probs, ranges, eng)
         x = self.samples
         d, nbins, grid = int(x.shape[-1]), int(nbins), int(grid)
-        if ranges is None:
-            ranges = [(s["min"], s["max"]) for s in (engine.pool_summary(x, p) for p in range(d))]
-        ranges = np.asarray(ranges, dtype=np.float64).reshape(d, 2)
-        axes = [np.linspace(lo, hi, grid) for lo, hi in ranges]
-        edges = [np.linspace(lo, hi, nbins + 1) for lo, hi in ranges]
-        res = {"joint": engine.pool_joint(x), "ranges": ranges, "probs": np.asarray(probs, dtype=np.float64), "marginals": [], "pairs": {}}
-        for p in range(d):
-            res["marginals"].append({"counts": _host(engine.pool_histogram(x, nbins, ranges[p, 0], ranges[p, 1], param=p))[1:-1],
-                                     "edges": edges[p], "grid": axes[p], "density": _host(engine.pool_kde(x, axes[p], param=p))})
-        for i in range(d):
-            for j in range(i + 1, d):
-                counts = _host(engine.pool_histogram2d(x, nbins, (ranges[i], ranges[j]), params=(i, j)))[1:-1, 1:-1]
-                mesh = np.stack(np.meshgrid(axes[i], axes[j], indexing="ij"), axis=-1).reshape(grid * grid, 2)
-                res["pairs"][i, j] = {"counts": counts, "xedges": edges[i], "yedges": edges[j], "x": axes[i], "y": axes[j],
-                                      "density": _host(engine.pool_kde2d(x, mesh, params=(i, j))).reshape(grid, grid),
-                                      "levels": engine.pool_hpd_levels(counts, probs)}
+        with _engine_for(engine) as eng:
+            if ranges is None:
+                ranges = [(s["min"], s["max"]) for s in (eng.pool_summary(x, p) for p in range(d))]
+            ranges = np.asarray(ranges, dtype=np.float64).reshape(d, 2)
+            axes = [np.linspace(lo, hi, grid) for lo, hi in ranges]
+            edges = [np.linspace(lo, hi, nbins + 1) for lo, hi in ranges]
+            res = {"joint": eng.pool_joint(x), "ranges": ranges, "probs": np.asarray(probs, dtype=np.float64), "marginals": [], "pairs": {}}
+            for p in range(d):
+                res["marginals"].append({"counts": _host(eng.pool_histogram(x, nbins, ranges[p, 0], ranges[p, 1], param=p))[1:-1],
+                                         "edges": edges[p], "grid": axes[p], "density": _host(eng.pool_kde(x, axes[p], param=p))})
+            for i in range(d):
+                for j in range(i + 1, d):
+                    counts = _host(eng.pool_histogram2d(x, nbins, (ranges[i], ranges[j]), params=(i, j)))[1:-1, 1:-1]
+                    mesh = np.stack(np.meshgrid(axes[i], axes[j], indexing="ij"), axis=-1).reshape(grid * grid, 2)
+                    res["pairs"][i, j] = {"counts": counts, "xedges": edges[i], "yedges": edges[j], "x": axes[i], "y": axes[j],
+                                          "density": _host(eng.pool_kde2d(x, mesh, params=(i, j))).reshape(grid, grid),
+                                          "levels": eng.pool_hpd_levels(counts, probs)}
         return res
 
     def evidence(self, model, data, lo, hi, transform=None, engine=None, substeps=None, **kw):
@@ -145,12 +143,7 @@ class PosteriorPool:
         set compare with bayes_factor.  transform: per parameter "identity" or "log" (log needs lo > 0); by default the identity
         for every parameter, also for (Dc, a, b): measured on the two fits of DESIGN.md 4g, log on (Dc, a) brings no more proposal
         draws into the box (0.977 both) and an re of 5.9e-3 against 6.8e-3, and it would refuse the usual box, whose Dc starts at 0."""
-        S = int(getattr(model, "substeps", 1) if substeps is None else substeps)
-        if engine is not None:
-            engine.set_model(model, S)
-            return engine.evidence(self.samples, data, lo, hi, transform=transform, **kw)
-        with Engine(mem="host") as eng:
-            eng.set_model(model, S)
+        with _engine_for(engine, model, substeps) as eng:
             return eng.evidence(self.samples, data, lo, hi, transform=transform, **kw)
 
     def pooled(self):

@@ -94,51 +94,49 @@ def allreduce_summary(local, group=None, device=None):
     return dict(n=N, mean=gmean, var=float(m2[0]) / (N - 1.0) if N > 1 else 0.0, min=float(lo[0]), max=float(hi[0]))
 
 
-def allreduce_histogram(counts, group=None, device=None):
-    """Summary path: per-rank `Engine.pool_histogram` counts (exact integers in float64) → the histogram of the union of all
-    ranks' draws, one all-reduce of nbins + 2 doubles (RCCL with backend "nccl", gloo in the CPU test-suite)."""
+def allreduce_sum(buf, group=None, device=None):
+    """One all-reduce SUM over the ranks of a float64 buffer (a tensor or array-like; on `device` if given) → a new tensor."""
     import torch
     import torch.distributed as dist
 
-    t = counts.clone() if isinstance(counts, torch.Tensor) else torch.as_tensor(np.array(counts, dtype=np.float64))
+    t = buf.clone() if isinstance(buf, torch.Tensor) else torch.as_tensor(np.array(buf, dtype=np.float64))
     if device is not None:
         t = t.to(device)
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     return t
+
+
+def allreduce_histogram(counts, group=None, device=None):
+    """Summary path: per-rank `Engine.pool_histogram` counts (exact integers in float64) → the histogram of the union of all
+    ranks' draws, one all-reduce of nbins + 2 doubles (RCCL with backend "nccl", gloo in the CPU test-suite)."""
+    return allreduce_sum(counts, group=group, device=device)
 
 
 def allreduce_diag_partials(partials, group=None, device=None):
     """Per-rank `Engine.diag_partials` (every rank's contiguous block of global chain ids, the same centre and lags, no
     superchain across two ranks) → the partials of all ranks' chains: one all-reduce SUM of d * (DIAG_HEAD + L) doubles.
     Feed the result to `Engine.diag_finish`."""
-    import torch
-    import torch.distributed as dist
-
-    t = partials.clone() if isinstance(partials, torch.Tensor) else torch.as_tensor(np.array(partials, dtype=np.float64))
-    if device is not None:
-        t = t.to(device)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-    return t
+    return allreduce_sum(partials, group=group, device=device)
 
 
 def allreduce_predictive_partials(partials, group=None, device=None):
     """Per-rank `Engine.predictive_partials` (every rank's own shard of the pooled draws, the same centres) → the partials of
     all ranks' draws: one all-reduce SUM of PREDICT_HEAD + nout * len(PREDICT_FIELDS) doubles.  Feed the result to
     `Engine.predictive_finish`."""
-    return allreduce_diag_partials(partials, group=group, device=device)
+    return allreduce_sum(partials, group=group, device=device)
 
 
 def allreduce_joint_partials(partials, group=None, device=None):
     """Per-rank `Engine.pool_joint_partials` (every rank's own shard of the pooled draws, the same centre) → the partials of all
     ranks' draws: one all-reduce SUM of JOINT_HEAD + d + d (d + 1) / 2 doubles.  Feed the result to `Engine.pool_joint_finish`."""
-    return allreduce_diag_partials(partials, group=group, device=device)
+    return allreduce_sum(partials, group=group, device=device)
 
 
 def allreduce_evidence_partials(partials, group=None, device=None):
     """Per-rank `Engine.evidence_partials` (every rank's own shard of l1 and l2, with the POOL's s1, s2 and the same lstar and r) →
     the partials of all ranks' draws: one all-reduce SUM of len(EVIDENCE_PARTIALS) doubles.  Feed the result to
     `Engine.evidence_finish`."""
-    return allreduce_diag_partials(partials, group=group, device=device)
+    return allreduce_sum(partials, group=group, device=device)
 
 
 def pool_to_chain_major(pool):

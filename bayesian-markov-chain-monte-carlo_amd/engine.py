@@ -9,6 +9,7 @@ The class is library-agnostic (`lib` is any handle typed by _abi.bind) so the te
 drive the CPU oracle through the very same code; the product always passes _abi.load().
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -29,6 +30,37 @@ def _dp(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+def _i32p(a):
+    """The int32_t* of an int32 NumPy array."""
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def _vec(x, d, what):
+    """x, a scalar or d values, as a contiguous float64 (d,)."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.shape not in ((), (1,), (d,)):
+        raise ValueError(f"{what} has shape {x.shape}: a scalar or {d} values")
+    return np.ascontiguousarray(np.broadcast_to(x, (d,)))
+
+
+def _probs(p, open_interval, allow_empty, what):
+    """Probabilities as a contiguous 1-D float64 array, in [0, 1] or with open_interval in (0, 1); None leaves the range to the library."""
+    p = np.ascontiguousarray(np.atleast_1d(np.asarray(p, dtype=np.float64)))
+    if p.ndim != 1 or not (p.size or allow_empty):
+        raise ValueError(f"{what} is a {'' if allow_empty else 'non-empty '}sequence of probabilities")
+    if open_interval is not None and not np.all((p > 0.0) & (p < 1.0) if open_interval else (p >= 0.0) & (p <= 1.0)):
+        raise ValueError(f"{what}: probabilities lie {'strictly inside (0, 1)' if open_interval else 'in [0, 1]'}")
+    return p
+
+
+def _batched_probs(probs, rows, call):
+    """call(pj, oj) fills the block oj (len(pj), rows) of the result (len(probs), rows), at most PREDICT_MAX_PROBS probabilities at a time."""
+    out = np.empty((probs.size, rows))
+    for j in range(0, probs.size, _abi.PREDICT_MAX_PROBS):
+        call(probs[j:j + _abi.PREDICT_MAX_PROBS], out[j:j + _abi.PREDICT_MAX_PROBS])
+    return out
+
+
 def _rows_totals(out, tot, row_names, total_names):
     """Per-row columns of out as arrays and the totals as floats, by name."""
     res = {name: np.ascontiguousarray(out[:, j]) for j, name in enumerate(row_names)}
@@ -36,11 +68,16 @@ def _rows_totals(out, tot, row_names, total_names):
     return res
 
 
-def _series_shape(x):
-    """(rows, n) of a materialised series (nout, n)."""
+def _series_args(x, std2=None, data=None):
+    """(rows, n) of a materialised series (nout, n), whose draws' std2 is (n,) and whose observation is (rows,)."""
     if x.ndim != 2 or int(x.shape[0]) < 1 or int(x.shape[1]) < 1:
         raise ValueError("a series is (nout, n)")
-    return int(x.shape[0]), int(x.shape[1])
+    rows, n = int(x.shape[0]), int(x.shape[1])
+    if std2 is not None and (std2.ndim != 1 or int(std2.shape[0]) != n):
+        raise ValueError(f"std2 has shape {tuple(std2.shape)}, the series has {n} draws")
+    if data is not None and (data.ndim != 1 or int(data.shape[0]) != rows):
+        raise ValueError(f"data has shape {tuple(data.shape)}, the series has {rows} rows")
+    return rows, n
 
 
 def _lag_blocks(N, lag_block, partials, finish, complete):
@@ -238,7 +275,7 @@ class Engine:
 
     def _mcmc_config(self, C, d, lo, hi, seed=0, chain_offset=0, n0=0.01, prior_len=0, adapt_mode="none", adapt_interval=10,
                      fd_rel_step=1e-6, n_groups=1):
-        lo, hi = np.broadcast_to(np.asarray(lo, dtype=np.float64), (d,)), np.broadcast_to(np.asarray(hi, dtype=np.float64), (d,))
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
         cfg = _abi.McmcConfig()
         cfg.size = ctypes.sizeof(_abi.McmcConfig)
         cfg.n_params, cfg.n_chains, cfg.chain_offset = d, C, int(chain_offset)
@@ -275,10 +312,20 @@ class Engine:
         _abi.check(self.lib, self.lib.rsf_mcmc_propose(self._ctx, self._ptr(z), self._ptr(qn), self._ptr(inb)))
         return qn, inb
 
+    def _replay_args(self, z, u, g, ssq_new=None):
+        """The variates of n = u.shape[0] iterations in this engine's memory space, each of the size the library reads."""
+        self._need_chains()
+        C, d = self.n_chains, self.n_params
+        z, u, g, ssq_new = self._in(z), self._in(u), self._in(g), self._in(ssq_new)
+        n = int(u.shape[0])
+        for name, x, per in (("z", z, C * d), ("u", u, C), ("g", g, C), ("ssq_new", ssq_new, C)):
+            if x is not None and math.prod(x.shape) != n * per:
+                raise ValueError(f"{name} holds {math.prod(x.shape)} values, not the {n * per} of {n} iterations (u.shape[0]) of {C} chains")
+        return n, z, u, g, ssq_new
+
     def mcmc_replay_ssq(self, z, u, g, ssq_new, traces=True):
         """mcmc_replay with the proposals' sums of squares supplied by the caller (n, C): the chain logic alone."""
-        z, u, g, ssq_new = self._in(z), self._in(u), self._in(g), self._in(ssq_new)
-        n_iters = int(u.shape[0])
+        n_iters, z, u, g, ssq_new = self._replay_args(z, u, g, ssq_new)
         tq, ts, ta = self._traces(n_iters, traces)
         _abi.check(self.lib, self.lib.rsf_mcmc_replay_ssq(self._ctx, n_iters, self._ptr(z), self._ptr(u), self._ptr(g), self._ptr(ssq_new),
                                                           self._ptr(tq), self._ptr(ts), self._ptr(ta)))
@@ -313,8 +360,8 @@ class Engine:
         return tq, ts, ta
 
     def mcmc_replay(self, z, u, g, traces=True):
-        z, u, g = self._in(z), self._in(u), self._in(g)
-        n_iters = int(u.shape[0])
+        """n = u.shape[0] iterations on the caller's variates: normals z (n, C, d), uniforms u (n, C), gamma variates g (n, C)."""
+        n_iters, z, u, g, _ = self._replay_args(z, u, g)
         tq, ts, ta = self._traces(n_iters, traces)
         _abi.check(self.lib, self.lib.rsf_mcmc_replay(self._ctx, n_iters, self._ptr(z), self._ptr(u), self._ptr(g),
                                                       self._ptr(tq), self._ptr(ts), self._ptr(ta)))
@@ -336,27 +383,28 @@ class Engine:
         return c
 
     # -- posterior post-processing (RSF.plot_dist, RSF.py:717-746) -------------------------
-    def _column(self, samples, param):
-        """samples: (n,) or trace block (..., d) in this engine's memory space → (array, n, stride)."""
+    def _block(self, samples, param=0):
+        """samples: (n,) or a trace block (..., d) in this engine's memory space, `param` one of its columns → (array, n, d)."""
         x = self._in(samples)
         d = int(x.shape[-1]) if x.ndim > 1 else 1
-        n = int(np.prod(x.shape)) // d
-        return x, n, d, int(param)
+        if not 0 <= int(param) < d:
+            raise ValueError(f"param = {param!r}: a column index in [0, {d})")
+        return x, int(np.prod(x.shape)) // d, d
 
     def pool_summary(self, samples, param=0):
         """→ dict(n, mean, var (ddof=1), min, max) of parameter `param` over all pooled draws."""
-        x, n, d, p = self._column(samples, param)
+        x, n, d = self._block(samples, param)
         out = (ctypes.c_double * 5)()
-        _abi.check(self.lib, self.lib.rsf_pool_summary(self._ctx, n, self._ptr(x) + 8 * p, d, out))
+        _abi.check(self.lib, self.lib.rsf_pool_summary(self._ctx, n, self._ptr(x) + 8 * int(param), d, out))
         return dict(zip(("n", "mean", "var", "min", "max"), list(out)))
 
     def pool_kde(self, samples, grid, param=0, bw_factor=0.0):
         """scipy.stats.gaussian_kde(samples).pdf(grid) (Scott bandwidth unless bw_factor > 0) → density[m]."""
-        x, n, d, p = self._column(samples, param)
+        x, n, d = self._block(samples, param)
         grid = self._in(grid)
         m = int(grid.shape[0])
         dens = self._empty((m,))
-        _abi.check(self.lib, self.lib.rsf_pool_kde(self._ctx, n, self._ptr(x) + 8 * p, d, m, self._ptr(grid), float(bw_factor),
+        _abi.check(self.lib, self.lib.rsf_pool_kde(self._ctx, n, self._ptr(x) + 8 * int(param), d, m, self._ptr(grid), float(bw_factor),
                                                    self._ptr(dens)))
         return dens
 
@@ -364,19 +412,13 @@ class Engine:
         """numpy.histogram(samples, nbins, (lo, hi)) of parameter `param` over all pooled draws, plus the out-of-range counts:
         → counts[nbins + 2] (float64 holding exact integers): [below lo, bin 0 .. bin nbins-1, above hi or NaN].  The summary path
         of SURVEY §8e: a few KB per rank, summed across ranks with pool_allreduce_sum / dist.allreduce_histogram."""
-        x, n, d, p = self._column(samples, param)
+        x, n, d = self._block(samples, param)
         counts = self._empty((int(nbins) + 2,))
-        _abi.check(self.lib, self.lib.rsf_pool_histogram(self._ctx, n, self._ptr(x) + 8 * p, d, int(nbins), float(lo), float(hi),
+        _abi.check(self.lib, self.lib.rsf_pool_histogram(self._ctx, n, self._ptr(x) + 8 * int(param), d, int(nbins), float(lo), float(hi),
                                                          self._ptr(counts)))
         return counts
 
     # -- the joint posterior of the pooled draws (include/rsf_joint.h) ---------------------------
-    def _block(self, samples):
-        """samples: (n,) or a trace block (..., d) in this engine's memory space → (array, n, d)."""
-        x = self._in(samples)
-        d = int(x.shape[-1]) if x.ndim > 1 else 1
-        return x, int(np.prod(x.shape)) // d, d
-
     @staticmethod
     def _pair(params, d):
         pa, pb = (int(p) for p in params)
@@ -461,8 +503,8 @@ class Engine:
         a regular grid; any shape) and probabilities strictly inside (0, 1) → levels[len(probs)]: levels[k] is the largest of
         the weights w for which the weights >= w hold at least probs[k] of the total."""
         w = _host(weights).reshape(-1)
-        p = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-        if p.ndim != 1 or p.size < 1 or w.size < 1:
+        p = _probs(probs, None, False, "probs")  # the range is the library's to refuse
+        if w.size < 1:
             raise ValueError("weights and probs are non-empty")
         out = np.empty(p.size)
         _abi.check(self.lib, self.lib.rsf_pool_hpd_levels(int(w.size), _dp(w), int(p.size), _dp(p), _dp(out)))
@@ -491,23 +533,17 @@ class Engine:
             raise ValueError(f"mean is (d,) and chol (d, d) with 1 <= d <= {_abi.EVIDENCE_MAX_PARAMS}")
         return m, L, d
 
-    @staticmethod
-    def _ev_box(lo, hi, d):
-        return (np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (d,))),
-                np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (d,))))
-
     def evidence_propose(self, mean, chol, lo, hi, n2, transform=None, seed=0, offset=0):
         """rsf_evidence_propose: n2 draws of the Gaussian proposal N(mean, chol chol^T) in the working coordinates (phi_p = q_p, or
         log q_p where transform[p] is "log") → (theta (n2, d) in natural coordinates, logg (n2,), inbox (n2,) uint8) in this
         engine's memory space.  Draw j uses the normals of draws(seed, offset + j, 0, d): shards with offsets form one stream."""
         m, L, d = self._ev_gauss(mean, chol)
         tr = self._ev_flags(transform, d)
-        lo, hi = self._ev_box(lo, hi, d)
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
         n2 = int(n2)
         theta, logg, inbox = self._empty((max(n2, 0), d)), self._empty((max(n2, 0),)), self._empty((max(n2, 0),), np.uint8)
-        _abi.check(self.lib, self.lib.rsf_evidence_propose(self._ctx, n2, d, _dp(m), _dp(L), tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                           _dp(lo), _dp(hi), int(seed), int(offset), self._ptr(theta), self._ptr(logg),
-                                                           self._ptr(inbox)))
+        _abi.check(self.lib, self.lib.rsf_evidence_propose(self._ctx, n2, d, _dp(m), _dp(L), _i32p(tr), _dp(lo), _dp(hi), int(seed),
+                                                           int(offset), self._ptr(theta), self._ptr(logg), self._ptr(inbox)))
         return theta, logg, inbox
 
     def evidence_logg(self, theta, mean, chol, transform=None):
@@ -519,8 +555,7 @@ class Engine:
         if int(np.prod(x.shape)) != n * d:
             raise ValueError(f"theta is (n, {d})")
         logg = self._empty((n,))
-        _abi.check(self.lib, self.lib.rsf_evidence_logg(self._ctx, n, d, self._ptr(x), _dp(m), _dp(L),
-                                                        tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._ptr(logg)))
+        _abi.check(self.lib, self.lib.rsf_evidence_logg(self._ctx, n, d, self._ptr(x), _dp(m), _dp(L), _i32p(tr), self._ptr(logg)))
         return logg
 
     def evidence_logtarget(self, theta, data, lo, hi, logg, shape=None, transform=None):
@@ -537,11 +572,11 @@ class Engine:
         if obs.ndim != 1 or int(obs.shape[0]) != self.nout:
             raise ValueError(f"data has shape {tuple(obs.shape)}, the model produces {self.nout} samples")
         tr = self._ev_flags(transform, d)
-        lo, hi = self._ev_box(lo, hi, d)
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
         l = self._empty((n,))
         _abi.check(self.lib, self.lib.rsf_evidence_logtarget(self._ctx, n, d, self._ptr(x), self._ptr(obs),
                                                              float(0.5 * self.nout if shape is None else shape), _dp(lo), _dp(hi),
-                                                             tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._ptr(g), self._ptr(l)))
+                                                             _i32p(tr), self._ptr(g), self._ptr(l)))
         return l
 
     def evidence_partials(self, l1, l2, lstar, r, s1=None, s2=None):
@@ -568,7 +603,7 @@ class Engine:
             raise ValueError(f"{part.size} partials, not {len(_abi.EVIDENCE_PARTIALS)}")
         full = shape is not None and lo is not None and hi is not None
         d = int(np.size(lo)) if full else 0
-        lo, hi = self._ev_box(lo, hi, d) if full else (None, None)
+        lo, hi = (_vec(lo, d, "lo"), _vec(hi, d, "hi")) if full else (None, None)
         out = np.empty(len(_abi.EVIDENCE_OUT))
         _abi.check(self.lib, self.lib.rsf_evidence_finish(_dp(part), float(r), float(lstar), float(ess_factor), float(shape) if full else 1.0,
                                                           d, _dp(lo) if full else None, _dp(hi) if full else None, _dp(out)))
@@ -617,7 +652,7 @@ class Engine:
         if not 0.0 < float(fit_fraction) < 1.0 or k < d + 1 or rows - k < 1:
             raise ValueError(f"fit_fraction = {fit_fraction!r} leaves {k} rows to fit the proposal and {rows - k} for the estimator")
         tr = self._ev_flags(transform, d)
-        lo, hi = self._ev_box(lo, hi, d)
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
         fit, est = x[:k].reshape(-1, d), x[k:].reshape(-1, d)
         n1 = int(est.shape[0])
         # the proposal's moments: pool_joint of the first part in the working coordinates
@@ -668,7 +703,7 @@ class Engine:
         shape = float(shape)
         d = int(np.shape(samples)[-1]) if np.ndim(samples) > 1 else 1
         tr = self._ev_flags(transform, d)
-        blo, bhi = self._ev_box(lo, hi, d)
+        blo, bhi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
 
         def ltarget(theta, logg):
             q, g = _host(theta).reshape(-1, d), _host(logg).reshape(-1)
@@ -696,9 +731,8 @@ class Engine:
     @staticmethod
     def _diag_center(x, d, center):
         if center is None:  # the trace's first draw of chain 0
-            first = x[0, 0]
-            return _host(first).reshape(d)
-        return np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), (d,)))
+            return _host(x[0, 0]).reshape(d)
+        return _vec(center, d, "center")
 
     def diag_partials(self, trace, superchain_size=None, center=None, lag_begin=0, lag_end=None):
         """rsf_diag_partials: the additive partials of the trace (n, C[, d]) about `center` (default: the first draw of chain 0)
@@ -722,7 +756,7 @@ class Engine:
         n_lags = int(part.shape[1]) - _abi.DIAG_HEAD if n_lags is None else int(n_lags)
         if part.shape[1] != _abi.DIAG_HEAD + n_lags:
             raise ValueError(f"partials have {part.shape[1] - _abi.DIAG_HEAD} lags, not n_lags = {n_lags}")
-        c = np.ascontiguousarray(np.broadcast_to(np.asarray(center, dtype=np.float64), (d,)))
+        c = _vec(center, d, "center")
         out = np.empty((d, len(_abi.DIAG_OUT)))
         _abi.check(self.lib, self.lib.rsf_diag_finish(int(n_iters), d, int(superchain_size or 0), _dp(c),
                                                       _dp(part), n_lags, _dp(out)))
@@ -894,21 +928,11 @@ class Engine:
     def predictive_quantiles(self, series, probs):
         """rsf_predict_quantiles: np.quantile(series, probs, axis=1) (method "linear", exact) of a series (nout, n) in this
         engine's memory space → (len(probs), nout) float64 on the host."""
-        probs = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-        if probs.ndim != 1 or probs.size < 1:
-            raise ValueError("probs is a non-empty sequence of probabilities")
-        if not np.all((probs >= 0.0) & (probs <= 1.0)):
-            raise ValueError("probabilities lie in [0, 1]")
+        probs = _probs(probs, False, False, "probs")
         x = self._in(series)
-        rows, n = _series_shape(x)
-        out = np.empty((probs.size, rows))
-        for j in range(0, probs.size, _abi.PREDICT_MAX_PROBS):
-            pj = np.ascontiguousarray(probs[j:j + _abi.PREDICT_MAX_PROBS])
-            oj = np.empty((pj.size, rows))
-            _abi.check(self.lib, self.lib.rsf_predict_quantiles(self._ctx, n, rows, self._ptr(x), int(pj.size), _dp(pj),
-                                                                _dp(oj)))
-            out[j:j + pj.size] = oj
-        return out
+        rows, n = _series_args(x)
+        return _batched_probs(probs, rows, lambda pj, oj: _abi.check(self.lib, self.lib.rsf_predict_quantiles(
+            self._ctx, n, rows, self._ptr(x), int(pj.size), _dp(pj), _dp(oj))))
 
     def psis_loo(self, series, std2, data, lpd, r_eff=1.0):
         """rsf_predict_psis_loo and rsf_predict_psis_finish: PSIS-LOO of a series (nout, n) in this engine's memory space (as
@@ -920,11 +944,7 @@ class Engine:
         std2 is equal — has pareto_k = +inf and is not smoothed (ArviZ's behaviour).  Ranks of the tail are global over the
         draws: nothing here is additive over shards, a multi-rank pool is gathered first."""
         x, s2, obs = self._in(series), self._in(std2), self._in(data)
-        rows, n = _series_shape(x)
-        if s2.ndim != 1 or int(s2.shape[0]) != n:
-            raise ValueError(f"std2 has shape {tuple(s2.shape)}, the series has {n} draws")
-        if obs.ndim != 1 or int(obs.shape[0]) != rows:
-            raise ValueError(f"data has shape {tuple(obs.shape)}, the series has {rows} rows")
+        rows, n = _series_args(x, s2, obs)
         lpd = _host(lpd)
         if lpd.shape != (rows,):
             raise ValueError(f"lpd has shape {lpd.shape}, the series has {rows} rows")
@@ -950,25 +970,18 @@ class Engine:
         Probabilities lie strictly inside (0, 1).  return_passes: also the passes the kernel made over each row (nout,) int32,
         at most PREDICT_NOISE_MAX_PASSES (the largest over the batches of PREDICT_MAX_PROBS probabilities).  A probability's
         result does not depend on which others are asked with it.  F is a mean over all draws: a multi-rank pool is gathered first."""
-        probs = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
-        if probs.ndim != 1 or probs.size < 1:
-            raise ValueError("probs is a non-empty sequence of probabilities")
-        if not np.all((probs > 0.0) & (probs < 1.0)):
-            raise ValueError("probabilities lie strictly inside (0, 1)")
+        probs = _probs(probs, True, False, "probs")
         x, s2 = self._in(series), self._in(std2)
-        rows, n = _series_shape(x)
-        if s2.ndim != 1 or int(s2.shape[0]) != n:
-            raise ValueError(f"std2 has shape {tuple(s2.shape)}, the series has {n} draws")
-        out = np.empty((probs.size, rows))
+        rows, n = _series_args(x, s2)
         passes = np.zeros(rows, dtype=np.int32)
-        for j in range(0, probs.size, _abi.PREDICT_MAX_PROBS):
-            pj = np.ascontiguousarray(probs[j:j + _abi.PREDICT_MAX_PROBS])
-            oj = np.empty((pj.size, rows))
+
+        def call(pj, oj):
             ps = np.empty(rows, dtype=np.int32)
             _abi.check(self.lib, self.lib.rsf_predict_noise_quantiles(self._ctx, n, rows, self._ptr(x), self._ptr(s2), int(pj.size), _dp(pj),
-                                                                      _dp(oj), ps.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
-            out[j:j + pj.size] = oj
+                                                                      _dp(oj), _i32p(ps)))
             np.maximum(passes, ps, out=passes)
+
+        out = _batched_probs(probs, rows, call)
         return (out, passes) if return_passes else out
 
     def predictive(self, q, std2, data, probs=(), center=None, return_series=False, loo=False, r_eff=1.0, noise_probs=()):
@@ -984,12 +997,7 @@ class Engine:
         PREDICTIVE band — where an observation lies, the inferred noise included: the one to overlay on the data.  A non-empty
         noise_probs materialises the series and adds the keys noise_probs and noise_quantiles; the default adds nothing."""
         q, std2, data, n, d = self._predict_args(q, std2, data)
-        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
-        if probs.ndim != 1 or not np.all((probs >= 0.0) & (probs <= 1.0)):
-            raise ValueError("probs is a sequence of probabilities in [0, 1]")
-        noise_probs = np.atleast_1d(np.asarray(noise_probs, dtype=np.float64))
-        if noise_probs.ndim != 1 or not np.all((noise_probs > 0.0) & (noise_probs < 1.0)):
-            raise ValueError("noise_probs is a sequence of probabilities strictly inside (0, 1)")
+        probs, noise_probs = _probs(probs, False, True, "probs"), _probs(noise_probs, True, True, "noise_probs")
 
         if center is None:
             qm = _host(q.mean(0)).reshape(d)

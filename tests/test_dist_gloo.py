@@ -62,6 +62,13 @@ def _worker(rank, port, out_dir):
     with pkg.Engine(lib=lib) as e:  # ... and a fixed-bin histogram of the local shard, summed over ranks with one all-reduce
         hist = rdist.allreduce_histogram(e.pool_histogram(pool[:, rank * per:(rank + 1) * per].contiguous().numpy(), 16, 900.0, 1100.0))
     np.save(os.path.join(out_dir, f"hist_{rank}.npy"), hist.numpy())
+    # the five sums of partials are one all-reduce SUM: the same tensor for the same input, and the input left alone
+    part = np.arange(6.0).reshape(2, 3) + rank
+    sums = [getattr(rdist, "allreduce_" + name)(part) for name in ("sum", "histogram", "diag_partials", "predictive_partials",
+                                                                    "joint_partials", "evidence_partials")]
+    for s in sums:
+        np.testing.assert_array_equal(s.numpy(), WORLD * np.arange(6.0).reshape(2, 3) + sum(range(WORLD)))
+    np.testing.assert_array_equal(part, np.arange(6.0).reshape(2, 3) + rank)
     assert stats["iters_done"] == N_ITERS
     dist.barrier()
     dist.destroy_process_group()

@@ -455,3 +455,117 @@ def test_unknown_dc_is_reported_not_sampled(pkg, model, capsys):
     problem.perform_sampling_and_plotting(np.zeros(1000), 777.0, 10, None)
     assert "Error: dc value 777.0 not found in dc_list." in capsys.readouterr().out
     assert problem.posteriors == {}
+
+
+# ---- the Python layer's argument checks (engine.py's helpers), each on its refusing path ----------------------------------
+def _replay_case(engine, oracle_mod, injected):
+    """C = 3 one-parameter chains and the variates of n = 2 iterations: on a 20-step model (mcmc_replay), or injected — from
+    an explicit state, the sums of squares supplied (mcmc_replay_ssq) → the method's arguments (z, u, g[, ssq_new])."""
+    from conftest import synthetic_data
+
+    q0 = np.array([[900.0], [1000.0], [1100.0]])
+    if injected:
+        engine.mcmc_init_state(q0, [2e-3] * 3, [1e-6] * 3, np.full((3, 1, 1), 25.0), [0.0], [1e4], prior_len=3)
+    else:
+        engine.set_model(oracle_mod.ModelSpec(20), 1)
+        engine.mcmc_init(q0, synthetic_data(engine), [0.0], [1e4], seed=1, prior_len=3)
+    rng = np.random.default_rng(3)
+    args = [rng.standard_normal((2, 3, 1)), rng.uniform(size=(2, 3)), rng.gamma(10.0, size=(2, 3))]
+    return args + [rng.uniform(1e-3, 3e-3, (2, 3))] if injected else args
+
+
+@pytest.mark.parametrize("injected", [False, True])
+def test_replay_refuses_arrays_of_the_wrong_size(cpu_engine, oracle_mod, injected):
+    """mcmc_replay / mcmc_replay_ssq take the iteration count from u.shape[0] and hand every array to the library, which reads
+    n C (z: n C d) values of each: any other size is a ValueError naming the array, and nothing has run.  Sizes, not shapes:
+    z as (n, C d) is the same call."""
+    replay = cpu_engine.mcmc_replay_ssq if injected else cpu_engine.mcmc_replay
+    names = ("z", "u", "g", "ssq_new")
+    args = _replay_case(cpu_engine, oracle_mod, injected)
+    for k in (0, 2, 3)[:len(args) - 1]:  # z, g (and ssq_new) one element short
+        bad = list(args)
+        bad[k] = bad[k].ravel()[:-1]
+        with pytest.raises(ValueError, match=rf"^{names[k]} holds {bad[k].size} values, not the {args[k].size} of 2 iterations"):
+            replay(*bad)
+    with pytest.raises(ValueError, match=r"^z holds 9 values, not the 6 of 2 iterations"):  # u says n = 2, z is sized for n = 3
+        replay(np.zeros((3, 3, 1)), *args[1:])
+    with pytest.raises(ValueError, match=r"^u holds 2 values, not the 6 of 2 iterations"):
+        replay(args[0], args[1][:, 0], *args[2:])
+    assert cpu_engine.stats()["iters_done"] == 0
+    first = replay(*args)
+    assert [t.shape for t in first] == [(2, 3, 1), (2, 3), (2, 3)] and cpu_engine.stats()["iters_done"] == 2
+    _replay_case(cpu_engine, oracle_mod, injected)  # the same chains again
+    again = replay(args[0].reshape(2, 3), *args[1:])
+    for a, b in zip(first, again):
+        np.testing.assert_array_equal(a, b)
+    _replay_case(cpu_engine, oracle_mod, injected)  # ... and one iteration per call
+    rows = [replay(*[x[k:k + 1] for x in args]) for k in range(2)]
+    for j, a in enumerate(first):
+        np.testing.assert_array_equal(a, np.concatenate([r[j] for r in rows]))
+
+
+def test_replay_before_mcmc_init_is_refused(pkg, cpu_engine):
+    z, u = np.zeros((1, 1, 1)), np.ones((1, 1))
+    for call in (lambda: cpu_engine.mcmc_replay(z, u, u), lambda: cpu_engine.mcmc_replay_ssq(z, u, u, u)):
+        with pytest.raises(pkg.RsfError) as ex:
+            call()
+        assert ex.value.code == -3
+
+
+def check_param_is_refused_before_the_library(pkg, engine):
+    """param outside [0, d) used to offset the pointer out of the block unchecked.  The engine is closed: an ABI call on its
+    NULL ctx is an RsfError, so a ValueError shows that the check came first."""
+    x = np.arange(16.0).reshape(8, 2)
+    engine.close()
+    for param in (2, -1):
+        for call in (lambda: engine.pool_summary(x, param), lambda: engine.pool_kde(x, [0.0, 1.0], param=param),
+                     lambda: engine.pool_histogram(x, 4, 0.0, 16.0, param=param)):
+            with pytest.raises(ValueError, match=r"^param = -?\d: a column index in \[0, 2\)"):
+                call()
+    with pytest.raises(pkg.RsfError):
+        engine.pool_summary(x, 1)
+
+
+def test_pool_param_outside_the_block_is_refused(pkg, cpu_engine):
+    check_param_is_refused_before_the_library(pkg, cpu_engine)
+
+
+@pytest.mark.gpu
+def test_pool_param_outside_the_block_is_refused_gpu(pkg, gpu_engine):
+    check_param_is_refused_before_the_library(pkg, gpu_engine)
+
+
+def test_probabilities_and_vectors_are_checked_once(pkg):
+    E = pkg.engine
+    for open_interval in (False, True):
+        for bad in (np.nan, -0.1, 1.1):
+            with pytest.raises(ValueError, match="^band: probabilities lie"):
+                E._probs([0.5, bad], open_interval, False, "band")
+        for edge in (0.0, 1.0):
+            if open_interval:
+                with pytest.raises(ValueError, match=r"strictly inside \(0, 1\)"):
+                    E._probs(edge, open_interval, False, "band")
+            else:
+                assert E._probs(edge, open_interval, False, "band").tolist() == [edge]
+        assert E._probs((), open_interval, True, "band").shape == (0,)
+        with pytest.raises(ValueError, match="^band is a non-empty sequence"):
+            E._probs((), open_interval, False, "band")
+        with pytest.raises(ValueError, match="^band is a sequence"):
+            E._probs([[0.5]], open_interval, True, "band")
+    p = E._probs((0.0, np.nan), None, False, "band")  # None: the range is the library's to refuse (pool_hpd_levels)
+    assert p.dtype == np.float64 and p.flags.c_contiguous and p.shape == (2,)
+    v = E._vec(2.5, 3, "lo")
+    assert v.tolist() == [2.5] * 3 and v.flags.c_contiguous and v.flags.writeable and v.dtype == np.float64
+    assert E._vec([1, 2, 3], 3, "lo").tolist() == [1.0, 2.0, 3.0]
+    with pytest.raises(ValueError, match="^hi has shape"):
+        E._vec([1.0, 2.0], 3, "hi")
+    # a series (nout, n) with its draws' std2 (n,) and its observation (nout,)
+    x = np.zeros((4, 5))
+    assert E._series_args(x, np.zeros(5), np.zeros(4)) == (4, 5)
+    for bad, text in (((np.zeros(4),), "a series is"), ((x, np.zeros(4)), "std2 has shape"), ((x, None, np.zeros(5)), "data has shape")):
+        with pytest.raises(ValueError, match=text):
+            E._series_args(*bad)
+    # more probabilities than one call takes: the batches land in their rows
+    seen = []
+    out = E._batched_probs(np.arange(2.0 * pkg._abi.PREDICT_MAX_PROBS + 1), 2, lambda pj, oj: (seen.append(pj.size), oj.__setitem__(..., pj[:, None])))
+    assert seen == [pkg._abi.PREDICT_MAX_PROBS] * 2 + [1] and out[:, 1].tolist() == list(range(2 * pkg._abi.PREDICT_MAX_PROBS + 1))
