@@ -76,6 +76,11 @@ struct Lane {
   double bh;            // beta/hhd: the TIGHT tier carries hhd/x in place of 1/x (rk4_tight)
   double c_l1p, c_l1q;  // series coefficients of the active tier kept in VGPRs (a VOP3 takes one SGPR source and the first Horner
   double c_em1;         //   term has two non-inline constants), see set_tier: b/3a and -b/4a of log1p, expm1's leading coefficient
+  // the in-step sum of squares (rk4_tight, INSTEP): the sample's residual straight from the step's two partial sums, and the
+  // full-step stage fed with the half increment c1 (rho = 2 c1) through doubled constants
+  double cv2;           // 2 cv
+  double boa2;          // 2 b/a     : (b/a) log1p(2 c1) = c1 (2b/a - (2b/a) c1)
+  double bh2, bh4;      // -2 bh, 4 bh: bh (1 - rho + rho^2) = bh + c1 (-2 bh + 4 bh c1)
 };
 
 template <int T>
@@ -113,6 +118,10 @@ __device__ __forceinline__ Lane make_lane(double dc, double a, double b, const C
   L.hdw = DAMP ? L.hd * ikw : L.hd;
   L.nhboa = -0.5 * L.boa;
   L.bh = L.beta * fm::rcp(L.hhd);
+  L.cv2 = 2.0 * L.cv;  // (exact doublings; formed only where an instantiation reads them)
+  L.boa2 = 2.0 * L.boa;
+  L.bh2 = -2.0 * L.bh;
+  L.bh4 = 4.0 * L.bh;
   set_tier<2>(L);
   return L;
 }
@@ -215,6 +224,7 @@ __device__ __forceinline__ void resync_t(State &s, const Lane &L, const Consts &
 struct Guard {
   float rho, dlt;
   float dlt_h;  // TIGHT: |dlt| of the two half-step stages, held to 2^-10 (truncation of their expm1 series < 8e-18)
+  float rho_f;  // INSTEP: |c1| = |rho| / 2 of the full-step stage, held to 2^-21 — the same bound on rho (tight_incr_doubled)
 };
 
 __device__ __forceinline__ float hi_as_float(double x) { return __builtin_bit_cast(float, __double2hiint(x)); }
@@ -305,8 +315,12 @@ __device__ __forceinline__ double rk4_cold(State &s, double vl0, double vlm, dou
 // instructions more per evaluation — and WIDE one and two more again — rho^4/4, dlt^8/40320, ... + rho^4: |rho| < 2^-11,
 // |dlt| < 2^-5 (7e-18, 2.4e-18, 2.8e-17).  (Until round 3 they were an unscaled form with Newton steps on 1/x: 131 and 144
 // instructions per step against 102 and 118, and their a-priori bounds reached less far down in Dc.)
-template <int T, bool HALF>
+// SHORT (the in-step mode's half-step stages, TIGHT): expm1 to dlt^3/6.  Their w is a stage value, not the carried state: at
+// the stage guard's edge, |dlt| = 2^-10, the dropped dlt^4/24 is 3.8e-14 of it, which reaches the step's sample with weight 1/3
+// and the carried state through another factor |dlt|; at the increments of a Dc ~ 1000 chain (|dlt| ~ 1e-4) it is 4e-18.
+template <int T, bool HALF, bool SHORT = false>
 __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L, double w0, double &w, double &q, Guard &g) {
+  static_assert(!SHORT || (T == TIGHT && HALF), "the short series is for TIGHT's half-step stages");
   g.rho = __builtin_fmaxf(g.rho, __builtin_fabsf(hi_as_float(rho)));
   double pb = L.nhboa;  // (b/a)(1 - rho/2 [+ rho^2/3 [- rho^3/4]])
   if (T == NARROW) pb = __builtin_fma(rho, L.c_l1p, pb);
@@ -315,7 +329,7 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
   // TIGHT: expm1 to dlt^4/24 at every stage, half-step stages held to |dlt| < 2^-10, the others to 2^-9
   if (T == TIGHT && HALF) g.dlt_h = __builtin_fmaxf(g.dlt_h, __builtin_fabsf(hi_as_float(dlt)));
   else g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
-  double e = L.c_em1;
+  double e = SHORT ? 1.0 / 6.0 : L.c_em1;
   if (T == WIDE) {
     e = fm::hfma(e, dlt, 1.0 / 5040.0);
     e = fm::hfma(e, dlt, 1.0 / 720.0);
@@ -324,7 +338,7 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
     e = fm::hfma(e, dlt, 1.0 / 120.0);
     e = fm::hfma(e, dlt, 1.0 / 24.0);
   }
-  e = fm::hfma(e, dlt, 1.0 / 6.0);
+  if (!SHORT) e = fm::hfma(e, dlt, 1.0 / 6.0);
   e = __builtin_fma(e, dlt, 0.5);
   e = __builtin_fma(e, dlt, 1.0);
   w = __builtin_fma(w0 * dlt, e, w0);
@@ -332,6 +346,20 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
   q = r1;                                                          // 1/x' = (1/x)(1 + q)
   if (T != TIGHT) q = __builtin_fma(-rho, q, -rho);                // NARROW: -rho + rho^2 - rho^3
   if (T == WIDE) q = __builtin_fma(-rho, q, -rho);                 // WIDE: ... + rho^4
+}
+
+// TIGHT's full-step stage fed with c1 = rho / 2, the previous stage's d1' as it stands (the in-step mode): the doublings are
+// exact, so dlt and w are tight_incr<TIGHT, false>(c1 + c1, ...)'s to the bit; brx = bh (1 + q) comes out of one Horner
+// pass in c1 instead of q and a product (one rounding placed differently), and the sum c1 + c1 is never formed.
+__device__ __forceinline__ void tight_incr_doubled(double c1, double dk, const Lane &L, double w0, double &w, double &brx, Guard &g) {
+  g.rho_f = __builtin_fmaxf(g.rho_f, __builtin_fabsf(hi_as_float(c1)));
+  const double dlt = __builtin_fma(-c1, __builtin_fma(-c1, L.boa2, L.boa2), dk);
+  g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
+  double e = fm::hfma(L.c_em1, dlt, 1.0 / 6.0);
+  e = __builtin_fma(e, dlt, 0.5);
+  e = __builtin_fma(e, dlt, 1.0);
+  w = __builtin_fma(w0 * dlt, e, w0);
+  brx = __builtin_fma(c1, __builtin_fma(c1, L.bh4, L.bh2), L.bh);
 }
 
 // d0 = V_l - V_ref w,  d1' = Rh - w xr  (xr = Rh x at the stage),  g = d0 - brx d1'  (brx = bh (1 + q)) and the damping pass.
@@ -352,21 +380,34 @@ __device__ __forceinline__ void rhs_tight(double w, double xr, double Rh, double
   }
 }
 
-template <bool DAMP, int T>
-__device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, double vl1, const Lane &L, const Consts &K, Guard &g) {
+//
+// INSTEP (TIGHT trips of the sampler, one step per sample: integrate_multi): the step adds its sample's squared residual to
+// *ssq itself (`first`: starts that sum), r = cv sv + (2 cv sm - obs), and returns nothing of use — no per-step sample leaves the step, so a trip keeps
+// neither its samples nor, beyond each step, its observations in registers.  Its half-step stages take the expm1 series
+// one term shorter (tight_incr, SHORT) and its full-step stage the half increment (tight_incr_doubled).
+template <bool DAMP, int T, bool INSTEP = false>
+__device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, double vl1, const Lane &L, const Consts &K, Guard &g,
+                                            double obs = 0.0, double *ssq = nullptr, bool first = false) {
+  static_assert(!INSTEP || T == TIGHT, "the in-step sum of squares is the TIGHT step's");
   double a0, a1, a2, b0, b1, b2, c0, c1, c2, e0, e1, e2, w, q;
   const double Rh = s.rx;
   const double vr = L.vrw, xh = L.hhdw, xf = L.hdw;  // (V_ref, hhd, hd) / kvk with damping: s.w is W (Lane::vrw)
   rhs_tight<DAMP>(s.w, xh, Rh, vl0, L.bh, vr, a0, a1, a2);
   double sv = s.w * a2;  // k1 + k4 of dV/dt (in units of vk, vk/kvk with damping), and k2 + k3 below: 5 instructions for the weighted sum
-  tight_incr<T, true>(a1, L.khh * a0, L, s.w, w, q, g);
+  tight_incr<T, true, INSTEP>(a1, L.khh * a0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, a1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, b0, b1, b2);
   double sm = w * b2;
-  tight_incr<T, true>(b1, L.khh * b0, L, s.w, w, q, g);
+  tight_incr<T, true, INSTEP>(b1, L.khh * b0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, b1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, c0, c1, c2);
   sm = __builtin_fma(w, c2, sm);
-  tight_incr<T, false>(c1 + c1, L.kh * c0, L, s.w, w, q, g);
-  rhs_tight<DAMP>(w, __builtin_fma(xf, c1, xh), Rh, vl1, __builtin_fma(L.bh, q, L.bh), vr, e0, e1, e2);
+  if constexpr (INSTEP) {
+    double brx;
+    tight_incr_doubled(c1, L.kh * c0, L, s.w, w, brx, g);
+    rhs_tight<DAMP>(w, __builtin_fma(xf, c1, xh), Rh, vl1, brx, vr, e0, e1, e2);
+  } else {
+    tight_incr<T, false>(c1 + c1, L.kh * c0, L, s.w, w, q, g);
+    rhs_tight<DAMP>(w, __builtin_fma(xf, c1, xh), Rh, vl1, __builtin_fma(L.bh, q, L.bh), vr, e0, e1, e2);
+  }
   sv = __builtin_fma(w, e2, sv);
   const double t0 = a0 + 2.0 * b0 + 2.0 * c0 + e0;
   const double t1 = a1 + 2.0 * b1 + 2.0 * c1 + e1;
@@ -375,6 +416,11 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
   s.ms = __builtin_fma(K.h6, t0, s.ms);
   s.w = w;
   s.rx = __builtin_fma(Rh, q, Rh);  // x' = x (1 + rho), exact to rounding for |rho| < 2^-20; like w, resynced
+  if constexpr (INSTEP) {
+    const double r = __builtin_fma(sv, L.cv, __builtin_fma(sm, L.cv2, -obs));
+    *ssq = first ? r * r : __builtin_fma(r, r, *ssq);
+    return 0.0;
+  }
   return __builtin_fma(2.0, sm, sv);
 }
 
@@ -458,7 +504,7 @@ __device__ __forceinline__ void emit_sample(double vnow, Emit &em, double obs, c
 // values are then not to be used: the caller restores the state it saved and takes trip_cold.
 template <bool DAMP, int T, int NU>
 __device__ __forceinline__ bool trip_fast(const double *v, const Lane &L, const Consts &K, State &s, double (&dv)[NU], bool *calm = nullptr) {
-  Guard g = {0, 0, 0};
+  Guard g = {0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < NU; ++j) dv[j] = rk4_tight<DAMP, T>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K, g);
   if constexpr (T != TIGHT) {
@@ -477,6 +523,19 @@ __device__ __forceinline__ void trip_cold(const double *v, const Lane &L, const 
     const double r = rk4_cold<DAMP>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K);
 #pragma unroll
     for (int m = 0; m < NU; ++m) dv[m] = m == j ? r : dv[m];
+  }
+  eval_full_t<DAMP, T>(s, L, K);
+}
+
+// the cold trip of the in-step mode (one step per sample, the sum of squares alone): each cold step's sample goes straight into
+// ssq against its observation ob[j], in emit_incr's arithmetic — no dv[] here either
+template <bool DAMP, int T, int NU>
+__device__ __forceinline__ void trip_cold_ssq(const double *v, const double *ob, const Lane &L, const Consts &K, State &s, double &ssq) {
+  tier_x<T>(s, L);
+#pragma unroll 1
+  for (int j = 0; j < NU; ++j) {
+    const double dvs = rk4_cold<DAMP>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K);
+    emit_incr<true, false>(dvs, j, ob[j], L, 0, ssq, false, nullptr, 0);
   }
   eval_full_t<DAMP, T>(s, L, K);
 }
@@ -560,6 +619,19 @@ __device__ __forceinline__ int wave_tier(const Wave &W) {
   return (W.need[2] & W.alive) ? FULL : ((W.need[1] & W.alive) ? WIDE : ((W.need[0] & W.alive) ? NARROW : TIGHT));
 }
 
+// the TIGHT trip with the in-step sum of squares (rk4_tight, INSTEP): step j squares the residual of its sample against obs[j];
+// tsum = the trip's sum of them, from zero, so that the caller's running sum is not touched by a trip whose lane left the
+// guard region (one add per trip, no copy kept for a restore).  Returns the wave's lanes that left it: the guard's compares
+// as ballots, OR-ed as scalars — the same set as ballot(!guard_ok), without forming the per-lane flag.
+template <bool DAMP, int NU>
+__device__ __forceinline__ unsigned long long trip_fast_ssq(const double *v, const double (&obs)[NU], const Lane &L, const Consts &K, State &s,
+                                                            double &tsum) {
+  Guard g = {0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < NU; ++j) rk4_tight<DAMP, TIGHT, true>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K, g, obs[j], &tsum, j == 0);
+  return ballot(!(g.rho < hi_pow2(-20))) | ballot(!(g.rho_f < hi_pow2(-21))) | ballot(!(g.dlt < hi_pow2(-9))) | ballot(!(g.dlt_h < hi_pow2(-10)));
+}
+
 // samples completed by a trip of NU steps starting at chunk step r (dv[j]: the steps' V-derivative sums).  S1: every step
 // is a sample, its observation obs[j] read ahead by the caller; else one every K.S steps (wave-uniform phase counter), V
 // carried, the observation read from LDS where the sample completes (at most one per K.S >= 2 steps: selecting among
@@ -593,18 +665,24 @@ __device__ __forceinline__ void emit_trip(const double (&dv)[NU], const double (
 // compare uses the sum of squares as the PREVIOUS trip left it, so the branch never waits for the trip's last result.
 constexpr int kTightUnroll = 8;  // steps per trip of the TIGHT loop (the one-parameter sampler runs 2 * kTightUnroll, rsf_kernels_sampler.h)
 constexpr int kNarrowUnroll = 8, kWiderUnroll = 4;  // NARROW; WIDE
-template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU>
+// INSTEP (TIGHT trips of a solve that wants the sum of squares alone, one step per sample: integrate_tiers): every step of
+// the fast trip squares its own residual (trip_fast_ssq) — no dv[] exists on the hot path and each observation dies at
+// its step.  The trip's sum joins ssq after the guard branch: the lanes in badmask drop it, restore the state and run the cold
+// trip, whose samples join ssq one by one (trip_cold_ssq: observations read again); the others add the sum they hold.  The early-rejection compare
+// reads ssq as the previous trip left it either way.
+template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU, bool INSTEP = false>
 __device__ __forceinline__ int integrate_multi(const double *lds, const double *ld, const Consts &K, Lane L, int k0, int kn, int r,
                                                int nsteps, State &s, Emit &em, double &ssq, double thr, bool active, double *acc_out,
                                                int64_t stride, Wave &W) {
   static_assert(NU >= 1 && (kResync % NU) == 0, "trip lengths divide the resync interval");
+  static_assert(!INSTEP || (T == TIGHT && WANT_SSQ && !WANT_ACC && S1), "the in-step sum of squares: TIGHT, SSq alone, one step per sample");
   set_tier<T>(L);
   for (; r + NU <= nsteps; r += NU) {
     const unsigned long long deadmask = WANT_SSQ ? ballot(ssq > thr) : 0ull;  // NaN compares false: such a lane runs on
     const double *v = lds + 2 * r;
     // one step per sample: the observations this trip completes, read before the arithmetic (a lone wave has nothing
     // else to hide the LDS latency behind)
-    double obs[NU], dv[NU];
+    double obs[NU], dv[INSTEP ? 1 : NU];
 #pragma unroll
     for (int j = 0; j < NU; ++j) obs[j] = (WANT_SSQ && S1) ? ld[r + j] : 0.0;
     if (r >= W.next_resync) {
@@ -613,8 +691,11 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
     }
     const State save = s;
     bool calm = false;
-    const bool bad = trip_fast<DAMP, T, NU>(v, L, K, s, dv, &calm);
-    const unsigned long long badmask = ballot(bad) & W.alive;  // wave-uniform, straight from the compares
+    double tsum = 0.0;
+    unsigned long long tripped;
+    if constexpr (INSTEP) tripped = trip_fast_ssq<DAMP, NU>(v, obs, L, K, s, tsum);
+    else tripped = ballot(trip_fast<DAMP, T, NU>(v, L, K, s, dv, &calm));
+    const unsigned long long badmask = tripped & W.alive;  // wave-uniform, straight from the compares
     W.steps[T] += NU;
     W.lane_steps += NU * (uint32_t)__builtin_popcountll(W.alive);
     if constexpr (T != TIGHT) {  // evidence for one tier tighter: every alive lane calm in this trip (struct Wave)
@@ -623,14 +704,20 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
     if (__builtin_expect(badmask != 0, 0)) {  // scalar branch: the hot path carries no exec-mask bookkeeping
       if (lane_in(badmask)) {
         s = save;
-        trip_cold<DAMP, T, NU>(v, L, K, s, dv);
+        if constexpr (INSTEP) {
+          tsum = 0.0;  // the cold trip's samples instead, straight onto the running sum
+          trip_cold_ssq<DAMP, T, NU>(v, ld + r, L, K, s, ssq);
+        } else {
+          trip_cold<DAMP, T, NU>(v, L, K, s, dv);
+        }
       }
       W.need[T] |= badmask;
       W.redone += NU;
       W.full_run = 0;
       W.calm = 0;
     }
-    emit_trip<WANT_SSQ, WANT_ACC, S1, NU>(dv, obs, ld, r, s, em, L, K, k0, ssq, active, acc_out, stride);
+    if constexpr (INSTEP) ssq += tsum;
+    else emit_trip<WANT_SSQ, WANT_ACC, S1, NU>(dv, obs, ld, r, s, em, L, K, k0, ssq, active, acc_out, stride);
     W.alive &= ~deadmask;
     if constexpr (T != TIGHT) {
       if (W.calm >= kCalmSteps && badmask == 0) {  // demote: constant index (a run-time one would put the Wave in scratch memory)
@@ -748,17 +835,21 @@ __device__ __forceinline__ void integrate_lockstep(double *lds, const Consts &K,
 }
 
 // trips of tier T from chunk step r (at least two steps are left): long trips while they fit, then pairs
-template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU>
+template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU, bool INSTEP = false>
 __device__ __forceinline__ int integrate_tier(const double *lds, const double *ld, const Consts &K, const Lane &L, int k0, int kn, int r,
                                               int nsteps, State &s, Emit &em, double &ssq, double thr, bool active, double *acc_out,
                                               int64_t stride, Wave &W) {
-  if (r + NU <= nsteps) return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, NU>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
-  return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, 2>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
+  if (r + NU <= nsteps) return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, NU, INSTEP>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
+  return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, 2, INSTEP>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
 }
 
-template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, bool S1, int NUT>
+// SSQ_IN_STEP: the caller wants the TIGHT trips' in-step sum of squares (integrate_multi, INSTEP) where the solve allows it —
+// the sum of squares alone, one step per sample.  The sampler asks for it; the forward kernel's SSq-only launch does not: it
+// returns the trajectory launch's sum to the bit.
+template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, bool S1, int NUT, bool SSQ_IN_STEP>
 __device__ __forceinline__ void integrate_tiers(const double *lds, const double *ld, const Consts &K, const Lane &L, int k0,
                                                 int kn, State &s, double &ssq, double thr, bool active, double *acc_out, int64_t stride, Wave &W) {
+  constexpr bool INSTEP = SSQ_IN_STEP && WANT_SSQ && !WANT_ACC && S1;
   const int nsteps = S1 ? kn : K.S * kn;
   Emit em = {0, 0, s.V};
   int r = 0;
@@ -775,7 +866,7 @@ __device__ __forceinline__ void integrate_tiers(const double *lds, const double 
     if (!scaled) { tier_enter<DAMP, TIGHT>(s, L); scaled = true; }
     // the chunk's odd last step (it always completes a sample): with the WIDE series whatever the tier — one instance
     if (nsteps - r == 1) r = integrate_multi<DAMP, WANT_SSQ, WANT_ACC, WIDE, S1, 1>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
-    else if (tier == TIGHT) r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, TIGHT, S1, NUT>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
+    else if (tier == TIGHT) r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, TIGHT, S1, NUT, INSTEP>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
     else if (tier == NARROW) r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, NARROW, S1, kNarrowUnroll>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
     else r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, WIDE, S1, kWiderUnroll>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
   }
@@ -784,12 +875,12 @@ __device__ __forceinline__ void integrate_tiers(const double *lds, const double 
 
 // Integrate kn output intervals from the staged chunk.  Accumulates the sum of squares
 // (MCMC.py:387) and optionally stores acc time-major (`active` lanes only).  Called by whole waves.
-template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int NUT>
+template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int NUT, bool SSQ_IN_STEP>
 __device__ __forceinline__ void integrate_chunk(const double *lds, const Consts &K, const Lane &L, int k0, int kn, State &s,
                                                 double &ssq, double thr, bool active, double *acc_out, int64_t stride, Wave &W) {
   const double *ld = lds + lds_data_offset(K);
-  if (K.S == 1) integrate_tiers<DAMP, WANT_SSQ, WANT_ACC, true, NUT>(lds, ld, K, L, k0, kn, s, ssq, thr, active, acc_out, stride, W);
-  else integrate_tiers<DAMP, WANT_SSQ, WANT_ACC, false, NUT>(lds, ld, K, L, k0, kn, s, ssq, thr, active, acc_out, stride, W);
+  if (K.S == 1) integrate_tiers<DAMP, WANT_SSQ, WANT_ACC, true, NUT, SSQ_IN_STEP>(lds, ld, K, L, k0, kn, s, ssq, thr, active, acc_out, stride, W);
+  else integrate_tiers<DAMP, WANT_SSQ, WANT_ACC, false, NUT, SSQ_IN_STEP>(lds, ld, K, L, k0, kn, s, ssq, thr, active, acc_out, stride, W);
 }
 
 // Full forward solve for one lane.  Every thread of the workgroup must call it (chunk staging has barriers);
@@ -797,8 +888,8 @@ __device__ __forceinline__ void integrate_chunk(const double *lds, const Consts 
 // NUT: RK4 steps per trip of the TIGHT loop (integrate_multi); 16 where the kernel's registers allow it (one-parameter
 // sampler), 8 otherwise.  thr: a sum of squares above it cannot be accepted (struct Wave; +inf where every lane's result is
 // wanted) — the value returned for a lane that stopped counting is the partial sum that disqualified it.  W: the solve's
-// wave-level control and statistics, for the caller's counters.
-template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int NUT = kTightUnroll>
+// wave-level control and statistics, for the caller's counters.  SSQ_IN_STEP: integrate_tiers.
+template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int NUT = kTightUnroll, bool SSQ_IN_STEP = false>
 __device__ __forceinline__ double solve(double *lds, const Consts &K, bool resident, bool active, double dc, double a,
                                         double b, double thr, double *acc_out, int64_t stride, Wave &W) {
   const Lane L = make_lane<DAMP>(dc, a, b, K);
@@ -816,7 +907,7 @@ __device__ __forceinline__ double solve(double *lds, const Consts &K, bool resid
     // a wave-uniform branch: every lane of a wave with work goes in — the lanes that are not `active` (out of bounds, past
     // the end of the batch) ride along masked out of W.alive and of the trajectory stores.  (Under `if (active)`, a divergent
     // branch, everything the solve leaves in W would count as divergent after it and move from scalar to vector registers.)
-    if (W.alive != 0) integrate_chunk<DAMP, WANT_SSQ, WANT_ACC, NUT>(lds, K, L, k0, kn, s, ssq, thr, active, acc_out, stride, W);
+    if (W.alive != 0) integrate_chunk<DAMP, WANT_SSQ, WANT_ACC, NUT, SSQ_IN_STEP>(lds, K, L, k0, kn, s, ssq, thr, active, acc_out, stride, W);
   }
   return ssq;
 }

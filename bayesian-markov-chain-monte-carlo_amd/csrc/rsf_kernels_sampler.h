@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(kMaxBlock, kMinBlocks) mcmc_kernel(Consts K, M
         if constexpr (MODE == DOP853) {
           ssqn = rsf::dp::solve<DAMP, true, false>(lds, K, resident, have, qn[0], an, bn, nullptr, 0);
         } else {
-          ssqn = rsf::solve<DAMP, true, false, (D == 1 ? 2 : kD3Trip) * rsf::kTightUnroll>(lds, K, resident, have, qn[0], an, bn, thr, nullptr, 0, cnt.W);
+          ssqn = rsf::solve<DAMP, true, false, (D == 1 ? 2 : kD3Trip) * rsf::kTightUnroll, true>(lds, K, resident, have, qn[0], an, bn, thr, nullptr, 0, cnt.W);
           cnt.early += (uint32_t)__builtin_popcountll(inbmask & ~cnt.W.alive);
         }
       }
