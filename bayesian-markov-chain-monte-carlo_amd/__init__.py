@@ -10,7 +10,7 @@ from . import _abi  # noqa: F401
 from ._abi import RsfError  # noqa: F401
 from .engine import Engine, bayes_factor  # noqa: F401
 from .RateStateModel import RateStateModel  # noqa: F401
-from .MCMC import MCMC  # noqa: F401
+from .MCMC import MCMC, PosteriorPool  # noqa: F401
 from .RSF import RSF, measure_execution_time  # noqa: F401
 
-__all__ = ["Engine", "bayes_factor", "RsfError", "RateStateModel", "MCMC", "RSF", "measure_execution_time"]
+__all__ = ["Engine", "bayes_factor", "RsfError", "RateStateModel", "MCMC", "PosteriorPool", "RSF", "measure_execution_time"]

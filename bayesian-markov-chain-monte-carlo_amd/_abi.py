@@ -212,6 +212,30 @@ EVIDENCE_MAX_ITER = 1000  # Engine.evidence_bridge: iterations at most
 EVIDENCE_RTOL = 1e-10     # ... and the relative change of r below which it has converged
 
 
+# include/rsf_smc.h: tempered sequential Monte Carlo over the box prior; exported by librsf_hip.so only, bound by load()
+SMC_PROTOTYPES = {
+    "rsf_smc_init": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_double), POINTER(c_double), c_uint64, c_int64, _P]),
+    "rsf_smc_weight_sums": (c_int, [c_void_p, c_int64, _P, c_int32, POINTER(c_double), c_double, POINTER(c_double)]),
+    "rsf_smc_section": (c_int, [c_double, c_int32, POINTER(c_double), POINTER(c_int32)]),
+    "rsf_smc_increment": (c_int, [c_int64, c_double, c_double, c_double, POINTER(c_double)]),
+    "rsf_smc_log_evidence": (c_int, [c_double, c_double, c_int32, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+    "rsf_smc_resample": (c_int, [c_void_p, c_int64, c_int32, _P, _P, c_double, c_double, c_double, _P, _P, _P, _P]),
+    "rsf_smc_move": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, c_double, POINTER(c_double), POINTER(c_double), POINTER(c_double),
+                             c_double, c_uint64, c_int64, c_int64, c_int32, POINTER(c_int64)]),
+    "rsf_smc_move_propose": (c_int, [c_void_p, c_int64, c_int32, _P, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_uint64,
+                                     c_int64, c_int64, _P, _P]),
+    "rsf_smc_move_accept": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, _P, _P, c_double, c_double, c_uint64, c_int64, c_int64,
+                                    POINTER(c_int64)]),
+    "rsf_smc_std2": (c_int, [c_void_p, c_int64, _P, c_double, c_uint64, c_int64, c_int64, _P]),
+}
+SMC_MAX_PARAMS = 3       # RSF_SMC_MAX_PARAMS
+SMC_MAX_CANDIDATES = 16  # RSF_SMC_MAX_CANDIDATES: steps evaluated in one read of l, the sections of Engine.smc's search
+SMC_HEAD = 3             # RSF_SMC_HEAD: lmax, finite entries, -inf entries before rsf_smc_weight_sums' sums
+SMC_MAX_STEPS = 64       # RSF_SMC_MAX_STEPS
+SMC_ROUNDS = 6           # Engine.smc: rounds of the 16-section search for the next temperature step
+SMC_RESAMPLE_COUNTER = (0xFFFFFFFF, 0xFFFFFFFF, 4)  # Philox counter (particle lo, particle hi, ., slot) of a stage's resampling uniform
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -255,7 +279,8 @@ def load():
                                "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
-        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES):
+        for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
+                      SMC_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

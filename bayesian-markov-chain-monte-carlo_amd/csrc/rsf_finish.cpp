@@ -1,5 +1,6 @@
 // rsf_finish.cpp — the host arithmetic that turns the device partials into the reported statistics: rsf_diag_finish,
-// rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish, rsf_pool_joint_finish, rsf_pool_hpd_levels, rsf_evidence_finish.  No ctx, no GPU:
+// rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish, rsf_pool_joint_finish, rsf_pool_hpd_levels, rsf_evidence_finish,
+// rsf_smc_section, rsf_smc_increment, rsf_smc_log_evidence.  No ctx, no GPU:
 // plain C++, the public headers and the standard library only.
 #include <cmath>
 #include <cstdint>
@@ -12,6 +13,7 @@
 #include "../../include/rsf_joint.h"
 #include "../../include/rsf_predict.h"
 #include "../../include/rsf_psis.h"
+#include "../../include/rsf_smc.h"
 
 #pragma GCC visibility push(hidden)
 namespace rsfh { int fail(int code, const char *fmt, ...); }  // rsf_hip.hip: formats rsf_last_error()'s message, returns code
@@ -257,6 +259,36 @@ int rsf_evidence_finish(const double *partials, double r, double lstar, double e
     const double re2 = std::fmax(v1, 0.0) / (n2 * e1 * e1) + std::fmax(v2, 0.0) / (ess_factor * n1 * e2 * e2);
     out[3] = std::sqrt(re2);
   }
+  return RSF_OK;
+}
+
+int rsf_smc_section(double target, int32_t m, const double *sums, int32_t *k) {
+  if (!sums || !k) return fail(RSF_ERR_INVALID, "rsf_smc_section: NULL argument");
+  if (m < 1 || m > RSF_SMC_MAX_CANDIDATES || !(target >= 0.0)) return fail(RSF_ERR_INVALID, "rsf_smc_section: need 1 <= m <= %d and target >= 0", RSF_SMC_MAX_CANDIDATES);
+  int32_t j = 0;
+  while (j < m && sums[2 * j] * sums[2 * j] >= target * sums[2 * j + 1]) ++j;  // a NaN sum compares false: the search stops there
+  *k = j;
+  return RSF_OK;
+}
+
+int rsf_smc_increment(int64_t n, double sum_w, double delta, double lmax, double *out) {
+  if (!out) return fail(RSF_ERR_INVALID, "rsf_smc_increment: NULL argument");
+  if (n < 1 || !(sum_w > 0.0) || !std::isfinite(sum_w) || !std::isfinite(delta) || !std::isfinite(lmax))
+    return fail(RSF_ERR_INVALID, "rsf_smc_increment: need n >= 1, finite sum_w > 0, finite delta and lmax");
+  *out = std::log(sum_w / (double)n) + delta * lmax;
+  return RSF_OK;
+}
+
+int rsf_smc_log_evidence(double log_integral, double shape, int32_t d, const double *lo, const double *hi, double *out) {
+  if (!out || !lo || !hi) return fail(RSF_ERR_INVALID, "rsf_smc_log_evidence: NULL argument");
+  if (!std::isfinite(shape) || !(shape > 0.0)) return fail(RSF_ERR_INVALID, "rsf_smc_log_evidence: shape must be finite and > 0");
+  if (d < 1 || d > RSF_SMC_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_smc_log_evidence: d outside 1..%d", RSF_SMC_MAX_PARAMS);
+  double logvol = 0.0;
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "rsf_smc_log_evidence: need finite lo[%d] < hi[%d]", p, p);
+    logvol += std::log(hi[p] - lo[p]);
+  }
+  *out = log_integral - logvol + std::lgamma(shape) - shape * std::log(3.14159265358979323846);
   return RSF_OK;
 }
 

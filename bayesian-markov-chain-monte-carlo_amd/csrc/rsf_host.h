@@ -69,6 +69,11 @@ enum Slot : int {
   // rsf_evidence_propose (theta, logg, inbox out), rsf_evidence_logg (theta in, logg out), rsf_evidence_logtarget (theta, the
   // observation and logg in, l out), rsf_evidence_partials (l1 in SLOT_EV_L, l2 in SLOT_EV_L2)
   SLOT_EV_THETA = SLOT_Z, SLOT_EV_LOGG = SLOT_U, SLOT_EV_OBS = SLOT_G, SLOT_EV_L = SLOT_TQ, SLOT_EV_L2 = SLOT_TS, SLOT_EV_INBOX = SLOT_TA,
+  // rsf_smc_init (q out), rsf_smc_weight_sums (l), rsf_smc_resample (q, l in; cum, anc, q_out, l_out out), rsf_smc_move (q, l in
+  // and out, the observation), rsf_smc_move_propose (q in; q_new in SLOT_SMC_Q_OUT, inbox out), rsf_smc_move_accept (q, l in and
+  // out; q_new, inbox, ssq_new in), rsf_smc_std2 (l in, std2 in SLOT_SMC_L_OUT)
+  SLOT_SMC_Q = SLOT_Z, SLOT_SMC_L = SLOT_U, SLOT_SMC_OBS = SLOT_G, SLOT_SMC_CUM = SLOT_G, SLOT_SMC_ANC = SLOT_TQ, SLOT_SMC_INBOX = SLOT_TQ,
+  SLOT_SMC_Q_OUT = SLOT_TS, SLOT_SMC_L_OUT = SLOT_TA, SLOT_SMC_SSQ = SLOT_SSQ_NEW,
   // rsf_pool_allgather[_all] / _allreduce_sum[_all] (the reduction is in place in SLOT_SEND)
   SLOT_SEND = SLOT_Z, SLOT_RECV = SLOT_U,
 };

@@ -1,0 +1,248 @@
+// rsf_smc.hip — tempered sequential Monte Carlo over the box prior (include/rsf_smc.h): rsf_smc_init / _weight_sums / _resample /
+// _move / _move_propose / _move_accept / _std2 (kernels: rsf_kernels_smc.h).  rsf_smc_section, rsf_smc_increment and
+// rsf_smc_log_evidence, the host arithmetic, are in rsf_finish.cpp.
+#include <cmath>
+#include <algorithm>
+
+#include "rsf_host.h"
+#include "rsf_kernels_smc.h"
+
+using namespace rsfk;
+using namespace rsfh;
+
+namespace {
+
+unsigned blocks_of(int64_t n) { return (unsigned)((n + kMaxBlock - 1) / kMaxBlock); }
+
+// the box of a call into A.lo[], A.hi[]; fn: the entry point the message names
+int set_box(const char *fn, int d, const double *lo, const double *hi, SmcArgs &A) {
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "%s: need finite lo[%d] < hi[%d]", fn, p, p);
+    A.lo[p] = lo[p]; A.hi[p] = hi[p];
+  }
+  return RSF_OK;
+}
+
+// chol[d][d]: lower triangular with a positive finite diagonal, into A.L
+int set_factor(const char *fn, int d, const double *chol, SmcArgs &A) {
+  int e = 0;
+  for (int p = 0; p < d; ++p)
+    for (int r = 0; r < d; ++r) {
+      const double v = chol[p * d + r];
+      if (!std::isfinite(v) || (r > p && v != 0.0) || (r == p && !(v > 0.0)))
+        return fail(RSF_ERR_INVALID, "%s: chol is not a lower triangular factor with a positive diagonal (entry [%d][%d])", fn, p, r);
+      if (r <= p) A.L[e++] = v;
+    }
+  return RSF_OK;
+}
+
+int set_stream(const char *fn, int64_t n, int64_t offset, int64_t iter, int64_t iter_min, uint64_t seed, SmcArgs &A) {
+  if (n < 1 || offset < 0 || iter < iter_min || iter > 0xffffffffll - RSF_SMC_MAX_STEPS)
+    return fail(RSF_ERR_INVALID, "%s: need n >= 1, offset >= 0 and an iteration in [%lld, 2^32 - %d)", fn, (long long)iter_min, RSF_SMC_MAX_STEPS + 1);
+  A.n = n; A.offset = offset; A.seed = seed; A.iter = (uint32_t)iter;
+  return RSF_OK;
+}
+
+auto init_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return smc_init_kernel<D>; }); }
+auto propose_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return smc_propose_kernel<D>; }); }
+// the float64 RK4 solve with or without damping, chosen as predict_kernel's dispatcher chooses
+auto move_fn(const rsf_ctx *c, int d) {
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return smc_move_kernel<D, DAMP>; }); });
+}
+
+// the accepted counts of `steps` steps: zeroed before the launch, read after it (the pool workspace's first bytes)
+int counts_begin(rsf_ctx *c, int steps, unsigned long long **cnt) {
+  int rc;
+  if ((rc = ensure(c->pool, sizeof(unsigned long long) * RSF_SMC_MAX_STEPS))) return rc;
+  *cnt = (unsigned long long *)c->pool.p;
+  HIP_TRY(hipMemsetAsync(*cnt, 0, sizeof(unsigned long long) * steps, c->stream));
+  return RSF_OK;
+}
+int counts_end(rsf_ctx *c, int steps, const unsigned long long *cnt, int64_t *accepted) {
+  unsigned long long h[RSF_SMC_MAX_STEPS];
+  HIP_TRY(hipMemcpyAsync(h, cnt, sizeof(unsigned long long) * steps, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int s = 0; s < steps; ++s) accepted[s] = (int64_t)h[s];
+  return RSF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsf_smc_init(rsf_ctx *c, int64_t n, int32_t d, const double *lo, const double *hi, uint64_t seed, int64_t offset, double *q) {
+  RSF_ENTER(c, NEED_NOTHING, lo && hi && q, "NULL argument");
+  if (d < 1 || d > RSF_SMC_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_smc_init: need 1 <= d <= %d", RSF_SMC_MAX_PARAMS);
+  int rc;
+  SmcArgs A{};
+  if ((rc = set_stream(__func__, n, offset, 0, 0, seed, A))) return rc;
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  const size_t nb = (size_t)n * d * sizeof(double);
+  double *dq;
+  if ((rc = stage_out(c, SLOT_SMC_Q, q, nb, &dq))) return rc;
+  if ((rc = launch(c, init_fn(d), blocks_of(n), kMaxBlock, 0, A, dq))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q, q, nb))) return rc;
+  return finish(c);
+}
+
+int rsf_smc_weight_sums(rsf_ctx *c, int64_t n, const double *l, int32_t m, const double *deltas, double lmax, double *out) {
+  RSF_ENTER(c, NEED_NOTHING, l && deltas && out, "NULL argument");
+  if (n < 1 || m < 1 || m > RSF_SMC_MAX_CANDIDATES) return fail(RSF_ERR_INVALID, "rsf_smc_weight_sums: need n >= 1 and 1 <= m <= %d", RSF_SMC_MAX_CANDIDATES);
+  if (std::isinf(lmax)) return fail(RSF_ERR_INVALID, "rsf_smc_weight_sums: lmax is finite, or NaN for the largest finite l");
+  SmcDeltas dl{};
+  for (int k = 0; k < m; ++k) {
+    if (!std::isfinite(deltas[k]) || deltas[k] < 0.0) return fail(RSF_ERR_INVALID, "rsf_smc_weight_sums: deltas[%d] is not finite and >= 0", k);
+    dl.v[k] = deltas[k];
+  }
+  int rc;
+  const double *dl_l;
+  if ((rc = stage_in(c, SLOT_SMC_L, l, (size_t)n * sizeof(double), &dl_l))) return rc;
+  // workspace, doubles: sums[kSmcFields] | head[kSmcHead] | the workgroups' partials of the sums | ... of the head
+  const int blocks = (int)std::min<int64_t>(kSmcBlocks, (n + kMaxBlock - 1) / kMaxBlock);
+  if ((rc = ensure(c->pool, sizeof(double) * (kSmcFields + kSmcHead) * (kSmcBlocks + 1)))) return rc;
+  double *ws = (double *)c->pool.p, *head = ws + kSmcFields, *part = head + kSmcHead, *parth = part + (size_t)kSmcFields * kSmcBlocks;
+  double h[kSmcHead + kSmcFields];
+  if ((rc = launch(c, smc_max_kernel, blocks, kMaxBlock, 0, n, dl_l, parth))) return rc;
+  if ((rc = launch(c, smc_max_finish_kernel, 1, kMaxBlock, 0, blocks, parth, head))) return rc;
+  HIP_TRY(hipMemcpyAsync(h, head, kSmcHead * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (h[1] + h[2] != (double)n) return fail(RSF_ERR_INVALID, "rsf_smc_weight_sums: %lld of l are NaN or +inf", (long long)((double)n - h[1] - h[2]));
+  if (!(h[1] > 0.0)) return fail(RSF_ERR_INVALID, "rsf_smc_weight_sums: every particle has l = -inf (no particle lies in the target's support)");
+  if (!std::isnan(lmax)) h[0] = lmax;
+  if ((rc = launch(c, smc_weight_sums_kernel, blocks, kMaxBlock, 0, n, dl_l, h[0], dl, part))) return rc;
+  if ((rc = sum_strided_tree(c, blocks, kSmcFields, part, ws))) return rc;
+  HIP_TRY(hipMemcpyAsync(h + kSmcHead, ws, kSmcFields * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
+  for (int k = 0; k < 2 * m; ++k) out[RSF_SMC_HEAD + k] = h[kSmcHead + k];
+  return RSF_OK;
+}
+
+int rsf_smc_resample(rsf_ctx *c, int64_t n, int32_t d, const double *q, const double *l, double delta, double lmax, double u, double *cum,
+                     int64_t *anc, double *q_out, double *l_out) {
+  RSF_ENTER(c, NEED_NOTHING, q && l && cum && anc && q_out && l_out, "NULL argument");
+  if (n < 1 || d < 1 || d > RSF_SMC_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_smc_resample: need n >= 1, 1 <= d <= %d", RSF_SMC_MAX_PARAMS);
+  if (!std::isfinite(delta) || delta < 0.0 || !std::isfinite(lmax) || !(u > 0.0 && u <= 1.0))
+    return fail(RSF_ERR_INVALID, "rsf_smc_resample: need finite delta >= 0, finite lmax and u inside (0, 1]");
+  int rc;
+  const size_t nb = (size_t)n * sizeof(double);
+  const double *dq, *dl;
+  double *dcum, *dqo, *dlo;
+  int64_t *danc;
+  if ((rc = stage_in(c, SLOT_SMC_Q, q, nb * d, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_L, l, nb, &dl))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_CUM, cum, nb, &dcum))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_ANC, anc, (size_t)n * sizeof(int64_t), &danc))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_Q_OUT, q_out, nb * d, &dqo))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_L_OUT, l_out, nb, &dlo))) return rc;
+  const int64_t ntiles = (n + kSmcTile - 1) / kSmcTile;
+  if ((rc = ensure(c->pool, sizeof(double) * (size_t)ntiles))) return rc;
+  double *tsum = (double *)c->pool.p;
+  if ((rc = launch(c, smc_scan_tiles_kernel, (unsigned)ntiles, kMaxBlock, 0, n, dl, delta, lmax, tsum))) return rc;
+  if ((rc = launch(c, smc_scan_carry_kernel, 1, 64, 0, ntiles, tsum))) return rc;
+  if ((rc = launch(c, smc_scan_final_kernel, (unsigned)ntiles, kMaxBlock, 0, n, dl, delta, lmax, tsum, dcum))) return rc;
+  if ((rc = launch(c, smc_ancestor_kernel, blocks_of(n), kMaxBlock, 0, n, dcum, u, danc))) return rc;
+  if ((rc = launch(c, smc_gather_kernel, blocks_of(n), kMaxBlock, 0, n, d, danc, dq, dl, dqo, dlo))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_CUM, cum, nb))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_ANC, anc, (size_t)n * sizeof(int64_t)))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q_OUT, q_out, nb * d))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L_OUT, l_out, nb))) return rc;
+  return finish(c);
+}
+
+int rsf_smc_move(rsf_ctx *c, int64_t n, int32_t d, double *q, double *l, const double *data, double shape, const double *lo, const double *hi,
+                 const double *chol, double beta, uint64_t seed, int64_t offset, int64_t iter0, int32_t steps, int64_t *accepted) {
+  RSF_ENTER(c, NEED_MODEL, q && l && data && lo && hi && chol && accepted, "NULL argument");
+  if (d != 1 && d != 3) return fail(RSF_ERR_INVALID, "rsf_smc_move: need d = 1 or 3");
+  if (!std::isfinite(shape) || !(shape > 0.0) || !std::isfinite(beta) || !(beta > 0.0))
+    return fail(RSF_ERR_INVALID, "rsf_smc_move: shape and beta must be finite and > 0");
+  if (steps < 1 || steps > RSF_SMC_MAX_STEPS) return fail(RSF_ERR_INVALID, "rsf_smc_move: need 1 <= steps <= %d", RSF_SMC_MAX_STEPS);
+  if (c->m.flags & RSF_FLAG_DOP853)
+    return fail(RSF_ERR_UNSUPPORTED, "rsf_smc_move: a model flagged RSF_FLAG_DOP853 is not supported (the solve is the float64 RK4)");
+  int rc;
+  SmcArgs A{};
+  if ((rc = set_stream(__func__, n, offset, iter0, 1, seed, A))) return rc;
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  if ((rc = set_factor(__func__, d, chol, A))) return rc;
+  A.steps = steps; A.beta = beta; A.shape = shape;
+  const size_t nb = (size_t)n * sizeof(double);
+  const double *dq, *dl, *ddata;
+  unsigned long long *cnt;
+  if ((rc = stage_in(c, SLOT_SMC_Q, (const double *)q, nb * d, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_L, (const double *)l, nb, &dl))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_OBS, data, (size_t)c->nout * sizeof(double), &ddata))) return rc;
+  if ((rc = counts_begin(c, steps, &cnt))) return rc;
+  // the shared chunking of the float64 tables (c->kc, c->lds_bytes), as rsf_evidence_logtarget's solve
+  if ((rc = launch(c, move_fn(c, d), grid_for(c, n), c->block, c->lds_bytes, make_consts(c, ddata), A, (double *)dq, (double *)dl, cnt))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q, q, nb * d))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L, l, nb))) return rc;
+  return counts_end(c, steps, cnt, accepted);
+}
+
+int rsf_smc_move_propose(rsf_ctx *c, int64_t n, int32_t d, const double *q, const double *lo, const double *hi, const double *chol, uint64_t seed,
+                         int64_t offset, int64_t iter, double *q_new, uint8_t *inbox) {
+  RSF_ENTER(c, NEED_NOTHING, q && lo && hi && chol && q_new && inbox, "NULL argument");
+  if (d < 1 || d > RSF_SMC_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_smc_move_propose: need 1 <= d <= %d", RSF_SMC_MAX_PARAMS);
+  int rc;
+  SmcArgs A{};
+  if ((rc = set_stream(__func__, n, offset, iter, 1, seed, A))) return rc;
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  if ((rc = set_factor(__func__, d, chol, A))) return rc;
+  const size_t nb = (size_t)n * d * sizeof(double);
+  const double *dq;
+  double *dqn;
+  uint8_t *dinb;
+  if ((rc = stage_in(c, SLOT_SMC_Q, q, nb, &dq))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_Q_OUT, q_new, nb, &dqn))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_INBOX, inbox, (size_t)n, &dinb))) return rc;
+  if ((rc = launch(c, propose_fn(d), blocks_of(n), kMaxBlock, 0, A, dq, dqn, dinb))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q_OUT, q_new, nb))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_INBOX, inbox, (size_t)n))) return rc;
+  return finish(c);
+}
+
+int rsf_smc_move_accept(rsf_ctx *c, int64_t n, int32_t d, double *q, double *l, const double *q_new, const uint8_t *inbox, const double *ssq_new,
+                        double shape, double beta, uint64_t seed, int64_t offset, int64_t iter, int64_t *accepted) {
+  RSF_ENTER(c, NEED_NOTHING, q && l && q_new && inbox && ssq_new && accepted, "NULL argument");
+  if (d < 1 || d > RSF_SMC_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_smc_move_accept: need 1 <= d <= %d", RSF_SMC_MAX_PARAMS);
+  if (!std::isfinite(shape) || !(shape > 0.0) || !std::isfinite(beta) || !(beta > 0.0))
+    return fail(RSF_ERR_INVALID, "rsf_smc_move_accept: shape and beta must be finite and > 0");
+  int rc;
+  SmcArgs A{};
+  if ((rc = set_stream(__func__, n, offset, iter, 1, seed, A))) return rc;
+  A.steps = 1; A.beta = beta; A.shape = shape;
+  const size_t nb = (size_t)n * sizeof(double);
+  const double *dq, *dl, *dqn, *dssq;
+  const uint8_t *dinb;
+  unsigned long long *cnt;
+  if ((rc = stage_in(c, SLOT_SMC_Q, (const double *)q, nb * d, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_L, (const double *)l, nb, &dl))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_Q_OUT, q_new, nb * d, &dqn))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_INBOX, inbox, (size_t)n, &dinb))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_SSQ, ssq_new, nb, &dssq))) return rc;
+  if ((rc = counts_begin(c, 1, &cnt))) return rc;
+  if ((rc = launch(c, smc_accept_kernel, blocks_of(n), kMaxBlock, 0, A, d, dqn, dinb, dssq, (double *)dq, (double *)dl, cnt))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q, q, nb * d))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L, l, nb))) return rc;
+  return counts_end(c, 1, cnt, accepted);
+}
+
+int rsf_smc_std2(rsf_ctx *c, int64_t n, const double *l, double shape, uint64_t seed, int64_t offset, int64_t iter, double *std2) {
+  RSF_ENTER(c, NEED_NOTHING, l && std2, "NULL argument");
+  if (!std::isfinite(shape) || !(shape >= 1.0)) return fail(RSF_ERR_INVALID, "rsf_smc_std2: shape must be finite and >= 1 (the gamma variate's range)");
+  int rc;
+  SmcArgs A{};
+  if ((rc = set_stream(__func__, n, offset, iter, 0, seed, A))) return rc;
+  A.shape = shape;
+  const size_t nb = (size_t)n * sizeof(double);
+  const double *dl;
+  double *ds;
+  if ((rc = stage_in(c, SLOT_SMC_L, l, nb, &dl))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_L_OUT, std2, nb, &ds))) return rc;
+  const double gd = shape - 1.0 / 3.0;
+  if ((rc = launch(c, smc_std2_kernel, blocks_of(n), kMaxBlock, 0, A, gd, 1.0 / std::sqrt(9.0 * gd), dl, ds))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L_OUT, std2, nb))) return rc;
+  return finish(c);
+}
+
+}  // extern "C"

@@ -719,6 +719,236 @@ class Engine:
         return self._evidence(samples, ltarget, lo, hi, shape, int(round(2 * shape)) if n_data is None else n_data, transform, n_proposal,
                               fit_fraction, seed, ess_factor)
 
+    # -- tempered sequential Monte Carlo over the box prior (include/rsf_smc.h) ------------------------------
+    def _smc_box(self, lo, hi, d=None):
+        d = int(np.size(lo)) if d is None else int(d)
+        return _vec(lo, d, "lo"), _vec(hi, d, "hi"), d
+
+    def _smc_particles(self, q, l=None):
+        """q (n,) or (n, d) and l (n,) in this engine's memory space → (q (n, d), l, n, d)"""
+        q = self._in(q)
+        if q.ndim == 1:
+            q = q.reshape(-1, 1)
+        n, d = int(q.shape[0]), int(q.shape[1])
+        l = self._in(l)
+        if l is not None and math.prod(l.shape) != n:
+            raise ValueError(f"l holds {math.prod(l.shape)} values, q {n} particles")
+        return q, l, n, d
+
+    def _bytes(self, x):
+        """a uint8 array in this engine's memory space"""
+        if self.mem == "device":
+            t = self._torch
+            return (x if isinstance(x, t.Tensor) else t.as_tensor(np.ascontiguousarray(x, dtype=np.uint8))).to(device=f"cuda:{self.device}", dtype=t.uint8).contiguous()
+        return np.ascontiguousarray(x, dtype=np.uint8)
+
+    def smc_init(self, lo, hi, n, seed=0, offset=0):
+        """rsf_smc_init: n particles uniform in the strict box (lo, hi) → q (n, d) in this engine's memory space.  Particle j uses
+        the Philox stream of (seed, offset + j, iteration 0): shards with offsets form one stream."""
+        lo, hi, d = self._smc_box(lo, hi)
+        q = self._empty((max(int(n), 0), d))
+        _abi.check(self.lib, self.lib.rsf_smc_init(self._ctx, int(n), d, _dp(lo), _dp(hi), int(seed), int(offset), self._ptr(q)))
+        return q
+
+    def smc_weight_sums(self, l, deltas, lmax=None):
+        """rsf_smc_weight_sums: for up to SMC_MAX_CANDIDATES steps `deltas`, in one read of l (n,) → dict(lmax, n_finite, n_neginf,
+        sums (m, 2): the sum of w = exp(delta (l - lmax)) and of w^2 per candidate).  lmax: by default the largest finite l;
+        shards of one population pass the population's, and their sums then add."""
+        x = self._in(l)
+        dl = np.ascontiguousarray(np.atleast_1d(np.asarray(deltas, dtype=np.float64)))
+        if dl.ndim != 1 or not 1 <= dl.size <= _abi.SMC_MAX_CANDIDATES:
+            raise ValueError(f"deltas holds 1 to {_abi.SMC_MAX_CANDIDATES} steps")
+        out = np.empty(_abi.SMC_HEAD + 2 * dl.size)
+        _abi.check(self.lib, self.lib.rsf_smc_weight_sums(self._ctx, math.prod(x.shape), self._ptr(x), int(dl.size), _dp(dl),
+                                                          float("nan") if lmax is None else float(lmax), _dp(out)))
+        return {"lmax": float(out[0]), "n_finite": int(out[1]), "n_neginf": int(out[2]), "sums": out[_abi.SMC_HEAD:].reshape(-1, 2).copy()}
+
+    def smc_next_delta(self, l, beta, ess_fraction=0.5):
+        """The next temperature step from beta: the largest delta <= 1 - beta that keeps the effective sample size of the weights
+        exp(delta (l - lmax)) at ess_fraction of the particles with a finite l, by SMC_ROUNDS rounds of 16-section, each one read of
+        l (rsf_smc_weight_sums, rsf_smc_section) → dict(delta, beta (the next; exactly 1.0 at the end), lmax, sum_w, ess)."""
+        x = self._in(l)
+        m = _abi.SMC_MAX_CANDIDATES
+        a, b, last, fail = 0.0, 1.0 - float(beta), None, None
+        k = ctypes.c_int32()
+        for rnd in range(_abi.SMC_ROUNDS):
+            cand = [a + (b - a) * j / m for j in range(1, m + 1)]
+            res = self.smc_weight_sums(x, cand)
+            sums = res["sums"]
+            _abi.check(self.lib, self.lib.rsf_smc_section(float(ess_fraction) * res["n_finite"], m, _dp(np.ascontiguousarray(sums)), ctypes.byref(k)))
+            if k.value:
+                last = (cand[k.value - 1], sums[k.value - 1])
+            if k.value == m:
+                if rnd == 0:
+                    return {"delta": b, "beta": 1.0, "lmax": res["lmax"], "sum_w": float(sums[-1, 0]), "ess": float(sums[-1, 0] ** 2 / sums[-1, 1])}
+                break
+            fail = (cand[k.value], sums[k.value])
+            a, b = (cand[k.value - 1] if k.value else a), cand[k.value]
+        delta, sw = last if last is not None else fail
+        return {"delta": delta, "beta": float(beta) + delta, "lmax": res["lmax"], "sum_w": float(sw[0]), "ess": float(sw[0] ** 2 / sw[1])}
+
+    def smc_stage_uniform(self, seed, stage):
+        """The resampling uniform of a stage: u53 of the first two Philox words of the counter (2^32 - 1, 2^32 - 1, stage, 4)."""
+        plo, phi, slot = _abi.SMC_RESAMPLE_COUNTER
+        w = self.philox((plo, phi, int(stage), slot), (int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF))
+        return ((((w[0] << 32) | w[1]) >> 11) + 1) * 2.0 ** -53
+
+    def smc_resample(self, q, l, delta, lmax, u):
+        """rsf_smc_resample: systematic resampling with the weights exp(delta (l - lmax)) and the uniform u in (0, 1] →
+        (cum (n,), ancestors (n,) int64, q (n, d) and l (n,) gathered through the ancestors) in this engine's memory space."""
+        q, l, n, d = self._smc_particles(q, l)
+        if l is None:
+            raise ValueError("l is (n,)")
+        cum, qo, lo_ = self._empty((n,)), self._empty((n, d)), self._empty((n,))
+        anc = self._torch.empty((n,), dtype=self._torch.int64, device=f"cuda:{self.device}") if self.mem == "device" else np.empty(n, dtype=np.int64)
+        _abi.check(self.lib, self.lib.rsf_smc_resample(self._ctx, n, d, self._ptr(q), self._ptr(l), float(delta), float(lmax), float(u),
+                                                       self._ptr(cum), self._ptr(anc), self._ptr(qo), self._ptr(lo_)))
+        return cum, anc, qo, lo_
+
+    def _smc_chol(self, chol, d):
+        L = _host(chol).reshape(-1)
+        if L.size != d * d:
+            raise ValueError(f"chol is ({d}, {d})")
+        return L
+
+    def smc_move(self, q, l, data, lo, hi, chol, beta, seed=0, offset=0, iter0=1, steps=3, shape=None):
+        """rsf_smc_move, the fused hot path: `steps` Metropolis steps per particle on pi_beta with the proposal N(q, chol chol^T),
+        each one float64 RK4 solve of the device model against `data` → (q (n, d), l (n,), accepted (steps,) int64); the arrays
+        handed in are not changed.  Step k uses the variates of draws(seed, offset + j, iter0 + k, d)."""
+        self._need_model()
+        q, l, n, d = self._smc_particles(q, l)
+        obs = self._in(data)
+        if obs.ndim != 1 or int(obs.shape[0]) != self.nout:
+            raise ValueError(f"data has shape {tuple(obs.shape)}, the model produces {self.nout} samples")
+        lo, hi, _ = self._smc_box(lo, hi, d)
+        L = self._smc_chol(chol, d)
+        q, l = (q.clone(), l.clone()) if hasattr(q, "clone") else (q.copy(), l.copy())
+        acc = np.zeros(max(int(steps), 1), dtype=np.int64)
+        _abi.check(self.lib, self.lib.rsf_smc_move(self._ctx, n, d, self._ptr(q), self._ptr(l), self._ptr(obs),
+                                                   float(0.5 * self.nout if shape is None else shape), _dp(lo), _dp(hi), _dp(L), float(beta),
+                                                   int(seed), int(offset), int(iter0), int(steps), acc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return q, l, acc
+
+    def smc_move_propose(self, q, lo, hi, chol, seed=0, offset=0, iteration=1):
+        """rsf_smc_move_propose: the proposals of one Metropolis step → (q_new (n, d), inbox (n,) uint8)."""
+        q, _, n, d = self._smc_particles(q)
+        lo, hi, _ = self._smc_box(lo, hi, d)
+        L = self._smc_chol(chol, d)
+        qn, inb = self._empty((n, d)), self._empty((n,), np.uint8)
+        _abi.check(self.lib, self.lib.rsf_smc_move_propose(self._ctx, n, d, self._ptr(q), _dp(lo), _dp(hi), _dp(L), int(seed), int(offset),
+                                                           int(iteration), self._ptr(qn), self._ptr(inb)))
+        return qn, inb
+
+    def smc_move_accept(self, q, l, q_new, inbox, ssq_new, shape, beta, seed=0, offset=0, iteration=1):
+        """rsf_smc_move_accept: the accept test of one Metropolis step with the caller's sums of squares ssq_new (n,), read where
+        inbox is 1 → (q (n, d), l (n,), accepted); the arrays handed in are not changed."""
+        q, l, n, d = self._smc_particles(q, l)
+        qn, ssq, inb = self._in(q_new), self._in(ssq_new), self._bytes(inbox)
+        if math.prod(qn.shape) != n * d or math.prod(ssq.shape) != n or math.prod(inb.shape) != n:
+            raise ValueError(f"q_new is ({n}, {d}), inbox and ssq_new ({n},)")
+        q, l = (q.clone(), l.clone()) if hasattr(q, "clone") else (q.copy(), l.copy())
+        acc = ctypes.c_int64()
+        _abi.check(self.lib, self.lib.rsf_smc_move_accept(self._ctx, n, d, self._ptr(q), self._ptr(l), self._ptr(qn), self._ptr(inb), self._ptr(ssq),
+                                                          float(shape), float(beta), int(seed), int(offset), int(iteration), ctypes.byref(acc)))
+        return q, l, int(acc.value)
+
+    def smc_std2(self, l, shape, seed=0, offset=0, iteration=0):
+        """rsf_smc_std2: sigma^2 of the final particles from InvGamma(shape, SSq / 2), SSq = exp(-l / shape) → (n,)."""
+        x = self._in(l)
+        out = self._empty((math.prod(x.shape),))
+        _abi.check(self.lib, self.lib.rsf_smc_std2(self._ctx, math.prod(x.shape), self._ptr(x), float(shape), int(seed), int(offset), int(iteration),
+                                                   self._ptr(out)))
+        return out
+
+    def _smc(self, lo, hi, n, shape, seed, offset, ess_fraction, steps, max_stages, ltarget, move, history):
+        """What smc and smc_from_ssq share.  ltarget(q (n, d)) → l (n,); move(q, l, chol, beta, iter0) → (q, l, accepted, solves)."""
+        lo, hi, d = self._smc_box(lo, hi)
+        n, steps, shape = int(n), int(steps), float(shape)
+        if d not in (1, 3):
+            raise ValueError("the box has d = 1 (Dc) or 3 (Dc, a, b) parameters")
+        if not 0.0 < float(ess_fraction) < 1.0 or not 1 <= steps <= _abi.SMC_MAX_STEPS or int(max_stages) < 1:
+            raise ValueError(f"ess_fraction lies strictly inside (0, 1), steps in [1, {_abi.SMC_MAX_STEPS}], max_stages >= 1")
+        q = self.smc_init(lo, hi, n, seed, offset)
+        l = ltarget(q)
+        logi, beta, stages, hist, solves = float(np.log(hi - lo).sum()), 0.0, [], [], n
+        inc = ctypes.c_double()
+        while beta < 1.0:
+            s = len(stages)
+            if s >= int(max_stages):
+                raise _abi.RsfError(-1, f"Engine.smc: beta = {beta!r} after max_stages = {max_stages} stages")
+            nd = self.smc_next_delta(l, beta, ess_fraction)
+            _abi.check(self.lib, self.lib.rsf_smc_increment(n, nd["sum_w"], nd["delta"], nd["lmax"], ctypes.byref(inc)))
+            logi, beta = logi + inc.value, nd["beta"]
+            u = self.smc_stage_uniform(seed, s)
+            cum, anc, q, l = self.smc_resample(q, l, nd["delta"], nd["lmax"], u)
+            cov = self.pool_joint(q)["cov"] if n > 1 else np.zeros((d, d))
+            if not np.isfinite(cov).all():
+                raise _abi.RsfError(-1, "Engine.smc: the resampled particles' covariance is not finite")
+            chol = np.linalg.cholesky((2.38 ** 2 / d) * cov + np.diag((1e-6 * (hi - lo)) ** 2))
+            q, l, acc, ns, after = move(q, l, chol, beta, s * steps + 1)
+            solves += ns
+            stages.append({"beta": beta, "delta": nd["delta"], "ess": nd["ess"], "accept_rate": float(np.sum(acc)) / (n * steps),
+                           "log_integral": logi})
+            if history:
+                hist.append({"lmax": nd["lmax"], "u": u, "cum": _host(cum), "ancestors": np.asarray(anc.cpu() if hasattr(anc, "cpu") else anc),
+                             "chol": chol, "after": after})
+        std2 = self.smc_std2(l, shape, seed, offset, len(stages) * steps + 1)
+        ev = ctypes.c_double()
+        _abi.check(self.lib, self.lib.rsf_smc_log_evidence(logi, shape, d, _dp(lo), _dp(hi), ctypes.byref(ev)))
+        out = {"q": q, "l": l, "std2": std2, "log_integral": logi, "log_evidence": ev.value, "stages": stages, "n_solves": solves,
+               "shape": shape, "d": d, "n": n}
+        if history:
+            out["history"] = hist
+        return out
+
+    def smc(self, data, lo, hi, n, shape=None, seed=0, offset=0, ess_fraction=0.5, steps=3, max_stages=200, history=False):
+        """Tempered sequential Monte Carlo for the device model (set_model) and the observation `data` over the strict box (lo, hi),
+        d = 1 (Dc) or 3 (Dc, a, b): n particles start uniform in the box — no start point, no burn-in — and move through
+        SSq^(-shape beta), beta from 0 to 1; each stage chooses its temperature step from the weights' effective sample size
+        (ess_fraction), resamples systematically and takes `steps` Metropolis steps per particle with the population's own
+        covariance (pool_joint), one forward solve each (smc_move).  → dict(q (n, d), l (n,) = -shape log SSq, std2 (n,) — an
+        equally weighted sample of the sampler's target —, log_integral, log_evidence (the constants of evidence_finish), stages
+        [dict(beta, delta, ess, accept_rate, log_integral so far)], n_solves, shape, d, n).  shape defaults to nout / 2."""
+        self._need_model()
+        shape = 0.5 * self.nout if shape is None else float(shape)
+        obs = self._in(data)
+        blo, bhi, d = self._smc_box(lo, hi)
+
+        def move(q, l, chol, beta, iter0):
+            q, l, acc = self.smc_move(q, l, obs, blo, bhi, chol, beta, seed, offset, iter0, steps, shape)
+            return q, l, acc, int(n) * int(steps), [(_host(q), _host(l))] if history else None
+
+        return self._smc(lo, hi, n, shape, seed, offset, ess_fraction, steps, max_stages,
+                         lambda q: self.evidence_logtarget(q, obs, blo, bhi, self._in(np.zeros(int(n))), shape), move, history)
+
+    def smc_from_ssq(self, ssq_fn, lo, hi, n, shape, seed=0, offset=0, ess_fraction=0.5, steps=3, max_stages=200, history=False):
+        """smc with the caller's sum of squares: ssq_fn(q (m, d) float64 on the host) → SSq (m,), called for points strictly inside
+        the box only.  The start, the weights, the resampling, the proposals and the accept tests run on the GPU."""
+        shape = float(shape)
+        blo, bhi, d = self._smc_box(lo, hi)
+
+        def ltarget(q):
+            ssq = np.asarray(ssq_fn(_host(q).reshape(-1, d)), dtype=np.float64).reshape(-1)
+            ok = np.isfinite(ssq) & (ssq > 0)
+            return self._in(np.where(ok, -shape * np.log(np.where(ok, ssq, 1.0)), -np.inf))
+
+        def move(q, l, chol, beta, iter0):
+            accs, solves, after = [], 0, []
+            for k in range(int(steps)):
+                qn, inb = self.smc_move_propose(q, blo, bhi, chol, seed, offset, iter0 + k)
+                hq, hi_ = _host(qn).reshape(-1, d), np.asarray(inb.cpu() if hasattr(inb, "cpu") else inb).astype(bool)
+                ssq = np.zeros(hq.shape[0])
+                if hi_.any():
+                    ssq[hi_] = np.asarray(ssq_fn(hq[hi_]), dtype=np.float64).reshape(-1)
+                q, l, a = self.smc_move_accept(q, l, qn, inb, ssq, shape, beta, seed, offset, iter0 + k)
+                accs.append(a)
+                solves += int(hi_.sum())
+                if history:
+                    after.append((_host(q), _host(l)))
+            return q, l, accs, solves, after
+
+        return self._smc(lo, hi, n, shape, seed, offset, ess_fraction, steps, max_stages, ltarget, move, history)
+
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
         x = self._in(trace)
