@@ -47,6 +47,11 @@ int pool_moments(rsf_ctx *c, int64_t n, const double *dx, int64_t stride, double
   out[0] = cnt; out[1] = shift + mean_s;
   out[2] = cnt > 1 ? (sumsq - cnt * mean_s * mean_s) / (cnt - 1) : 0.0;
   out[3] = mn; out[4] = mx;
+  // the non-finite rule of rsf_abi.h.  A NaN sample already makes both sums NaN; one infinite sample leaves sum = +-inf (a mean of
+  // +-inf, and a variance of 0 at n = 1) unless x[0] is that sample: NaN in every case.  fmin/fmax skip NaN samples, so min and
+  // max are those of the others, and the reduction's start values survive only when every sample is NaN.
+  if (!std::isfinite(sum) || !std::isfinite(sumsq)) out[1] = out[2] = NAN;
+  if (mn > mx) out[3] = out[4] = NAN;
   return RSF_OK;
 }
 
@@ -73,6 +78,7 @@ int rsf_pool_kde(rsf_ctx *c, int64_t n, const double *x, int64_t stride, int32_t
   if ((rc = pool_moments(c, n, dx, stride, s))) return rc;
   const double factor = bw_factor > 0.0 ? bw_factor : std::pow((double)n, -1.0 / 5.0);  // scipy scotts_factor, d = 1
   const double cov = s[2] * factor * factor;
+  if (!std::isfinite(s[2])) return fail(RSF_ERR_INVALID, "rsf_pool_kde: a non-finite draw (or a variance beyond the range of a double)");
   if (!(cov > 0.0)) return fail(RSF_ERR_INVALID, "rsf_pool_kde: the samples have zero variance (singular KDE)");
   const int blocks = (int)std::min<int64_t>(kPoolBlocks, (n + kKdeTile - 1) / kKdeTile);
   DevBuf &ws = c->poolws;

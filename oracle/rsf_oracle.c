@@ -1006,16 +1006,21 @@ int rsf_mcmc_counters(rsf_ctx *c, int64_t *out, int32_t n) {
 /* ------------------------------------------------------------------------------------ */
 int rsf_pool_summary(rsf_ctx *c, int64_t n, const double *x, int64_t stride, double *out) {
   if (!c || !x || !out || n < 1 || stride < 1) return fail(RSF_ERR_INVALID, "rsf_pool_summary: bad argument");
-  double mean = 0.0, mn = x[0], mx = x[0], ss = 0.0;
+  double mean = 0.0, mn = INFINITY, mx = -INFINITY, ss = 0.0;
+  int finite = 1;
   for (int64_t i = 0; i < n; ++i) {
     double v = x[i * stride];
     mean += v;
-    if (v < mn) mn = v;
+    if (!isfinite(v)) finite = 0;
+    if (v < mn) mn = v;   /* a NaN compares false: min and max are those of the other samples */
     if (v > mx) mx = v;
   }
   mean /= (double)n;
   for (int64_t i = 0; i < n; ++i) { double dlt = x[i * stride] - mean; ss += dlt * dlt; }  /* two-pass, like np.cov */
   out[0] = (double)n; out[1] = mean; out[2] = n > 1 ? ss / (double)(n - 1) : 0.0; out[3] = mn; out[4] = mx;
+  /* the non-finite rule of include/rsf_abi.h: one NaN or infinite sample makes mean and variance NaN; all NaN: min, max too */
+  if (!finite) out[1] = out[2] = NAN;
+  if (mn > mx) out[3] = out[4] = NAN;
   return RSF_OK;
 }
 
@@ -1027,6 +1032,7 @@ int rsf_pool_kde(rsf_ctx *c, int64_t n, const double *x, int64_t stride, int32_t
   if (rc) return rc;
   double factor = bw_factor > 0.0 ? bw_factor : pow((double)n, -1.0 / 5.0);  /* scipy scotts_factor, d = 1 */
   double cov = s[2] * factor * factor;
+  if (!isfinite(s[2])) return fail(RSF_ERR_INVALID, "rsf_pool_kde: a non-finite draw (or a variance beyond the range of a double)");
   if (!(cov > 0.0)) return fail(RSF_ERR_INVALID, "rsf_pool_kde: the samples have zero variance (singular KDE)");
   double norm = 1.0 / ((double)n * sqrt(2.0 * 3.14159265358979323846 * cov)), inv2c = 0.5 / cov;
   int nt = nthreads(c);

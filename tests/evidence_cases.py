@@ -36,6 +36,9 @@ PROPOSALS = (
 )
 
 BRIDGE_SIZES = ((1, 1), (5, 3), (1037, 16421))
+# past the cap of evidence_terms_kernel's grid (1024 workgroups x 256 threads): a second trip of the grid-stride loop in 257 threads
+# only, and a third; each size once as the posterior draws' set and once as the proposal draws'
+BRIDGE_SIZES_CAPPED = ((262144 + 257, 2 * 262144 + 77), (2 * 262144 + 77, 262144 + 257))
 
 
 def crafted_l(n1, n2, seed=7):

@@ -18,6 +18,12 @@ Bounds of the GPU tests, from the issue that introduced the feature:
 import numpy as np
 
 SIZES = (3, 5, 1037, 16421)   # 1037 crosses one 1024-sample tile; 16421 spans many slices and leaves an uneven tail
+# past the cap of 1024 workgroups x 256 threads, where the grid-stride loops of pool_joint_moments_kernel and pool_hist2d_kernel take a
+# second trip (in 257 threads only) and a third: kept out of SIZES, so that the parametrised matrix does not grow
+SIZES_CAPPED = (262144 + 257, 2 * 262144 + 77)
+# pool_kde2d_kernel past one 1024-sample tile a slice: m = 1 → 1024 slices of 1025 samples (a second tile of one sample; the last slice
+# holds 2); m = 1031 → two chunks, 512 slices of 2049 samples, three tiles each
+N_MULTI_TILE = (1 << 20) + 1
 MEAN3 = np.array([1000.0, 0.011, 0.006])
 TOL_MEAN_SD = 1e-13
 TOL_COV = 1e-11

@@ -98,6 +98,24 @@ def test_bridge_reduction(pkg, gpu_engine, n1, n2):
         np.testing.assert_array_equal(gpu_engine.evidence_partials(l1, l2, lstar, 0.37), got)
 
 
+@pytest.mark.parametrize("n1,n2", cases.BRIDGE_SIZES_CAPPED)
+def test_bridge_partials_past_the_grid_cap(pkg, gpu_engine, n1, n2):
+    """evidence_terms_kernel where its grid-stride loop takes a second and a third trip, at the bound of test_bridge_reduction."""
+    l1, l2, lstar = cases.crafted_l(n1, n2)
+    left_out = int(np.isneginf(l2).sum())
+    assert left_out > n2 // 20
+    for r in (1.0, 0.37):
+        got, want = gpu_engine.evidence_partials(l1, l2, lstar, r), ref.partials(l1, l2, lstar, r, dtype=LD).astype(np.float64)
+        np.testing.assert_array_equal(got[:3], want[:3])
+        assert got[0] == n1 and got[1] == n2 and got[2] == n2 - left_out
+        nz = want[3:] != 0
+        e = float(np.abs((got[3:][nz] - want[3:][nz]) / want[3:][nz]).max())
+        print(f"({n1}, {n2}) r {r}: partials {e:.3e} (relative), {left_out} proposal draws left out")
+        assert nz.all() and e <= cases.TOL_PARTIAL and np.isfinite(got).all()
+    with pkg.Engine(mem="device") as dev:
+        np.testing.assert_array_equal(dev.evidence_partials(l1, l2, lstar, 0.37), got)
+
+
 def test_bridge_without_a_draw_in_the_support(gpu_engine):
     l1, _, lstar = cases.crafted_l(1037, 5)
     res = gpu_engine.evidence_bridge(l1, np.full(257, -np.inf), lstar=lstar, shape=12.0, lo=[0.0], hi=[1.3])

@@ -87,6 +87,21 @@ def test_moments(gpu_engine, dev_engine, d, n):
         assert np.array_equal(gpu_engine.pool_joint_partials(x, center), part)
 
 
+@pytest.mark.parametrize("n", cases.SIZES_CAPPED)
+@pytest.mark.parametrize("d", [3, 8])
+def test_moments_past_the_grid_cap(gpu_engine, dev_engine, d, n):
+    """The second and third trip of the grid-stride loop, in the unrolled (d = 3) and the run-time (d = 8) instantiation."""
+    import torch
+
+    x = _block(None, None, "synthetic", n, d)
+    cases.check_center(x, x[0])
+    got = gpu_engine.pool_joint(x)
+    assert got["n"] == n and got["nonfinite"] == 0
+    cases.check_moments(got, ref.moments(x, x[0]), f"moments d={d} n={n} (capped grid) centre first row")
+    part = gpu_engine.pool_joint_partials(x)
+    assert np.array_equal(dev_engine.pool_joint_partials(torch.tensor(x, device="cuda")), part)
+
+
 def test_moments_of_real_draws(pkg, oracle_lib, gpu_engine):
     for n in (1037, 16421):
         x = _block(pkg, oracle_lib, "real", n)
@@ -219,6 +234,22 @@ def test_kde2d_shards_add(gpu_engine):
     assert np.all(np.abs(same - whole) <= cases.RTOL_SHARDS * whole)
 
 
+def test_kde2d_slices_of_more_than_one_tile(gpu_engine):
+    """n = 2^20 + 1 (joint_cases.N_MULTI_TILE): the first sizes at which a slice of pool_kde2d_kernel streams more than one tile."""
+    n = cases.N_MULTI_TILE
+    x = _block(None, None, "synthetic", n, 3)
+    pair = (0, 1)
+    x2 = np.ascontiguousarray(x[:, list(pair)])
+    one = _points(x2, "one")
+    cases.check_kde(gpu_engine.pool_kde2d(x, one, params=pair), _kde_ref(("syn", n, pair, "one"), x2, one), f"kde2d n={n} m=1: 1024 slices of 1025")
+    pts = _points(x2, "m1031")
+    got = gpu_engine.pool_kde2d(x, pts, params=pair)
+    assert got.shape == (1031,) and np.isfinite(got).all() and np.all(got >= 0)
+    idx = [0, 255, 1024, 1030]   # the first chunk's first and second register point, the second chunk's first and last thread
+    want = _kde_ref(("syn", n, pair, "m1031", tuple(idx)), x2, pts[idx])
+    cases.check_kde(got[idx], want, f"kde2d n={n} m=1031 (512 slices of 2049, three tiles each), points {idx}")
+
+
 def test_kde2d_refuses(pkg, gpu_engine):
     x = cases.synthetic(1037, 3).copy()
     pts = x[:4, :2].copy()
@@ -270,6 +301,18 @@ def test_histogram2d_edge_block(gpu_engine, dev_engine, nbins):
     assert np.array_equal(a + b, want)
     t = gpu_engine.pool_histogram2d(x, (nby, nbx), ranges[::-1], params=(2, 0))
     assert np.array_equal(t, want.T)
+
+
+@pytest.mark.parametrize("n", cases.SIZES_CAPPED)
+def test_histogram2d_past_the_grid_cap(gpu_engine, n):
+    nbx, nby = 20, 16
+    x, ranges = cases.edge_block(n, nbx, nby, 23)
+    got = gpu_engine.pool_histogram2d(x, (nbx, nby), ranges, params=(0, 2))
+    assert got.shape == (nbx + 2, nby + 2) and got.sum() == n
+    fin = np.isfinite(x[:, 0]) & np.isfinite(x[:, 2])
+    assert np.array_equal(got[1:-1, 1:-1], np.histogram2d(x[fin, 0], x[fin, 2], (nbx, nby), ranges)[0])
+    assert np.array_equal(got, ref.hist2d(x[:, 0], x[:, 2], nbx, nby, *ranges[0], *ranges[1]))
+    assert got[0].sum() > 0 and got[-1].sum() > 0 and got[:, 0].sum() > 0 and got[:, -1].sum() > 0
 
 
 def test_histogram2d_blocks_and_int_nbins(pkg, oracle_lib, gpu_engine):
