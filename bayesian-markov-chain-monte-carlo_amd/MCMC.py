@@ -508,29 +508,46 @@ class MCMC:
         rate = stats["accepted"] / max(1, n_iters * n_chains)
         return PosteriorPool(samples, std2, rate, stats, nburn, superchain_size=S)
 
-    def sample_smc(self, n_particles, seed=0, ess_fraction=0.5, steps=3, max_stages=200, mem="device", device=-1, offset=0):
+    @staticmethod
+    def _smc_pool(res, extra=None):
+        """One result of Engine.smc (or one run of Engine.smc_batch), its arrays on the host → the PosteriorPool of sample_smc."""
+        q, std2, l = _host(res["q"]), _host(res["std2"]), _host(res["l"])
+        stats = {k: res[k] for k in ("log_integral", "log_evidence", "stages", "n_solves", "shape")}
+        stats["l"] = l
+        stats.update(extra or {})
+        rate = float(np.mean([s["accept_rate"] for s in res["stages"]]))
+        rows = 16 if q.shape[0] % 16 == 0 else 1
+        samples = np.ascontiguousarray(q.reshape(-1, rows, q.shape[1]).transpose(1, 0, 2))
+        return PosteriorPool(samples, np.ascontiguousarray(std2.reshape(-1, rows).T), rate, stats, 0)
+
+    def sample_smc(self, n_particles, seed=0, ess_fraction=0.5, steps=3, max_stages=200, mem="device", device=-1, offset=0, replicates=1):
         """Tempered sequential Monte Carlo (additive; Engine.smc): n_particles start uniform in the prior box and end as an
         equally weighted sample of the n0 = 0 target — no start point, no burn-in, the proposal at every stage is the population's
         own covariance.  Returns a PosteriorPool on which predictive, loo, joint, corner and evidence work unchanged.  Its layout is
         (16, n_particles / 16, d) when 16 divides n_particles — column c holds the particles 16 c .. 16 c + 15, so that the copies
         systematic resampling leaves next to each other read as the autocorrelation of one column, which is where evidence's ESS
         factor looks for it — and (1, n_particles, d) otherwise (evidence then needs a flat pool and fit_fraction).  Its stats carry log_integral, log_evidence (the constants of Engine.evidence_finish), the stage table
-        `stages`, n_solves and the particles' l = -shape log SSq.  accept_rate is the mean over the stages' Metropolis steps."""
+        `stages`, n_solves and the particles' l = -shape log SSq.  accept_rate is the mean over the stages' Metropolis steps.
+        replicates > 1: that many independent populations, seeds seed .. seed + replicates - 1, run together (Engine.smc_batch);
+        the pool is the first one's — the run replicates = 1 gives — and its stats add replicate_log_evidence, the replicates'
+        log evidences, log_evidence_mean (the logarithm of their mean evidence) and log_evidence_se, its standard error: the error
+        bar one run's dependent particles cannot give."""
         if not self._device_model():
             raise TypeError("sample_smc integrates the model on the device: `model` must be this package's RateStateModel")
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         with Engine(mem=mem, device=device) as eng:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            if int(replicates) > 1:
+                out = eng.smc_batch(data, lo, hi, int(n_particles), seeds=int(seed), offsets=int(offset), replicates=int(replicates),
+                                    ess_fraction=ess_fraction, steps=steps, max_stages=max_stages)
+                eng.sync()
+                summ = out["summary"][0]
+                return self._smc_pool(out["runs"][0], {"replicate_log_evidence": np.array([r["log_evidence"] for r in out["runs"]]),
+                                                       "log_evidence_mean": summ["log_evidence_mean"], "log_evidence_se": summ["log_evidence_se"]})
             res = eng.smc(data, lo, hi, int(n_particles), seed=seed, offset=offset, ess_fraction=ess_fraction, steps=steps, max_stages=max_stages)
             eng.sync()
-            q, std2, l = _host(res["q"]), _host(res["std2"]), _host(res["l"])
-        stats = {k: res[k] for k in ("log_integral", "log_evidence", "stages", "n_solves", "shape")}
-        stats["l"] = l
-        rate = float(np.mean([s["accept_rate"] for s in res["stages"]]))
-        rows = 16 if q.shape[0] % 16 == 0 else 1
-        samples = np.ascontiguousarray(q.reshape(-1, rows, q.shape[1]).transpose(1, 0, 2))
-        return PosteriorPool(samples, np.ascontiguousarray(std2.reshape(-1, rows).T), rate, stats, 0)
+            return self._smc_pool(res)
 
     # ---- visualisation (off the hot path; degrades gracefully) --------------------------
     def _animate(self, qparams):

@@ -131,6 +131,28 @@ class RSF:
         self.posteriors = {dc: pool.pooled() for dc, pool in out.items()}
         return out
 
+    def inference_smc(self, n_particles, replicates=1, seed=0, mem="device", device=-1, ess_fraction=0.5, steps=3, max_stages=200):
+        """Additive: tempered SMC over the whole dc_list sweep in ONE batch (Engine.smc_batch) — every true Dc is an observation
+        group with `replicates` independent populations of n_particles (seeds seed .. seed + replicates - 1), no start point and
+        no burn-in, so the Dc far from qstart cost no more than the others.  Returns {dc: PosteriorPool} of each group's first
+        replicate (MCMC.sample_smc's pool); its stats carry replicate_log_evidence, log_evidence_mean and log_evidence_se over the
+        group's replicates (se NaN for one).  The `inference` path is not touched."""
+        n, G = self.model.num_tsteps, len(self.dc_list)
+        data = np.ascontiguousarray(np.asarray(self.data, dtype=np.float64).reshape(G, n))
+        probe = MCMC(self.model, data[0], self.dc_list[0], self.qpriors, self.qstart, nsamples=10)
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            res = eng.smc_batch(data, probe.qstart_limits[:, 0], probe.qstart_limits[:, 1], int(n_particles), seeds=int(seed),
+                                replicates=int(replicates), ess_fraction=ess_fraction, steps=steps, max_stages=max_stages)
+            eng.sync()
+            out = {}
+            for g, (dc, summ) in enumerate(zip(self.dc_list, res["summary"])):
+                runs = res["runs"][g * int(replicates):(g + 1) * int(replicates)]
+                out[float(dc)] = MCMC._smc_pool(runs[0], {"replicate_log_evidence": np.array([r["log_evidence"] for r in runs]),
+                                                          "log_evidence_mean": summ["log_evidence_mean"], "log_evidence_se": summ["log_evidence_se"]})
+        self.posteriors = {dc: pool.pooled() for dc, pool in out.items()}
+        return out
+
     @measure_execution_time
     def inference(self, nsamples):
         data = self.prepare_data(self.data)

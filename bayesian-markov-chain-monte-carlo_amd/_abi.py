@@ -236,6 +236,21 @@ SMC_ROUNDS = 6           # Engine.smc: rounds of the 16-section search for the n
 SMC_RESAMPLE_COUNTER = (0xFFFFFFFF, 0xFFFFFFFF, 4)  # Philox counter (particle lo, particle hi, ., slot) of a stage's resampling uniform
 
 
+# include/rsf_smc_batch.h: P independent SMC populations per call; exported by librsf_hip.so only, bound by load().  The
+# per-population parameter arrays are host arrays and travel as typed pointers, the particles as raw addresses
+_U64P, _I64P, _I32P, _U8P, _DP = POINTER(c_uint64), POINTER(c_int64), POINTER(c_int32), POINTER(c_uint8), POINTER(c_double)
+SMC_BATCH_PROTOTYPES = {
+    "rsf_smc_batch_init": (c_int, [c_void_p, c_int32, c_int64, c_int32, _DP, _DP, _U64P, _I64P, _P]),
+    "rsf_smc_batch_logtarget": (c_int, [c_void_p, c_int32, c_int64, c_int32, _P, _P, c_int32, _I32P, c_double, _DP, _DP, _P]),
+    "rsf_smc_batch_weight_sums": (c_int, [c_void_p, c_int32, c_int64, _P, c_int32, _DP, _DP, _U8P, _DP]),
+    "rsf_smc_batch_resample": (c_int, [c_void_p, c_int32, c_int64, c_int32, _P, _P, _DP, _DP, _DP, _U8P, _P, _P, _P, _P]),
+    "rsf_smc_batch_move": (c_int, [c_void_p, c_int32, c_int64, c_int32, _P, _P, _P, c_int32, _I32P, c_double, _DP, _DP, _DP, _DP, _U64P, _I64P,
+                                   _I64P, c_int32, _U8P, _I64P]),
+    "rsf_smc_batch_std2": (c_int, [c_void_p, c_int32, c_int64, _P, c_double, _U64P, _I64P, _I64P, _P]),
+}
+SMC_BATCH_MAX = 64  # RSF_SMC_BATCH_MAX: populations per call
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -280,7 +295,7 @@ def load():
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
-                      SMC_PROTOTYPES):
+                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

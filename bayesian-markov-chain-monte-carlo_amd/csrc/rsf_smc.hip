@@ -1,11 +1,15 @@
 // rsf_smc.hip — tempered sequential Monte Carlo over the box prior (include/rsf_smc.h): rsf_smc_init / _weight_sums / _resample /
 // _move / _move_propose / _move_accept / _std2 (kernels: rsf_kernels_smc.h).  rsf_smc_section, rsf_smc_increment and
-// rsf_smc_log_evidence, the host arithmetic, are in rsf_finish.cpp.
+// rsf_smc_log_evidence, the host arithmetic, are in rsf_finish.cpp.  Behind them the same calls for P independent populations per
+// launch (include/rsf_smc_batch.h: rsf_smc_batch_init / _logtarget / _weight_sums / _resample / _move / _std2; kernels:
+// rsf_kernels_smc_batch.h, which needs the chain logic of rsf_kernels_smc.h and therefore lives in this unit).
 #include <cmath>
+#include <cstdio>
 #include <algorithm>
 
 #include "rsf_host.h"
 #include "rsf_kernels_smc.h"
+#include "rsf_kernels_smc_batch.h"
 
 using namespace rsfk;
 using namespace rsfh;
@@ -241,6 +245,284 @@ int rsf_smc_std2(rsf_ctx *c, int64_t n, const double *l, double shape, uint64_t 
   if ((rc = stage_out(c, SLOT_SMC_L_OUT, std2, nb, &ds))) return rc;
   const double gd = shape - 1.0 / 3.0;
   if ((rc = launch(c, smc_std2_kernel, blocks_of(n), kMaxBlock, 0, A, gd, 1.0 / std::sqrt(9.0 * gd), dl, ds))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L_OUT, std2, nb))) return rc;
+  return finish(c);
+}
+
+}  // extern "C"
+
+// ---- P independent populations per call (include/rsf_smc_batch.h) ------------------------------------------------------------------
+namespace {
+
+// "<entry point>: population p", what the single calls' checks name in a message about one population
+struct Who {
+  char s[96];
+  Who(const char *fn, int p) { snprintf(s, sizeof s, "%s: population %d", fn, p); }
+};
+
+int check_batch(const char *fn, int32_t P, int64_t n) {
+  if (P < 1 || P > RSF_SMC_BATCH_MAX) return fail(RSF_ERR_INVALID, "%s: need 1 <= P <= %d populations", fn, RSF_SMC_BATCH_MAX);
+  if (n < 1) return fail(RSF_ERR_INVALID, "%s: need n >= 1", fn);
+  return RSF_OK;
+}
+
+int set_groups(const char *fn, int32_t P, int32_t G, const int32_t *group, const uint8_t *active, SmcPop *pops) {
+  if (G < 1) return fail(RSF_ERR_INVALID, "%s: need G >= 1 observation series", fn);
+  for (int p = 0; p < P; ++p) {
+    if (active && !active[p]) continue;
+    if (group[p] < 0 || group[p] >= G) return fail(RSF_ERR_INVALID, "%s: population %d: group %d is outside 0..%d", fn, p, group[p], G - 1);
+    pops[p].group = group[p];
+  }
+  return RSF_OK;
+}
+
+// The populations' parameters on the device (the ctx's second pool workspace).  The source is pageable host memory, which the
+// runtime has read when the copy call returns (as rsf_set_model's table): the caller's array may go out of scope.
+int put_pops(rsf_ctx *c, int32_t P, const SmcPop *pops, const SmcPop **dev) {
+  int rc;
+  if ((rc = ensure(c->poolws, sizeof(SmcPop) * RSF_SMC_BATCH_MAX))) return rc;
+  HIP_TRY(hipMemcpyAsync(c->poolws.p, pops, sizeof(SmcPop) * P, hipMemcpyHostToDevice, c->stream));
+  *dev = (const SmcPop *)c->poolws.p;
+  return RSF_OK;
+}
+
+// rows [p] of `bytes` each of an output staged in `slot`, back to a host caller for the active populations only
+int copy_back_active(rsf_ctx *c, Slot slot, void *dst, size_t bytes, int32_t P, const uint8_t *active) {
+  if (!host_mem(c)) return RSF_OK;
+  for (int p = 0; p < P; ++p)
+    if (active[p])
+      HIP_TRY(hipMemcpyAsync((char *)dst + p * bytes, (const char *)c->stage[slot].p + p * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
+  return RSF_OK;
+}
+
+auto batch_init_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return smc_batch_init_kernel<D>; }); }
+auto batch_logtarget_fn(const rsf_ctx *c, int d) {
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return smc_batch_logtarget_kernel<D, DAMP>; }); });
+}
+auto batch_move_fn(const rsf_ctx *c, int d) {
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return smc_batch_move_kernel<D, DAMP>; }); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsf_smc_batch_init(rsf_ctx *c, int32_t P, int64_t n, int32_t d, const double *lo, const double *hi, const uint64_t *seeds,
+                       const int64_t *offsets, double *q) {
+  RSF_ENTER(c, NEED_NOTHING, lo && hi && seeds && offsets && q, "NULL argument");
+  int rc;
+  if ((rc = check_batch(__func__, P, n))) return rc;
+  if (d < 1 || d > RSF_SMC_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_smc_batch_init: need 1 <= d <= %d", RSF_SMC_MAX_PARAMS);
+  SmcArgs A{}, S{};
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  A.n = n;
+  SmcPop pops[RSF_SMC_BATCH_MAX] = {};
+  for (int p = 0; p < P; ++p) {
+    if ((rc = set_stream(Who(__func__, p).s, n, offsets[p], 0, 0, seeds[p], S))) return rc;
+    pops[p].seed = S.seed; pops[p].offset = S.offset; pops[p].iter = S.iter;
+  }
+  const SmcPop *dp;
+  const size_t nb = (size_t)P * n * d * sizeof(double);
+  double *dq;
+  if ((rc = put_pops(c, P, pops, &dp))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_Q, q, nb, &dq))) return rc;
+  if ((rc = launch(c, batch_init_fn(d), dim3(blocks_of(n), P), kMaxBlock, 0, A, dp, dq))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q, q, nb))) return rc;
+  return finish(c);
+}
+
+int rsf_smc_batch_logtarget(rsf_ctx *c, int32_t P, int64_t n, int32_t d, const double *q, const double *data, int32_t G,
+                            const int32_t *group, double shape, const double *lo, const double *hi, double *l) {
+  RSF_ENTER(c, NEED_MODEL, q && data && group && lo && hi && l, "NULL argument");
+  int rc;
+  if ((rc = check_batch(__func__, P, n))) return rc;
+  if (d != 1 && d != 3) return fail(RSF_ERR_INVALID, "rsf_smc_batch_logtarget: need d = 1 or 3");
+  if (!std::isfinite(shape) || !(shape > 0.0)) return fail(RSF_ERR_INVALID, "rsf_smc_batch_logtarget: shape must be finite and > 0");
+  if (c->m.flags & RSF_FLAG_DOP853)
+    return fail(RSF_ERR_UNSUPPORTED, "rsf_smc_batch_logtarget: a model flagged RSF_FLAG_DOP853 is not supported (the solve is the float64 RK4)");
+  SmcArgs A{};
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  A.n = n; A.shape = shape;
+  SmcPop pops[RSF_SMC_BATCH_MAX] = {};
+  if ((rc = set_groups(__func__, P, G, group, nullptr, pops))) return rc;
+  const SmcPop *dp;
+  const size_t nb = (size_t)P * n * sizeof(double);
+  const double *dq, *ddata;
+  double *dl;
+  if ((rc = put_pops(c, P, pops, &dp))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_Q, q, nb * d, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_OBS, data, (size_t)G * c->nout * sizeof(double), &ddata))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_L, l, nb, &dl))) return rc;
+  if ((rc = launch(c, batch_logtarget_fn(c, d), dim3(grid_for(c, n), P), c->block, c->lds_bytes, make_consts(c, ddata), A, dp, dq, dl))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L, l, nb))) return rc;
+  return finish(c);
+}
+
+int rsf_smc_batch_weight_sums(rsf_ctx *c, int32_t P, int64_t n, const double *l, int32_t m, const double *deltas, const double *lmax,
+                              const uint8_t *active, double *out) {
+  RSF_ENTER(c, NEED_NOTHING, l && deltas && lmax && active && out, "NULL argument");
+  int rc;
+  if ((rc = check_batch(__func__, P, n))) return rc;
+  if (m < 1 || m > RSF_SMC_MAX_CANDIDATES) return fail(RSF_ERR_INVALID, "rsf_smc_batch_weight_sums: need 1 <= m <= %d", RSF_SMC_MAX_CANDIDATES);
+  SmcPop pops[RSF_SMC_BATCH_MAX] = {};
+  for (int p = 0; p < P; ++p) {
+    if (!(pops[p].active = active[p] != 0)) continue;
+    if (std::isinf(lmax[p])) return fail(RSF_ERR_INVALID, "rsf_smc_batch_weight_sums: population %d: lmax is finite, or NaN for the largest finite l", p);
+    pops[p].lmax = lmax[p];
+    for (int k = 0; k < m; ++k) {
+      const double v = deltas[(size_t)p * m + k];
+      if (!std::isfinite(v) || v < 0.0) return fail(RSF_ERR_INVALID, "rsf_smc_batch_weight_sums: population %d: deltas[%d] is not finite and >= 0", p, k);
+      pops[p].dl[k] = v;
+    }
+  }
+  const SmcPop *dp;
+  const double *dl_l;
+  if ((rc = put_pops(c, P, pops, &dp))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_L, l, (size_t)P * n * sizeof(double), &dl_l))) return rc;
+  // workspace, doubles: sums[P][kSmcFields] | head[P][kSmcHead] | the workgroups' partials of the sums [P][blocks][..] | ... of the head
+  const int blocks = (int)std::min<int64_t>(kSmcBlocks, (n + kMaxBlock - 1) / kMaxBlock);
+  if ((rc = ensure(c->pool, sizeof(double) * (kSmcFields + kSmcHead) * (size_t)P * (blocks + 1)))) return rc;
+  double *ws = (double *)c->pool.p, *head = ws + (size_t)kSmcFields * P, *part = head + (size_t)kSmcHead * P, *parth = part + (size_t)kSmcFields * P * blocks;
+  if ((rc = launch(c, smc_batch_max_kernel, dim3(blocks, P), kMaxBlock, 0, n, dp, dl_l, parth))) return rc;
+  if ((rc = launch(c, smc_batch_max_finish_kernel, P, kMaxBlock, 0, blocks, dp, parth, head))) return rc;
+  // a population without a finite l has the head -inf: its sums are computed and not used (the check below refuses the call)
+  if ((rc = launch(c, smc_batch_weight_sums_kernel, dim3(blocks, P), kMaxBlock, 0, n, dp, dl_l, head, part))) return rc;
+  if ((rc = launch(c, smc_batch_tree_kernel, dim3(kSmcFields, P), kMaxBlock, 0, blocks, kSmcFields, dp, part, ws))) return rc;
+  double h[RSF_SMC_BATCH_MAX * (kSmcFields + kSmcHead)];
+  HIP_TRY(hipMemcpyAsync(h, ws, sizeof(double) * (kSmcFields + kSmcHead) * P, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const double *hs = h, *hh = h + (size_t)kSmcFields * P;
+  for (int p = 0; p < P; ++p) {
+    if (!active[p]) continue;
+    const double *e = hh + p * kSmcHead;
+    if (e[1] + e[2] != (double)n)
+      return fail(RSF_ERR_INVALID, "rsf_smc_batch_weight_sums: population %d: %lld of l are NaN or +inf", p, (long long)((double)n - e[1] - e[2]));
+    if (!(e[1] > 0.0))
+      return fail(RSF_ERR_INVALID, "rsf_smc_batch_weight_sums: population %d: every particle has l = -inf (no particle lies in the target's support)", p);
+  }
+  for (int p = 0; p < P; ++p) {
+    if (!active[p]) continue;
+    double *o = out + (size_t)p * (RSF_SMC_HEAD + 2 * m);
+    const double *e = hh + p * kSmcHead;
+    o[0] = std::isnan(lmax[p]) ? e[0] : lmax[p]; o[1] = e[1]; o[2] = e[2];
+    for (int k = 0; k < 2 * m; ++k) o[RSF_SMC_HEAD + k] = hs[p * kSmcFields + k];
+  }
+  return RSF_OK;
+}
+
+int rsf_smc_batch_resample(rsf_ctx *c, int32_t P, int64_t n, int32_t d, const double *q, const double *l, const double *delta,
+                           const double *lmax, const double *u, const uint8_t *active, double *cum, int64_t *anc, double *q_out,
+                           double *l_out) {
+  RSF_ENTER(c, NEED_NOTHING, q && l && delta && lmax && u && active && cum && anc && q_out && l_out, "NULL argument");
+  int rc;
+  if ((rc = check_batch(__func__, P, n))) return rc;
+  if (d < 1 || d > RSF_SMC_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_smc_batch_resample: need 1 <= d <= %d", RSF_SMC_MAX_PARAMS);
+  SmcPop pops[RSF_SMC_BATCH_MAX] = {};
+  for (int p = 0; p < P; ++p) {
+    if (!(pops[p].active = active[p] != 0)) continue;
+    if (!std::isfinite(delta[p]) || delta[p] < 0.0 || !std::isfinite(lmax[p]) || !(u[p] > 0.0 && u[p] <= 1.0))
+      return fail(RSF_ERR_INVALID, "rsf_smc_batch_resample: population %d: need finite delta >= 0, finite lmax and u inside (0, 1]", p);
+    pops[p].delta = delta[p]; pops[p].lmax = lmax[p]; pops[p].u = u[p];
+  }
+  const SmcPop *dp;
+  const size_t nb = (size_t)n * sizeof(double);
+  const double *dq, *dl;
+  double *dcum, *dqo, *dlo;
+  int64_t *danc;
+  if ((rc = put_pops(c, P, pops, &dp))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_Q, q, nb * d * P, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_L, l, nb * P, &dl))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_CUM, cum, nb * P, &dcum))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_ANC, anc, (size_t)n * sizeof(int64_t) * P, &danc))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_Q_OUT, q_out, nb * d * P, &dqo))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_L_OUT, l_out, nb * P, &dlo))) return rc;
+  const int64_t ntiles = (n + kSmcTile - 1) / kSmcTile;
+  if ((rc = ensure(c->pool, sizeof(double) * (size_t)ntiles * P))) return rc;
+  double *tsum = (double *)c->pool.p;
+  if ((rc = launch(c, smc_batch_scan_tiles_kernel, dim3((unsigned)ntiles, P), kMaxBlock, 0, n, dp, dl, tsum))) return rc;
+  if ((rc = launch(c, smc_batch_scan_carry_kernel, P, 64, 0, ntiles, dp, tsum))) return rc;
+  if ((rc = launch(c, smc_batch_scan_final_kernel, dim3((unsigned)ntiles, P), kMaxBlock, 0, n, dp, dl, tsum, dcum))) return rc;
+  if ((rc = launch(c, smc_batch_ancestor_kernel, dim3(blocks_of(n), P), kMaxBlock, 0, n, dp, dcum, danc))) return rc;
+  if ((rc = launch(c, smc_batch_gather_kernel, dim3(blocks_of(n), P), kMaxBlock, 0, n, d, dp, danc, dq, dl, dqo, dlo))) return rc;
+  if ((rc = copy_back_active(c, SLOT_SMC_CUM, cum, nb, P, active))) return rc;
+  if ((rc = copy_back_active(c, SLOT_SMC_ANC, anc, (size_t)n * sizeof(int64_t), P, active))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q_OUT, q_out, nb * d * P))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L_OUT, l_out, nb * P))) return rc;
+  return finish(c);
+}
+
+int rsf_smc_batch_move(rsf_ctx *c, int32_t P, int64_t n, int32_t d, double *q, double *l, const double *data, int32_t G,
+                       const int32_t *group, double shape, const double *lo, const double *hi, const double *chol, const double *beta,
+                       const uint64_t *seeds, const int64_t *offsets, const int64_t *iter0, int32_t steps, const uint8_t *active,
+                       int64_t *accepted) {
+  RSF_ENTER(c, NEED_MODEL, q && l && data && group && lo && hi && chol && beta && seeds && offsets && iter0 && active && accepted, "NULL argument");
+  int rc;
+  if ((rc = check_batch(__func__, P, n))) return rc;
+  if (d != 1 && d != 3) return fail(RSF_ERR_INVALID, "rsf_smc_batch_move: need d = 1 or 3");
+  if (!std::isfinite(shape) || !(shape > 0.0)) return fail(RSF_ERR_INVALID, "rsf_smc_batch_move: shape must be finite and > 0");
+  if (steps < 1 || steps > RSF_SMC_MAX_STEPS) return fail(RSF_ERR_INVALID, "rsf_smc_batch_move: need 1 <= steps <= %d", RSF_SMC_MAX_STEPS);
+  if (c->m.flags & RSF_FLAG_DOP853)
+    return fail(RSF_ERR_UNSUPPORTED, "rsf_smc_batch_move: a model flagged RSF_FLAG_DOP853 is not supported (the solve is the float64 RK4)");
+  SmcArgs A{}, S{};
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  A.n = n; A.steps = steps; A.shape = shape;
+  SmcPop pops[RSF_SMC_BATCH_MAX] = {};
+  if ((rc = set_groups(__func__, P, G, group, active, pops))) return rc;
+  for (int p = 0; p < P; ++p) {
+    if (!(pops[p].active = active[p] != 0)) continue;
+    const Who who(__func__, p);
+    if (!std::isfinite(beta[p]) || !(beta[p] > 0.0)) return fail(RSF_ERR_INVALID, "%s: beta must be finite and > 0", who.s);
+    if ((rc = set_stream(who.s, n, offsets[p], iter0[p], 1, seeds[p], S))) return rc;
+    if ((rc = set_factor(who.s, d, chol + (size_t)p * d * d, S))) return rc;
+    pops[p].seed = S.seed; pops[p].offset = S.offset; pops[p].iter = S.iter; pops[p].beta = beta[p];
+    for (int k = 0; k < d * (d + 1) / 2; ++k) pops[p].L[k] = S.L[k];
+  }
+  const SmcPop *dp;
+  const size_t nb = (size_t)P * n * sizeof(double);
+  const double *dq, *dl, *ddata;
+  if ((rc = put_pops(c, P, pops, &dp))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_Q, (const double *)q, nb * d, &dq))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_L, (const double *)l, nb, &dl))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_OBS, data, (size_t)G * c->nout * sizeof(double), &ddata))) return rc;
+  // the accepted counts cnt[P][steps]: zeroed before the launch, read after it (the pool workspace's first bytes)
+  const size_t cb = sizeof(unsigned long long) * (size_t)P * steps;
+  if ((rc = ensure(c->pool, sizeof(unsigned long long) * RSF_SMC_BATCH_MAX * RSF_SMC_MAX_STEPS))) return rc;
+  unsigned long long *cnt = (unsigned long long *)c->pool.p;
+  HIP_TRY(hipMemsetAsync(cnt, 0, cb, c->stream));
+  if ((rc = launch(c, batch_move_fn(c, d), dim3(grid_for(c, n), P), c->block, c->lds_bytes, make_consts(c, ddata), A, dp, (double *)dq, (double *)dl, cnt)))
+    return rc;
+  if ((rc = copy_back(c, SLOT_SMC_Q, q, nb * d))) return rc;
+  if ((rc = copy_back(c, SLOT_SMC_L, l, nb))) return rc;
+  static thread_local unsigned long long h[RSF_SMC_BATCH_MAX * RSF_SMC_MAX_STEPS];
+  HIP_TRY(hipMemcpyAsync(h, cnt, cb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int p = 0; p < P; ++p)
+    for (int s = 0; active[p] && s < steps; ++s) accepted[(size_t)p * steps + s] = (int64_t)h[(size_t)p * steps + s];
+  return RSF_OK;
+}
+
+int rsf_smc_batch_std2(rsf_ctx *c, int32_t P, int64_t n, const double *l, double shape, const uint64_t *seeds, const int64_t *offsets,
+                       const int64_t *iter, double *std2) {
+  RSF_ENTER(c, NEED_NOTHING, l && seeds && offsets && iter && std2, "NULL argument");
+  int rc;
+  if ((rc = check_batch(__func__, P, n))) return rc;
+  if (!std::isfinite(shape) || !(shape >= 1.0)) return fail(RSF_ERR_INVALID, "rsf_smc_batch_std2: shape must be finite and >= 1 (the gamma variate's range)");
+  SmcArgs A{}, S{};
+  A.n = n; A.shape = shape;
+  SmcPop pops[RSF_SMC_BATCH_MAX] = {};
+  for (int p = 0; p < P; ++p) {
+    if ((rc = set_stream(Who(__func__, p).s, n, offsets[p], iter[p], 0, seeds[p], S))) return rc;
+    pops[p].seed = S.seed; pops[p].offset = S.offset; pops[p].iter = S.iter;
+  }
+  const SmcPop *dp;
+  const size_t nb = (size_t)P * n * sizeof(double);
+  const double *dl;
+  double *ds;
+  if ((rc = put_pops(c, P, pops, &dp))) return rc;
+  if ((rc = stage_in(c, SLOT_SMC_L, l, nb, &dl))) return rc;
+  if ((rc = stage_out(c, SLOT_SMC_L_OUT, std2, nb, &ds))) return rc;
+  const double gd = shape - 1.0 / 3.0;
+  if ((rc = launch(c, smc_batch_std2_kernel, dim3(blocks_of(n), P), kMaxBlock, 0, A, dp, gd, 1.0 / std::sqrt(9.0 * gd), dl, ds))) return rc;
   if ((rc = copy_back(c, SLOT_SMC_L_OUT, std2, nb))) return rc;
   return finish(c);
 }

@@ -127,6 +127,98 @@ def _model_struct(model, substeps):
     return m
 
 
+def _pop_array(x, P, dtype, what):
+    """x, a scalar or P values, as a contiguous (P,) array of dtype: one entry per SMC population."""
+    x = np.asarray(x)
+    if x.shape not in ((), (1,), (P,)):
+        raise ValueError(f"{what} has shape {x.shape}: a scalar or one entry for each of the {P} populations")
+    return np.ascontiguousarray(np.broadcast_to(x, (P,)).astype(dtype))
+
+
+def _ptr_of(a, ctype):
+    return a.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+def smc_batch_populations(n_groups, groups=None, seeds=None, offsets=None, replicates=1):
+    """The populations of Engine.smc_batch: every group of `groups` (rows of the (n_groups, nout) data; default all) x `replicates`,
+    the replicates of a group next to each other → dict(group (P,) int32 — the data row —, replicate (P,) int64, seed (P,) uint64,
+    offset (P,) int64).  seeds: None or an integer seed0 (default 0) — replicate r then has seed0 + r, what a loop over
+    Engine.smc(seed=...) uses — or one seed per replicate; offsets: a scalar (default 0) or one per replicate.  Pure NumPy."""
+    n_groups, R = int(n_groups), int(replicates)
+    if n_groups < 1 or R < 1:
+        raise ValueError("need at least one data row and replicates >= 1")
+    g = np.arange(n_groups) if groups is None else np.atleast_1d(np.asarray(groups))
+    if g.ndim != 1 or g.size < 1 or not np.issubdtype(g.dtype, np.integer) or g.min() < 0 or g.max() >= n_groups:
+        raise ValueError(f"groups is a non-empty sequence of data rows in 0..{n_groups - 1}")
+    if g.size * R > _abi.SMC_BATCH_MAX:
+        raise ValueError(f"{g.size} groups x {R} replicates exceed the {_abi.SMC_BATCH_MAX} populations of one call")
+    sd, off = np.asarray(0 if seeds is None else seeds), np.asarray(0 if offsets is None else offsets)
+    sd = int(sd) + np.arange(R) if sd.ndim == 0 else sd
+    off = np.full(R, int(off)) if off.ndim == 0 else off
+    if sd.shape != (R,) or off.shape != (R,):
+        raise ValueError(f"seeds and offsets are a scalar or one entry per replicate ({R})")
+    if (sd < 0).any() or (off < 0).any():
+        raise ValueError("seeds and offsets are >= 0")
+    return {"group": np.repeat(g, R).astype(np.int32), "replicate": np.tile(np.arange(R), g.size).astype(np.int64),
+            "seed": np.tile(sd, g.size).astype(np.uint64), "offset": np.tile(off, g.size).astype(np.int64)}
+
+
+def smc_batch_summary(log_evidence, group):
+    """log p(y | M) of replicate SMC runs, per group: log_evidence (P,) and the group (P,) each belongs to → a list, in order of
+    first appearance, of dict(group, replicates, log_evidence_mean — the logarithm of the mean evidence (log-mean-exp: the evidence
+    estimate is unbiased, its logarithm is not) —, log_evidence_sd — the sample standard deviation (ddof = 1) of the replicates'
+    log evidences —, log_evidence_se — the standard error of log_evidence_mean by the delta method, sd(Z_r / mean Z) / sqrt(R)).
+    One replicate: sd and se are NaN.  Pure NumPy."""
+    le, g = np.asarray(log_evidence, dtype=np.float64).reshape(-1), np.asarray(group).reshape(-1)
+    if le.size != g.size or le.size < 1:
+        raise ValueError("one group label for each log evidence, at least one")
+    out = []
+    for key in dict.fromkeys(g.tolist()):
+        x = le[g == key]
+        R, top = x.size, x.max()
+        ratio = np.exp(x - top)  # in (0, 1], the largest exactly 1
+        mean = top + np.log(ratio.mean())
+        rel = ratio / ratio.mean()
+        out.append({"group": key, "replicates": int(R), "log_evidence_mean": float(mean),
+                    "log_evidence_sd": float(x.std(ddof=1)) if R > 1 else float("nan"),
+                    "log_evidence_se": float(rel.std(ddof=1) / np.sqrt(R)) if R > 1 else float("nan")})
+    return out
+
+
+class _DeltaSearch:
+    """The search of Engine.smc_next_delta for one population, SMC_ROUNDS rounds of 16-section: candidates() → the steps of the next
+    read of l, update(res) with that read's smc_weight_sums → True once `out`, smc_next_delta's result, is there."""
+
+    def __init__(self, lib, beta, ess_fraction):
+        self.lib, self.beta, self.rho = lib, float(beta), float(ess_fraction)
+        self.a, self.b, self.last, self.fail, self.rnd, self.cand, self.out = 0.0, 1.0 - float(beta), None, None, 0, None, None
+
+    def candidates(self):
+        m = _abi.SMC_MAX_CANDIDATES
+        self.cand = [self.a + (self.b - self.a) * j / m for j in range(1, m + 1)]
+        return self.cand
+
+    def update(self, res):
+        m, cand, sums = _abi.SMC_MAX_CANDIDATES, self.cand, res["sums"]
+        k = ctypes.c_int32()
+        _abi.check(self.lib, self.lib.rsf_smc_section(self.rho * res["n_finite"], m, _dp(np.ascontiguousarray(sums)), ctypes.byref(k)))
+        k = k.value
+        if k:
+            self.last = (cand[k - 1], sums[k - 1])
+        if k == m and self.rnd == 0:
+            self.out = {"delta": self.b, "beta": 1.0, "lmax": res["lmax"], "sum_w": float(sums[-1, 0]), "ess": float(sums[-1, 0] ** 2 / sums[-1, 1])}
+            return True
+        if k < m:
+            self.fail = (cand[k], sums[k])
+            self.a, self.b = (cand[k - 1] if k else self.a), cand[k]
+        self.rnd += 1
+        if k == m or self.rnd == _abi.SMC_ROUNDS:
+            delta, sw = self.last if self.last is not None else self.fail
+            self.out = {"delta": delta, "beta": self.beta + delta, "lmax": res["lmax"], "sum_w": float(sw[0]), "ess": float(sw[0] ** 2 / sw[1])}
+            return True
+        return False
+
+
 def bayes_factor(ev_a, ev_b):
     """The log Bayes factor of two results of Engine.evidence / evidence_from_ssq / PosteriorPool.evidence, model a against model
     b, for the SAME observation → dict(log_bf = log_evidence_a - log_evidence_b, re = sqrt(re_a^2 + re_b^2), the approximate
@@ -768,24 +860,10 @@ class Engine:
         exp(delta (l - lmax)) at ess_fraction of the particles with a finite l, by SMC_ROUNDS rounds of 16-section, each one read of
         l (rsf_smc_weight_sums, rsf_smc_section) → dict(delta, beta (the next; exactly 1.0 at the end), lmax, sum_w, ess)."""
         x = self._in(l)
-        m = _abi.SMC_MAX_CANDIDATES
-        a, b, last, fail = 0.0, 1.0 - float(beta), None, None
-        k = ctypes.c_int32()
-        for rnd in range(_abi.SMC_ROUNDS):
-            cand = [a + (b - a) * j / m for j in range(1, m + 1)]
-            res = self.smc_weight_sums(x, cand)
-            sums = res["sums"]
-            _abi.check(self.lib, self.lib.rsf_smc_section(float(ess_fraction) * res["n_finite"], m, _dp(np.ascontiguousarray(sums)), ctypes.byref(k)))
-            if k.value:
-                last = (cand[k.value - 1], sums[k.value - 1])
-            if k.value == m:
-                if rnd == 0:
-                    return {"delta": b, "beta": 1.0, "lmax": res["lmax"], "sum_w": float(sums[-1, 0]), "ess": float(sums[-1, 0] ** 2 / sums[-1, 1])}
-                break
-            fail = (cand[k.value], sums[k.value])
-            a, b = (cand[k.value - 1] if k.value else a), cand[k.value]
-        delta, sw = last if last is not None else fail
-        return {"delta": delta, "beta": float(beta) + delta, "lmax": res["lmax"], "sum_w": float(sw[0]), "ess": float(sw[0] ** 2 / sw[1])}
+        search = _DeltaSearch(self.lib, beta, ess_fraction)
+        while not search.update(self.smc_weight_sums(x, search.candidates())):
+            pass
+        return search.out
 
     def smc_stage_uniform(self, seed, stage):
         """The resampling uniform of a stage: u53 of the first two Philox words of the counter (2^32 - 1, 2^32 - 1, stage, 4)."""
@@ -948,6 +1026,216 @@ class Engine:
             return q, l, accs, solves, after
 
         return self._smc(lo, hi, n, shape, seed, offset, ess_fraction, steps, max_stages, ltarget, move, history)
+
+    # -- P independent SMC populations per call (include/rsf_smc_batch.h) --------------------------------------
+    def _smc_batch_particles(self, q, l=None):
+        """q (P, n) or (P, n, d) and l (P, n) in this engine's memory space → (q (P, n, d), l, P, n, d)"""
+        q = self._in(q)
+        if q.ndim == 2:
+            q = q.reshape(int(q.shape[0]), int(q.shape[1]), 1)
+        if q.ndim != 3:
+            raise ValueError("the particles of P populations are (P, n, d)")
+        P, n, d = (int(v) for v in q.shape)
+        l = self._in(l)
+        if l is not None and tuple(l.shape) != (P, n):
+            raise ValueError(f"l has shape {tuple(l.shape)}, q {P} populations of {n} particles")
+        return q, l, P, n, d
+
+    def _smc_batch_data(self, data):
+        """data (nout,) or (G, nout) in this engine's memory space → ((G, nout), G)"""
+        obs = self._in(data)
+        if obs.ndim == 1:
+            obs = obs.reshape(1, -1)
+        if obs.ndim != 2 or int(obs.shape[0]) < 1 or int(obs.shape[1]) != self.nout:
+            raise ValueError(f"data has shape {tuple(obs.shape)}: (nout,) or (G, nout) with the model's nout = {self.nout}")
+        return obs, int(obs.shape[0])
+
+    @staticmethod
+    def _smc_active(active, P):
+        return np.ones(P, dtype=np.uint8) if active is None else _pop_array(np.asarray(active, dtype=bool), P, np.uint8, "active")
+
+    def smc_batch_init(self, lo, hi, n, seeds, offsets=0):
+        """rsf_smc_batch_init: smc_init for P = len(seeds) populations in one launch → q (P, n, d)."""
+        lo, hi, d = self._smc_box(lo, hi)
+        sd = np.ascontiguousarray(np.atleast_1d(np.asarray(seeds)).astype(np.uint64))
+        P = int(sd.size)
+        off = _pop_array(offsets, P, np.int64, "offsets")
+        q = self._empty((P, max(int(n), 0), d))
+        _abi.check(self.lib, self.lib.rsf_smc_batch_init(self._ctx, P, int(n), d, _dp(lo), _dp(hi), _ptr_of(sd, ctypes.c_uint64),
+                                                         _ptr_of(off, ctypes.c_int64), self._ptr(q)))
+        return q
+
+    def smc_batch_logtarget(self, q, data, group, lo, hi, shape=None):
+        """rsf_smc_batch_logtarget: l = -shape log SSq of every particle of q (P, n, d) against the row group[p] of data (G, nout),
+        one solve each in one launch → (P, n); -inf outside the strict box."""
+        self._need_model()
+        q, _, P, n, d = self._smc_batch_particles(q)
+        obs, G = self._smc_batch_data(data)
+        lo, hi, _ = self._smc_box(lo, hi, d)
+        grp = _pop_array(group, P, np.int32, "group")
+        l = self._empty((P, n))
+        _abi.check(self.lib, self.lib.rsf_smc_batch_logtarget(self._ctx, P, n, d, self._ptr(q), self._ptr(obs), G, _i32p(grp),
+                                                              float(0.5 * self.nout if shape is None else shape), _dp(lo), _dp(hi), self._ptr(l)))
+        return l
+
+    def smc_batch_weight_sums(self, l, deltas, lmax=None, active=None):
+        """rsf_smc_batch_weight_sums: smc_weight_sums of every active population of l (P, n) with its own steps deltas (P, m) (or
+        (m,) for all) and lmax (P,) (None or NaN: the population's largest finite l) in one read → a list of smc_weight_sums'
+        dicts, None for an inactive population."""
+        x = self._in(l)
+        if x.ndim != 2:
+            raise ValueError("l is (P, n)")
+        P, n = int(x.shape[0]), int(x.shape[1])
+        dl = np.asarray(deltas, dtype=np.float64)
+        dl = np.ascontiguousarray(np.broadcast_to(dl, (P, dl.shape[-1])) if dl.ndim == 1 else dl)
+        if dl.ndim != 2 or dl.shape[0] != P or not 1 <= dl.shape[1] <= _abi.SMC_MAX_CANDIDATES:
+            raise ValueError(f"deltas holds 1 to {_abi.SMC_MAX_CANDIDATES} steps for each of the {P} populations")
+        m = int(dl.shape[1])
+        lm = _pop_array(float("nan") if lmax is None else lmax, P, np.float64, "lmax")
+        act = self._smc_active(active, P)
+        out = np.zeros((P, _abi.SMC_HEAD + 2 * m))
+        _abi.check(self.lib, self.lib.rsf_smc_batch_weight_sums(self._ctx, P, n, self._ptr(x), m, _dp(dl), _dp(lm), _ptr_of(act, ctypes.c_uint8), _dp(out)))
+        return [{"lmax": float(o[0]), "n_finite": int(o[1]), "n_neginf": int(o[2]), "sums": o[_abi.SMC_HEAD:].reshape(-1, 2).copy()} if a else None
+                for o, a in zip(out, act)]
+
+    def smc_batch_next_delta(self, l, beta, ess_fraction=0.5, active=None):
+        """smc_next_delta for every active population of l (P, n) from its own temperature beta (P,): each round of the search is
+        one smc_batch_weight_sums over the populations still searching → a list of smc_next_delta's dicts, None for an inactive one."""
+        x = self._in(l)
+        P = int(x.shape[0])
+        bt, act = _pop_array(beta, P, np.float64, "beta"), self._smc_active(active, P)
+        search = [_DeltaSearch(self.lib, bt[p], ess_fraction) if act[p] else None for p in range(P)]
+        todo = act.astype(bool)
+        cand = np.zeros((P, _abi.SMC_MAX_CANDIDATES))
+        while todo.any():
+            for p in np.flatnonzero(todo):
+                cand[p] = search[p].candidates()
+            res = self.smc_batch_weight_sums(x, cand, None, todo)
+            for p in np.flatnonzero(todo):
+                todo[p] = not search[p].update(res[p])
+        return [sr.out if sr is not None else None for sr in search]
+
+    def smc_batch_resample(self, q, l, delta, lmax, u, active=None, out=None):
+        """rsf_smc_batch_resample: smc_resample of every active population of q (P, n, d), l (P, n) with its delta, lmax and u (P,)
+        → (cum (P, n), ancestors (P, n) int64, local to the population, q (P, n, d) and l (P, n) gathered).  An inactive
+        population's q and l are copied through and its rows of cum and ancestors are left as they are (zero in fresh buffers;
+        out = (cum, ancestors, q_out, l_out) supplies the buffers)."""
+        q, l, P, n, d = self._smc_batch_particles(q, l)
+        if l is None:
+            raise ValueError("l is (P, n)")
+        dl, lm, uu = (_pop_array(v, P, np.float64, w) for v, w in ((delta, "delta"), (lmax, "lmax"), (u, "u")))
+        act = self._smc_active(active, P)
+        if out is None:
+            cum, qo, lo_ = self._empty((P, n)), self._empty((P, n, d)), self._empty((P, n))
+            anc = self._torch.empty((P, n), dtype=self._torch.int64, device=f"cuda:{self.device}") if self.mem == "device" else np.empty((P, n), dtype=np.int64)
+            for x in (cum, anc):
+                x.fill_(0) if hasattr(x, "fill_") else x.fill(0)
+        else:
+            cum, anc, qo, lo_ = out
+        _abi.check(self.lib, self.lib.rsf_smc_batch_resample(self._ctx, P, n, d, self._ptr(q), self._ptr(l), _dp(dl), _dp(lm), _dp(uu),
+                                                             _ptr_of(act, ctypes.c_uint8), self._ptr(cum), self._ptr(anc), self._ptr(qo), self._ptr(lo_)))
+        return cum, anc, qo, lo_
+
+    def smc_batch_move(self, q, l, data, group, lo, hi, chol, beta, seeds, offsets=0, iter0=1, steps=3, shape=None, active=None, inplace=False):
+        """rsf_smc_batch_move, the fused hot path for P populations in ONE launch: population p takes `steps` Metropolis steps on
+        pi_beta[p] against the row group[p] of data (G, nout) with the proposal factor chol[p] (P, d, d), the stream (seeds[p],
+        offsets[p]) and the first iteration iter0[p] → (q (P, n, d), l (P, n), accepted (P, steps) int64).  The arrays handed in are
+        not changed unless inplace; an inactive population is not touched (its accepted counts read 0)."""
+        self._need_model()
+        q, l, P, n, d = self._smc_batch_particles(q, l)
+        if l is None:
+            raise ValueError("l is (P, n)")
+        obs, G = self._smc_batch_data(data)
+        lo, hi, _ = self._smc_box(lo, hi, d)
+        L = _host(chol).reshape(-1)
+        if L.size != P * d * d:
+            raise ValueError(f"chol is ({P}, {d}, {d})")
+        grp, bt = _pop_array(group, P, np.int32, "group"), _pop_array(beta, P, np.float64, "beta")
+        sd, off, it = _pop_array(seeds, P, np.uint64, "seeds"), _pop_array(offsets, P, np.int64, "offsets"), _pop_array(iter0, P, np.int64, "iter0")
+        act = self._smc_active(active, P)
+        if not inplace:
+            q, l = (q.clone(), l.clone()) if hasattr(q, "clone") else (q.copy(), l.copy())
+        acc = np.zeros((P, max(int(steps), 1)), dtype=np.int64)
+        _abi.check(self.lib, self.lib.rsf_smc_batch_move(self._ctx, P, n, d, self._ptr(q), self._ptr(l), self._ptr(obs), G, _i32p(grp),
+                                                         float(0.5 * self.nout if shape is None else shape), _dp(lo), _dp(hi), _dp(L), _dp(bt),
+                                                         _ptr_of(sd, ctypes.c_uint64), _ptr_of(off, ctypes.c_int64), _ptr_of(it, ctypes.c_int64),
+                                                         int(steps), _ptr_of(act, ctypes.c_uint8), _ptr_of(acc, ctypes.c_int64)))
+        return q, l, acc
+
+    def smc_batch_std2(self, l, shape, seeds, offsets=0, iteration=0):
+        """rsf_smc_batch_std2: smc_std2 of every population of l (P, n) with its own stream and iteration → (P, n)."""
+        x = self._in(l)
+        if x.ndim != 2:
+            raise ValueError("l is (P, n)")
+        P, n = int(x.shape[0]), int(x.shape[1])
+        sd, off, it = _pop_array(seeds, P, np.uint64, "seeds"), _pop_array(offsets, P, np.int64, "offsets"), _pop_array(iteration, P, np.int64, "iteration")
+        out = self._empty((P, n))
+        _abi.check(self.lib, self.lib.rsf_smc_batch_std2(self._ctx, P, n, self._ptr(x), float(shape), _ptr_of(sd, ctypes.c_uint64),
+                                                         _ptr_of(off, ctypes.c_int64), _ptr_of(it, ctypes.c_int64), self._ptr(out)))
+        return out
+
+    def smc_batch(self, data, lo, hi, n, groups=None, seeds=None, offsets=None, replicates=1, shape=None, ess_fraction=0.5, steps=3,
+                  max_stages=200, history=False):
+        """Engine.smc for many independent populations at once: every row of `groups` of data (nout,) or (G, nout) x `replicates`
+        (smc_batch_populations: by default replicate r has seed r and offset 0), each with its own temperature ladder, stage
+        count, resampling uniforms and proposal covariance, every stage ONE launch per kernel over the populations still below
+        beta = 1 (a population that reaches it goes inactive).  Each population's result equals, bit for bit, Engine.smc with
+        its seed, offset and data row.  → dict(runs: a list of Engine.smc's dicts — plus group, replicate, seed, offset —, the
+        replicates of a group next to each other; summary: smc_batch_summary of their log evidences, per group)."""
+        self._need_model()
+        obs, G = self._smc_batch_data(data)
+        pops = smc_batch_populations(G, groups, seeds, offsets, replicates)
+        grp, sd, off = pops["group"], pops["seed"], pops["offset"]
+        P = int(grp.size)
+        lo, hi, d = self._smc_box(lo, hi)
+        n, steps, shape = int(n), int(steps), 0.5 * self.nout if shape is None else float(shape)
+        if d not in (1, 3):
+            raise ValueError("the box has d = 1 (Dc) or 3 (Dc, a, b) parameters")
+        if not 0.0 < float(ess_fraction) < 1.0 or not 1 <= steps <= _abi.SMC_MAX_STEPS or int(max_stages) < 1:
+            raise ValueError(f"ess_fraction lies strictly inside (0, 1), steps in [1, {_abi.SMC_MAX_STEPS}], max_stages >= 1")
+        q = self.smc_batch_init(lo, hi, n, sd, off)
+        l = self.smc_batch_logtarget(q, obs, grp, lo, hi, shape)
+        logi, beta = np.full(P, float(np.log(hi - lo).sum())), np.zeros(P)
+        stages, hist = [[] for _ in range(P)], [[] for _ in range(P)]
+        delta, lmax, u, chol = np.zeros(P), np.zeros(P), np.ones(P), np.tile(np.eye(d), (P, 1, 1))
+        inc = ctypes.c_double()
+        active = beta < 1.0
+        while active.any():
+            live = np.flatnonzero(active)
+            for p in live:
+                if len(stages[p]) >= int(max_stages):
+                    raise _abi.RsfError(-1, f"Engine.smc_batch: population {p}: beta = {beta[p]!r} after max_stages = {max_stages} stages")
+            nd = self.smc_batch_next_delta(l, beta, ess_fraction, active)
+            for p in live:
+                _abi.check(self.lib, self.lib.rsf_smc_increment(n, nd[p]["sum_w"], nd[p]["delta"], nd[p]["lmax"], ctypes.byref(inc)))
+                logi[p], beta[p], delta[p], lmax[p] = logi[p] + inc.value, nd[p]["beta"], nd[p]["delta"], nd[p]["lmax"]
+                u[p] = self.smc_stage_uniform(int(sd[p]), len(stages[p]))
+            cum, anc, q, l = self.smc_batch_resample(q, l, delta, lmax, u, active)
+            for p in live:
+                cov = self.pool_joint(q[p])["cov"] if n > 1 else np.zeros((d, d))
+                if not np.isfinite(cov).all():
+                    raise _abi.RsfError(-1, f"Engine.smc_batch: population {p}: the resampled particles' covariance is not finite")
+                chol[p] = np.linalg.cholesky((2.38 ** 2 / d) * cov + np.diag((1e-6 * (hi - lo)) ** 2))
+            it0 = np.array([len(st) * steps + 1 for st in stages], dtype=np.int64)
+            q, l, acc = self.smc_batch_move(q, l, obs, grp, lo, hi, chol, np.where(active, beta, 1.0), sd, off, it0, steps, shape, active, inplace=True)
+            for p in live:
+                stages[p].append({"beta": float(beta[p]), "delta": float(delta[p]), "ess": nd[p]["ess"],
+                                  "accept_rate": float(np.sum(acc[p])) / (n * steps), "log_integral": float(logi[p])})
+                if history:
+                    hist[p].append({"lmax": float(lmax[p]), "u": float(u[p]), "cum": _host(cum[p]),
+                                    "ancestors": np.asarray(anc[p].cpu() if hasattr(anc, "cpu") else anc[p]).copy(), "chol": chol[p].copy(),
+                                    "after": [(_host(q[p]).copy(), _host(l[p]).copy())]})
+            active = beta < 1.0
+        std2 = self.smc_batch_std2(l, shape, sd, off, [len(st) * steps + 1 for st in stages])
+        ev, runs = ctypes.c_double(), []
+        for p in range(P):
+            _abi.check(self.lib, self.lib.rsf_smc_log_evidence(float(logi[p]), shape, d, _dp(lo), _dp(hi), ctypes.byref(ev)))
+            runs.append({"q": q[p], "l": l[p], "std2": std2[p], "log_integral": float(logi[p]), "log_evidence": ev.value, "stages": stages[p],
+                         "n_solves": n * (1 + steps * len(stages[p])), "shape": shape, "d": d, "n": n, "group": int(grp[p]),
+                         "replicate": int(pops["replicate"][p]), "seed": int(sd[p]), "offset": int(off[p])})
+            if history:
+                runs[-1]["history"] = hist[p]
+        return {"runs": runs, "summary": smc_batch_summary([r["log_evidence"] for r in runs], grp)}
 
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
