@@ -549,6 +549,33 @@ class MCMC:
             eng.sync()
             return self._smc_pool(res)
 
+    def _fit_starts(self, eng, n_starts, seed):
+        """start 0 is qstart, the others rsf_smc_init's uniform start in the prior box (seed, particles 0 .. n_starts - 2)"""
+        lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
+        q0 = np.asarray(self.qstart, dtype=np.float64).reshape(1, self.n_params)
+        if int(n_starts) < 1:
+            raise ValueError("n_starts must be >= 1")
+        if int(n_starts) > 1:
+            q0 = np.concatenate([q0, _host(eng.smc_init(lo, hi, int(n_starts) - 1, seed))])
+        return q0, lo, hi
+
+    def fit(self, n_starts=64, seed=0, mem="host", device=-1, **kw):
+        """Least squares before any sampling (additive; Engine.fit): a Levenberg-Marquardt fit from n_starts start points at once —
+        start 0 is qstart, the others are uniform in the prior box — each iteration one group solve on the GPU.  Returns a
+        FitResult: best() is the start with the smallest sum of squares, covariance() its least-squares covariance, laplace() a
+        quick evidence to set beside PosteriorPool.evidence and sample_smc's.  sample_batched(q0=...) takes best()'s point as the
+        chains' start.  With three parameters the estimate is ONE POINT on the ridge Dc a = const: only its sum of squares and
+        Dc a are reproducible.  kw: Engine.fit's fd_rel_step, ftol, max_iter, iters_per_launch."""
+        if not self._device_model():
+            raise TypeError("fit integrates the model on the device: `model` must be this package's RateStateModel")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            q0, lo, hi = self._fit_starts(eng, n_starts, seed)
+            res = eng.fit(q0, data, lo, hi, **kw)
+            eng.sync()
+            return res
+
     # ---- visualisation (off the hot path; degrades gracefully) --------------------------
     def _animate(self, qparams):
         _figures.chain_movie(qparams[0], f"MCMC Sampling Evolution for dc = {self.dc_true:.2f} as True value",

@@ -153,6 +153,27 @@ class RSF:
         self.posteriors = {dc: pool.pooled() for dc, pool in out.items()}
         return out
 
+    def inference_fit(self, n_starts=64, seed=0, mem="host", device=-1, **kw):
+        """Additive: the least-squares estimate of every true Dc of dc_list in ONE call (Engine.fit) — each is an observation group
+        with n_starts start points (MCMC.fit's: qstart, then uniform in the prior box).  Returns {dc: dict(q, ssq, cov, stderr,
+        status, iters, index)} of each group's best start; the FitResult of all starts is kept in self.fit_result.  The
+        `inference` path is not touched."""
+        n, G = self.model.num_tsteps, len(self.dc_list)
+        data = np.ascontiguousarray(np.asarray(self.data, dtype=np.float64).reshape(G, n))
+        probe = MCMC(self.model, data[0], self.dc_list[0], self.qpriors, self.qstart, nsamples=10)
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            q0, lo, hi = probe._fit_starts(eng, n_starts, seed)
+            res = eng.fit(np.tile(q0, (G, 1)), data, lo, hi, **kw)
+            eng.sync()
+        self.fit_result, out = res, {}
+        for g, dc in enumerate(self.dc_list):
+            i = res.best(g)
+            cov = res.covariance(i)
+            out[float(dc)] = {"q": res.q[i].copy(), "ssq": float(res.ssq[i]), "cov": cov, "stderr": np.sqrt(np.diag(cov)),
+                              "status": int(res.status[i]), "iters": int(res.iters[i]), "index": i}
+        return out
+
     @measure_execution_time
     def inference(self, nsamples):
         data = self.prepare_data(self.data)

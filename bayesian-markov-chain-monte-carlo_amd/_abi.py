@@ -251,6 +251,21 @@ SMC_BATCH_PROTOTYPES = {
 SMC_BATCH_MAX = 64  # RSF_SMC_BATCH_MAX: populations per call
 
 
+# include/rsf_fit.h: multi-start Levenberg-Marquardt least squares; exported by librsf_hip.so only, bound by load()
+FIT_PROTOTYPES = {
+    "rsf_fit_normal": (c_int, [c_void_p, c_int64, c_int32, _P, _P, c_int32, c_double, _P, _P, _P]),
+    "rsf_fit_run": (c_int, [c_void_p, c_int64, c_int32, _P, _P, c_int32, _DP, _DP, c_double, c_double, c_int32, _P, _P, _P, _P, _P, _P]),
+    "rsf_fit_trial": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, _P, _DP, _DP, _P, _P, _P]),
+    "rsf_fit_decide": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_double]),
+    "rsf_fit_laplace": (c_int, [c_int32, c_int64, c_double, c_double, _DP, _DP, _DP, _DP]),
+}
+FIT_MAX_PARAMS = 3  # RSF_FIT_MAX_PARAMS
+FIT_MAX_ITER = 64   # RSF_FIT_MAX_ITER: iterations per rsf_fit_run call
+FIT_RUNNING, FIT_CONVERGED, FIT_STALLED, FIT_FAILED = 0, 1, 2, 3  # RSF_FIT_*: a start's status
+FIT_LAM0 = 1e-3     # RSF_FIT_LAM0: the damping a start begins with
+MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
+
+
 def bind(lib):
     """Attach the rsf_abi.h prototypes to an opened CDLL; raises if a symbol is missing."""
     for name, (restype, argtypes) in PROTOTYPES.items():
@@ -295,7 +310,7 @@ def load():
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
-                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES):
+                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

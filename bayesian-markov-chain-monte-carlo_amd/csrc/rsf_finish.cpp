@@ -1,6 +1,6 @@
 // rsf_finish.cpp — the host arithmetic that turns the device partials into the reported statistics: rsf_diag_finish,
 // rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish, rsf_pool_joint_finish, rsf_pool_hpd_levels, rsf_evidence_finish,
-// rsf_smc_section, rsf_smc_increment, rsf_smc_log_evidence.  No ctx, no GPU:
+// rsf_smc_section, rsf_smc_increment, rsf_smc_log_evidence, rsf_fit_laplace.  No ctx, no GPU:
 // plain C++, the public headers and the standard library only.
 #include <cmath>
 #include <cstdint>
@@ -10,6 +10,7 @@
 #include "../../include/rsf_abi.h"
 #include "../../include/rsf_diag.h"
 #include "../../include/rsf_evidence.h"
+#include "../../include/rsf_fit.h"
 #include "../../include/rsf_joint.h"
 #include "../../include/rsf_predict.h"
 #include "../../include/rsf_psis.h"
@@ -290,6 +291,41 @@ int rsf_smc_log_evidence(double log_integral, double shape, int32_t d, const dou
   }
   *out = log_integral - logvol + std::lgamma(shape) - shape * std::log(3.14159265358979323846);
   return RSF_OK;
+}
+
+int rsf_fit_laplace(int32_t d, int64_t n_obs, double shape, double ssq, const double *jtj, const double *lo, const double *hi, double *out) {
+  if (!jtj || !lo || !hi || !out) return fail(RSF_ERR_INVALID, "rsf_fit_laplace: NULL argument");
+  if (d < 1 || d > RSF_FIT_MAX_PARAMS || n_obs <= d) return fail(RSF_ERR_INVALID, "rsf_fit_laplace: need 1 <= d <= %d and n_obs > d", RSF_FIT_MAX_PARAMS);
+  if (!std::isfinite(shape) || !(shape > 0.0) || !std::isfinite(ssq) || !(ssq > 0.0))
+    return fail(RSF_ERR_INVALID, "rsf_fit_laplace: shape and ssq must be finite and > 0");
+  // jtj = L L^T (lower triangle read); log det from the pivots, the inverse from L^-1
+  double L[RSF_FIT_MAX_PARAMS * RSF_FIT_MAX_PARAMS] = {}, Li[RSF_FIT_MAX_PARAMS * RSF_FIT_MAX_PARAMS] = {}, logdet = 0.0;
+  for (int p = 0; p < d; ++p)
+    for (int r = 0; r <= p; ++r) {
+      double s = jtj[p * d + r];
+      for (int k = 0; k < r; ++k) s -= L[p * d + k] * L[r * d + k];
+      if (r < p) { L[p * d + r] = s / L[r * d + r]; continue; }
+      if (!(s > 0.0) || !std::isfinite(s)) return fail(RSF_ERR_NOT_POSDEF, "rsf_fit_laplace: jtj is not positive definite (pivot %d)", p);
+      L[p * d + p] = std::sqrt(s);
+      logdet += std::log(s);
+    }
+  for (int c = 0; c < d; ++c)  // column c of L^-1 by forward substitution
+    for (int p = c; p < d; ++p) {
+      double s = p == c ? 1.0 : 0.0;
+      for (int k = c; k < p; ++k) s -= L[p * d + k] * Li[k * d + c];
+      Li[p * d + c] = s / L[p * d + p];
+    }
+  const double s2 = ssq / (double)(n_obs - d);
+  for (int p = 0; p < d; ++p)
+    for (int r = 0; r < d; ++r) {
+      double s = 0.0;
+      for (int k = std::max(p, r); k < d; ++k) s += Li[k * d + p] * Li[k * d + r];  // (L^-T L^-1)_pr
+      out[p * d + r] = s2 * s;
+    }
+  const double two_pi = 6.28318530717958647692;
+  const double logi = -shape * std::log(ssq) + 0.5 * d * std::log(two_pi) - 0.5 * (logdet + d * std::log(2.0 * shape / ssq));
+  out[d * d] = logi;
+  return rsf_smc_log_evidence(logi, shape, d, lo, hi, out + d * d + 1);
 }
 
 }  // extern "C"

@@ -1,0 +1,169 @@
+// rsf_fit.hip — multi-start Levenberg-Marquardt least squares (include/rsf_fit.h): rsf_fit_normal / _run / _trial / _decide
+// (kernels: rsf_kernels_fit.h).  rsf_fit_laplace, the host arithmetic, is in rsf_finish.cpp.
+#include <cmath>
+
+#include "rsf_host.h"
+#include "rsf_kernels_fit.h"
+
+using namespace rsfk;
+using namespace rsfh;
+
+namespace {
+
+unsigned blocks_of(int64_t n) { return (unsigned)((n + kMaxBlock - 1) / kMaxBlock); }
+
+// The arrays of one call for an RSF_MEM_HOST caller.  These calls take more arrays than the ctx has named staging slots
+// (rsf_host.h, Slot), so they stage all of them in ONE workspace, the ctx's pool buffer: add() every array, commit() sizes the
+// workspace and copies the inputs in, dev() is the pointer the kernels take, back() copies the outputs out.  A device caller's
+// pointers pass through.
+struct Staged {
+  struct Item { void *host; size_t bytes, off; bool in, out; };
+  rsf_ctx *c;
+  Item items[12];
+  int count = 0;
+  size_t total = 0;
+  explicit Staged(rsf_ctx *ctx) : c(ctx) {}
+  int add(const void *p, size_t bytes, bool in, bool out) {
+    items[count] = {const_cast<void *>(p), bytes, total, in, out};
+    total += (bytes + 255) & ~(size_t)255;
+    return count++;
+  }
+  int commit() {
+    if (!host_mem(c)) return RSF_OK;
+    if (int rc = ensure(c->pool, total)) return rc;
+    for (int k = 0; k < count; ++k)
+      if (items[k].in) HIP_TRY(hipMemcpyAsync((char *)c->pool.p + items[k].off, items[k].host, items[k].bytes, hipMemcpyHostToDevice, c->stream));
+    return RSF_OK;
+  }
+  template <class T> T *dev(int k) const { return host_mem(c) ? (T *)((char *)c->pool.p + items[k].off) : (T *)items[k].host; }
+  int back() {
+    if (!host_mem(c)) return RSF_OK;
+    for (int k = 0; k < count; ++k)
+      if (items[k].out) HIP_TRY(hipMemcpyAsync(items[k].host, (char *)c->pool.p + items[k].off, items[k].bytes, hipMemcpyDeviceToHost, c->stream));
+    return RSF_OK;
+  }
+};
+
+int set_box(const char *fn, int d, const double *lo, const double *hi, FitArgs &A) {
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "%s: need finite lo[%d] < hi[%d]", fn, p, p);
+    A.lo[p] = lo[p]; A.hi[p] = hi[p];
+  }
+  return RSF_OK;
+}
+
+// what the calls with a solve share: the shape, the model's integrator, the split of the starts over the observation series
+int set_solve(const char *fn, const rsf_ctx *c, int64_t n, int32_t d, int32_t n_groups, double fd, FitArgs &A) {
+  if (n < 1 || (d != 1 && d != 3)) return fail(RSF_ERR_INVALID, "%s: need n >= 1 and d = 1 or 3", fn);
+  if (!std::isfinite(fd) || !(fd > 0.0)) return fail(RSF_ERR_INVALID, "%s: fd must be finite and > 0", fn);
+  if (c->m.flags & RSF_FLAG_DOP853)
+    return fail(RSF_ERR_UNSUPPORTED, "%s: a model flagged RSF_FLAG_DOP853 is not supported (the solve is the float64 RK4)", fn);
+  // a workgroup's starts share one observation series: rsf_mcmc_init's rule for chain groups
+  if (n_groups < 1 || n % n_groups || (n_groups > 1 && (n / n_groups) % c->block))
+    return fail(RSF_ERR_INVALID, "%s: need n_groups >= 1 and, with more than one, n/n_groups a whole multiple of a workgroup's threads (%d)", fn, c->block);
+  A.n = n; A.fd = fd;
+  A.group_starts = n_groups > 1 ? n / n_groups : 0;
+  return RSF_OK;
+}
+
+auto normal_fn(const rsf_ctx *c, int d) {
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return fit_normal_kernel<D, DAMP>; }); });
+}
+auto run_fn(const rsf_ctx *c, int d) {
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return fit_kernel<D, DAMP>; }); });
+}
+auto trial_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return fit_trial_kernel<D>; }); }
+auto decide_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return fit_decide_kernel<D>; }); }
+
+}  // namespace
+
+extern "C" {
+
+int rsf_fit_normal(rsf_ctx *c, int64_t n, int32_t d, const double *q, const double *data, int32_t n_groups, double fd, double *ssq,
+                   double *grad, double *jtj) {
+  RSF_ENTER(c, NEED_MODEL, q && data && ssq && grad && jtj, "NULL argument");
+  int rc;
+  FitArgs A{};
+  if ((rc = set_solve(__func__, c, n, d, n_groups, fd, A))) return rc;
+  const size_t nb = (size_t)n * sizeof(double);
+  Staged s(c);
+  const int iq = s.add(q, nb * d, true, false), idata = s.add(data, (size_t)n_groups * c->nout * sizeof(double), true, false);
+  const int issq = s.add(ssq, nb, false, true), ig = s.add(grad, nb * d, false, true), ih = s.add(jtj, nb * d * d, false, true);
+  if ((rc = s.commit())) return rc;
+  A.q = s.dev<double>(iq); A.ssq = s.dev<double>(issq); A.grad = s.dev<double>(ig); A.jtj = s.dev<double>(ih);
+  // one lane per TRAJECTORY: 1 + d adjacent lanes per start, the shared chunking of the float64 tables (c->kc, c->lds_bytes)
+  if ((rc = launch(c, normal_fn(c, d), grid_for(c, n * (d + 1)), c->block, c->lds_bytes, make_consts(c, s.dev<const double>(idata)), A))) return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+int rsf_fit_run(rsf_ctx *c, int64_t n, int32_t d, double *q, const double *data, int32_t n_groups, const double *lo, const double *hi,
+                double fd, double ftol, int32_t n_iter, double *ssq, double *grad, double *jtj, double *lam, int32_t *status,
+                int32_t *iters) {
+  RSF_ENTER(c, NEED_MODEL, q && data && lo && hi && ssq && grad && jtj && lam && status && iters, "NULL argument");
+  int rc;
+  FitArgs A{};
+  if ((rc = set_solve(__func__, c, n, d, n_groups, fd, A))) return rc;
+  if (n_iter < 1 || n_iter > RSF_FIT_MAX_ITER) return fail(RSF_ERR_INVALID, "rsf_fit_run: need 1 <= n_iter <= %d", RSF_FIT_MAX_ITER);
+  if (!std::isfinite(ftol) || ftol < 0.0) return fail(RSF_ERR_INVALID, "rsf_fit_run: ftol must be finite and >= 0");
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  A.ftol = ftol; A.n_iter = n_iter;
+  const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int32_t);
+  Staged s(c);
+  const int iq = s.add(q, nb * d, true, true), idata = s.add(data, (size_t)n_groups * c->nout * sizeof(double), true, false);
+  const int issq = s.add(ssq, nb, true, true), ig = s.add(grad, nb * d, true, true), ih = s.add(jtj, nb * d * d, true, true);
+  const int il = s.add(lam, nb, true, true), ist = s.add(status, ni, true, true), iit = s.add(iters, ni, true, true);
+  if ((rc = s.commit())) return rc;
+  A.q = s.dev<double>(iq); A.ssq = s.dev<double>(issq); A.grad = s.dev<double>(ig); A.jtj = s.dev<double>(ih); A.lam = s.dev<double>(il);
+  A.status = s.dev<int32_t>(ist); A.iters = s.dev<int32_t>(iit);
+  if ((rc = launch(c, run_fn(c, d), grid_for(c, n * (d + 1)), c->block, c->lds_bytes, make_consts(c, s.dev<const double>(idata)), A))) return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+int rsf_fit_trial(rsf_ctx *c, int64_t n, int32_t d, const double *q, const double *grad, const double *jtj, const double *lam,
+                  const double *lo, const double *hi, const int32_t *status, double *q_trial, uint8_t *ok) {
+  RSF_ENTER(c, NEED_NOTHING, q && grad && jtj && lam && lo && hi && status && q_trial && ok, "NULL argument");
+  if (n < 1 || d < 1 || d > RSF_FIT_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_fit_trial: need n >= 1 and 1 <= d <= %d", RSF_FIT_MAX_PARAMS);
+  int rc;
+  FitArgs A{};
+  if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
+  A.n = n;
+  const size_t nb = (size_t)n * sizeof(double);
+  Staged s(c);
+  const int iq = s.add(q, nb * d, true, false), ig = s.add(grad, nb * d, true, false), ih = s.add(jtj, nb * d * d, true, false);
+  const int il = s.add(lam, nb, true, false), ist = s.add(status, (size_t)n * sizeof(int32_t), true, false);
+  const int iqt = s.add(q_trial, nb * d, false, true), iok = s.add(ok, (size_t)n, false, true);
+  if ((rc = s.commit())) return rc;
+  A.q = s.dev<double>(iq); A.grad = s.dev<double>(ig); A.jtj = s.dev<double>(ih); A.lam = s.dev<double>(il); A.status = s.dev<int32_t>(ist);
+  if ((rc = launch(c, trial_fn(d), blocks_of(n), kMaxBlock, 0, A, s.dev<double>(iqt), s.dev<uint8_t>(iok)))) return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+int rsf_fit_decide(rsf_ctx *c, int64_t n, int32_t d, double *q, double *ssq, double *grad, double *jtj, double *lam, int32_t *status,
+                   int32_t *iters, const double *q_trial, const uint8_t *ok, const double *ssq_new, const double *grad_new,
+                   const double *jtj_new, double ftol) {
+  RSF_ENTER(c, NEED_NOTHING, q && ssq && grad && jtj && lam && status && iters && q_trial && ok && ssq_new && grad_new && jtj_new, "NULL argument");
+  if (n < 1 || d < 1 || d > RSF_FIT_MAX_PARAMS) return fail(RSF_ERR_INVALID, "rsf_fit_decide: need n >= 1 and 1 <= d <= %d", RSF_FIT_MAX_PARAMS);
+  if (!std::isfinite(ftol) || ftol < 0.0) return fail(RSF_ERR_INVALID, "rsf_fit_decide: ftol must be finite and >= 0");
+  int rc;
+  FitArgs A{};
+  A.n = n; A.ftol = ftol;
+  const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int32_t);
+  Staged s(c);
+  const int iq = s.add(q, nb * d, true, true), issq = s.add(ssq, nb, true, true), ig = s.add(grad, nb * d, true, true);
+  const int ih = s.add(jtj, nb * d * d, true, true), il = s.add(lam, nb, true, true), ist = s.add(status, ni, true, true);
+  const int iit = s.add(iters, ni, true, true), iqt = s.add(q_trial, nb * d, true, false), iok = s.add(ok, (size_t)n, true, false);
+  const int isn = s.add(ssq_new, nb, true, false), ign = s.add(grad_new, nb * d, true, false), ihn = s.add(jtj_new, nb * d * d, true, false);
+  if ((rc = s.commit())) return rc;
+  A.q = s.dev<double>(iq); A.ssq = s.dev<double>(issq); A.grad = s.dev<double>(ig); A.jtj = s.dev<double>(ih); A.lam = s.dev<double>(il);
+  A.status = s.dev<int32_t>(ist); A.iters = s.dev<int32_t>(iit);
+  if ((rc = launch(c, decide_fn(d), blocks_of(n), kMaxBlock, 0, A, s.dev<const double>(iqt), s.dev<const uint8_t>(iok), s.dev<const double>(isn),
+                   s.dev<const double>(ign), s.dev<const double>(ihn))))
+    return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+}  // extern "C"

@@ -232,6 +232,56 @@ def bayes_factor(ev_a, ev_b):
     return {"log_bf": float(ev_a["log_evidence"] - ev_b["log_evidence"]), "re": float(np.hypot(ev_a["re"], ev_b["re"]))}
 
 
+class FitResult:
+    """Result of Engine.fit / Engine.fit_from_residuals: per start the point q (n, d), its sum of squares ssq (n,), grad = X^T r
+    (n, d), jtj = X^T X (n, d, d), the damping lam (n,), status (n,) int32 (_abi.FIT_RUNNING / _CONVERGED / _STALLED / _FAILED) and
+    iters (n,) int32, NumPy arrays on the host; n_groups observation series (the starts split evenly over them in order) of n_obs
+    samples each.  At d = 3 the problem has a ridge (Dc a = const): a start's q is ONE POINT ON IT — compare ssq and Dc a, not the
+    three parameters."""
+
+    def __init__(self, lib, q, ssq, grad, jtj, lam, status, iters, n_groups, n_obs):
+        self._lib = lib
+        self.q, self.ssq, self.grad, self.jtj, self.lam, self.status, self.iters = q, ssq, grad, jtj, lam, status, iters
+        self.n_groups, self.n_obs = int(n_groups), int(n_obs)
+
+    def best(self, group=None):
+        """The index of the start with the smallest finite ssq among those that are not FAILED — of observation group `group`, or
+        of all starts."""
+        n = self.ssq.shape[0]
+        per = n // self.n_groups
+        if group is not None and not 0 <= int(group) < self.n_groups:
+            raise ValueError(f"group {group} is outside 0..{self.n_groups - 1}")
+        idx = np.arange(n) if group is None else np.arange(int(group) * per, (int(group) + 1) * per)
+        idx = idx[(self.status[idx] != _abi.FIT_FAILED) & np.isfinite(self.ssq[idx])]
+        if idx.size == 0:
+            raise _abi.RsfError(-1, "FitResult.best: no start has a finite sum of squares")
+        return int(idx[np.argmin(self.ssq[idx])])
+
+    def _laplace(self, shape, lo, hi, i):
+        i = self.best() if i is None else int(i)
+        d = int(self.q.shape[1])
+        out = np.empty(d * d + 2)
+        jtj = np.ascontiguousarray(self.jtj[i], dtype=np.float64)
+        _abi.check(self._lib, self._lib.rsf_fit_laplace(d, self.n_obs, float(shape), float(self.ssq[i]), _dp(jtj), _dp(_vec(lo, d, "lo")),
+                                                        _dp(_vec(hi, d, "hi")), _dp(out)))
+        return i, out[:d * d].reshape(d, d).copy(), float(out[d * d]), float(out[d * d + 1])
+
+    def covariance(self, i=None):
+        """rsf_fit_laplace's cov = ssq / (n_obs - d) (X^T X)^-1 of start i (by default best()) → (d, d); the standard errors are
+        the square roots of its diagonal."""
+        return self._laplace(1.0, 0.0, 1.0, i)[1]
+
+    def laplace(self, shape=None, lo=0.0, hi=1.0e4, i=None):
+        """rsf_fit_laplace at start i (by default best()) → dict(index, q, ssq, cov, stderr, log_integral, log_evidence, shape):
+        Laplace's approximation of the integral of SSq^-shape (shape defaults to n_obs / 2) and log p(y | M) with the constants of
+        Engine.evidence_finish and Engine.smc over the box (lo, hi).  The value IGNORES THE BOX'S EDGES: it is meaningful at d = 1
+        with an interior mode, not on the ridge of d = 3."""
+        shape = 0.5 * self.n_obs if shape is None else float(shape)
+        i, cov, logi, ev = self._laplace(shape, lo, hi, i)
+        return {"index": i, "q": self.q[i].copy(), "ssq": float(self.ssq[i]), "cov": cov, "stderr": np.sqrt(np.diag(cov)), "log_integral": logi,
+                "log_evidence": ev, "shape": shape}
+
+
 class Engine:
     def __init__(self, lib=None, mem="host", device=-1, block_threads=0, cpu_threads=0, stream=None, checker=False):
         if lib is None:
@@ -253,6 +303,7 @@ class Engine:
         cfg.device = device
         cfg.mem_space = _abi.MEM_DEVICE if mem == "device" else _abi.MEM_HOST
         cfg.block_threads, cfg.cpu_threads = block_threads, cpu_threads
+        self.block_threads = int(block_threads) or _abi.MAX_BLOCK
         if mem == "device":
             import torch
 
@@ -1236,6 +1287,181 @@ class Engine:
             if history:
                 runs[-1]["history"] = hist[p]
         return {"runs": runs, "summary": smc_batch_summary([r["log_evidence"] for r in runs], grp)}
+
+    # -- multi-start Levenberg-Marquardt least squares (include/rsf_fit.h) ----------------------------------------
+    def _ints(self, x):
+        """an int32 array in this engine's memory space"""
+        if self.mem == "device":
+            t = self._torch
+            return t.as_tensor(np.ascontiguousarray(x, dtype=np.int32)).to(device=f"cuda:{self.device}")
+        return np.array(x, dtype=np.int32)
+
+    @staticmethod
+    def _fit_args(q0, lo, hi, dims, fd_rel_step, ftol, max_iter, iters_per_launch):
+        """The checks Engine.fit and fit_from_residuals share → (q0 (n, d) a fresh host array, lo, hi, d, fd, ftol, max_iter, iters_per_launch)"""
+        q0 = _host(q0).copy()
+        if q0.ndim == 1:
+            q0 = q0.reshape(-1, 1)
+        if q0.ndim != 2 or q0.shape[0] < 1 or q0.shape[1] not in dims:
+            raise ValueError(f"q0 has shape {q0.shape}: (n,) or (n, d) start points, d one of {dims}")
+        d = int(q0.shape[1])
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo < hi).all()):
+            raise ValueError("the box needs finite lo < hi in every parameter")
+        fd = (1e-6 if d == 1 else 1e-4) if fd_rel_step is None else float(fd_rel_step)
+        ftol, max_iter, ipl = float(ftol), int(max_iter), int(iters_per_launch)
+        if not (math.isfinite(fd) and fd > 0.0 and math.isfinite(ftol) and ftol >= 0.0 and max_iter >= 1 and 1 <= ipl <= _abi.FIT_MAX_ITER):
+            raise ValueError(f"fd_rel_step is finite and > 0, ftol finite and >= 0, max_iter >= 1, iters_per_launch in [1, {_abi.FIT_MAX_ITER}]")
+        return q0, lo, hi, d, fd, ftol, max_iter, ipl
+
+    def fit_normal(self, q, data, fd_rel_step=None):
+        """rsf_fit_normal: the normal equations of the device model at the points q (n,) or (n, d), d = 1 (Dc) or 3 (Dc, a, b),
+        against data (nout,) or (G, nout) (the points split evenly over the G series in order; G > 1: n / G a whole multiple of a
+        workgroup's threads) → (ssq (n,), grad (n, d), jtj (n, d, d)) in this engine's memory space."""
+        self._need_model()
+        q = self._in(q)
+        if q.ndim == 1:
+            q = q.reshape(-1, 1)
+        n, d = int(q.shape[0]), int(q.shape[1])
+        obs = self._in(data)
+        if obs.ndim not in (1, 2) or int(obs.shape[-1]) != self.nout:
+            raise ValueError(f"data has shape {tuple(obs.shape)}: (nout,) or (G, nout), the model produces nout = {self.nout} samples")
+        G = int(obs.shape[0]) if obs.ndim == 2 else 1
+        fd = (1e-6 if d == 1 else 1e-4) if fd_rel_step is None else float(fd_rel_step)
+        ssq, grad, jtj = self._empty((n,)), self._empty((n, d)), self._empty((n, d, d))
+        _abi.check(self.lib, self.lib.rsf_fit_normal(self._ctx, n, d, self._ptr(q), self._ptr(obs), G, fd, self._ptr(ssq), self._ptr(grad), self._ptr(jtj)))
+        return ssq, grad, jtj
+
+    def _fit_state(self, q, grad, jtj, lam, status, ssq=None, iters=None):
+        """The check of a fit state handed to the low-level calls, which read and write it through raw addresses: q (n, d), grad
+        (n, d), jtj (n, d, d), lam (n,) and ssq (n,) float64, status (n,) and iters (n,) int32, each a C-contiguous array of this
+        engine's memory space (a NumPy array, or a torch tensor on its device) → (n, d)"""
+        if getattr(q, "ndim", 0) != 2:
+            raise ValueError("q is (n, d)")
+        n, d = int(q.shape[0]), int(q.shape[1])
+        t = self._torch
+        for what, x, shape, dt in (("q", q, (n, d), "float64"), ("grad", grad, (n, d), "float64"), ("jtj", jtj, (n, d, d), "float64"),
+                                   ("lam", lam, (n,), "float64"), ("ssq", ssq, (n,), "float64"), ("status", status, (n,), "int32"),
+                                   ("iters", iters, (n,), "int32")):
+            if x is None and what in ("ssq", "iters"):
+                continue
+            if self.mem == "device":
+                good = isinstance(x, t.Tensor) and x.is_cuda and x.is_contiguous() and str(x.dtype) == "torch." + dt
+            else:
+                good = isinstance(x, np.ndarray) and x.flags["C_CONTIGUOUS"] and x.dtype == np.dtype(dt)
+            if not good or tuple(x.shape) != shape:
+                raise ValueError(f"{what} must be a C-contiguous {dt} array of shape {shape} in this engine's memory space ({self.mem})")
+        return n, d
+
+    def fit_run(self, q, data, lo, hi, ssq, grad, jtj, lam, status, iters, n_iter, fd_rel_step=None, ftol=1e-9):
+        """rsf_fit_run, the fused hot path: n_iter iterations of every RUNNING start IN PLACE in q (n, d), ssq, grad, jtj, lam,
+        status and iters (int32), contiguous arrays of this engine's memory space as fit_normal leaves them."""
+        self._need_model()
+        n, d = self._fit_state(q, grad, jtj, lam, status, ssq, iters)
+        data = self._in(data)
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        fd = (1e-6 if d == 1 else 1e-4) if fd_rel_step is None else float(fd_rel_step)
+        _abi.check(self.lib, self.lib.rsf_fit_run(self._ctx, n, d, self._ptr(q), self._ptr(data), G, _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")), fd,
+                                                  float(ftol), int(n_iter), self._ptr(ssq), self._ptr(grad), self._ptr(jtj), self._ptr(lam),
+                                                  self._ptr(status), self._ptr(iters)))
+
+    def fit_trial(self, q, grad, jtj, lam, status, lo, hi):
+        """rsf_fit_trial: the trial points of the RUNNING starts → (q_trial (n, d), ok (n,) uint8)."""
+        n, d = self._fit_state(q, grad, jtj, lam, status)
+        qt, ok = self._empty((n, d)), self._empty((n,), np.uint8)
+        _abi.check(self.lib, self.lib.rsf_fit_trial(self._ctx, n, d, self._ptr(q), self._ptr(grad), self._ptr(jtj), self._ptr(lam), _dp(_vec(lo, d, "lo")),
+                                                    _dp(_vec(hi, d, "hi")), self._ptr(status), self._ptr(qt), self._ptr(ok)))
+        return qt, ok
+
+    def fit_decide(self, q, ssq, grad, jtj, lam, status, iters, q_trial, ok, ssq_new, grad_new, jtj_new, ftol=1e-9):
+        """rsf_fit_decide: accept or reject the trial points with the caller's normal equations there, IN PLACE in q, ssq, grad,
+        jtj, lam, status and iters (contiguous arrays of this engine's memory space); q_trial (n, d), ok (n,), ssq_new (n,), grad_new
+        (n, d) and jtj_new (n, d, d) are read and may have any layout."""
+        n, d = self._fit_state(q, grad, jtj, lam, status, ssq, iters)
+        q_trial, ok, ssq_new, grad_new, jtj_new = self._in(q_trial), self._bytes(ok), self._in(ssq_new), self._in(grad_new), self._in(jtj_new)
+        if (tuple(q_trial.shape), tuple(ok.shape), tuple(ssq_new.shape), tuple(grad_new.shape), tuple(jtj_new.shape)) != ((n, d), (n,), (n,), (n, d), (n, d, d)):
+            raise ValueError(f"q_trial and grad_new are ({n}, {d}), ok and ssq_new ({n},), jtj_new ({n}, {d}, {d})")
+        _abi.check(self.lib, self.lib.rsf_fit_decide(self._ctx, n, d, self._ptr(q), self._ptr(ssq), self._ptr(grad), self._ptr(jtj), self._ptr(lam),
+                                                     self._ptr(status), self._ptr(iters), self._ptr(q_trial), self._ptr(ok), self._ptr(ssq_new),
+                                                     self._ptr(grad_new), self._ptr(jtj_new), float(ftol)))
+
+    @staticmethod
+    def _ints_host(x):
+        return np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+
+    def _fit_result(self, keep, q, ssq, grad, jtj, lam, status, iters, n_groups, n_obs):
+        return FitResult(self.lib, _host(q)[keep], _host(ssq)[keep], _host(grad)[keep], _host(jtj)[keep], _host(lam)[keep],
+                         self._ints_host(status)[keep].astype(np.int32), self._ints_host(iters)[keep].astype(np.int32), n_groups, n_obs)
+
+    def fit(self, q0, data, lo, hi, fd_rel_step=None, ftol=1e-9, max_iter=100, iters_per_launch=8):
+        """Multi-start Levenberg-Marquardt least squares of the device model (set_model) against `data` over the strict box
+        (lo, hi): q0 (n,) or (n, d) start points, d = 1 (Dc) or 3 (Dc, a, b); data (nout,), or (G, nout) with the starts split
+        evenly over the G series in order.  Every start iterates on the GPU (rsf_fit_run, iters_per_launch iterations per launch,
+        one group solve each) until it is CONVERGED (a relative decrease of ssq below ftol), STALLED or max_iter is reached; only
+        the statuses are read between launches.  fd_rel_step: the forward-difference step of the sensitivities, by default 1e-6
+        at d = 1 and 1e-4 at d = 3 (sample_batched's).  → FitResult.  With G > 1 each series' starts are padded to whole
+        workgroups with copies of its first start; the result holds the caller's starts only."""
+        self._need_model()
+        q0, lo, hi, d, fd, ftol, max_iter, ipl = self._fit_args(q0, lo, hi, (1, 3), fd_rel_step, ftol, max_iter, iters_per_launch)
+        obs = _host(data)
+        obs = obs.reshape(1, -1) if obs.ndim == 1 else obs
+        if obs.ndim != 2 or obs.shape[1] != self.nout:
+            raise ValueError(f"data has shape {obs.shape}: (nout,) or (G, nout), the model produces nout = {self.nout} samples")
+        n, G = q0.shape[0], obs.shape[0]
+        if n % G:
+            raise ValueError(f"{n} starts cannot be split evenly over {G} observation series")
+        per = n // G
+        pad = (-per) % self.block_threads if G > 1 else 0
+        keep = (np.arange(n) // per) * (per + pad) + np.arange(n) % per
+        if pad:
+            q0 = np.concatenate([np.concatenate([q0[g * per:(g + 1) * per], np.repeat(q0[g * per:g * per + 1], pad, axis=0)]) for g in range(G)])
+        q, obs = self._in(q0), self._in(obs)
+        ssq, grad, jtj = self.fit_normal(q, obs, fd)
+        running = np.isfinite(_host(ssq))
+        lam = self._in(np.full(q0.shape[0], _abi.FIT_LAM0))
+        status = self._ints(np.where(running, _abi.FIT_RUNNING, _abi.FIT_FAILED))
+        iters = self._ints(np.zeros(q0.shape[0]))
+        done = 0
+        while done < max_iter and running.any():
+            k = min(ipl, max_iter - done)
+            self.fit_run(q, obs, lo, hi, ssq, grad, jtj, lam, status, iters, k, fd, ftol)
+            running = self._ints_host(status) == _abi.FIT_RUNNING
+            done += k
+        return self._fit_result(keep, q, ssq, grad, jtj, lam, status, iters, G, self.nout)
+
+    def fit_from_residuals(self, res_fn, q0, lo, hi, fd_rel_step=None, ftol=1e-9, max_iter=100):
+        """fit with the caller's residuals: res_fn(points (m, d) float64 on the host) → residuals model - data (m, N), called for
+        points strictly inside the box (the trial points and their forward-difference neighbours, parameter p times
+        (1 + fd_rel_step)) and for the start points.  d = 1..3, no model needed.  The normal equations are formed on the host;
+        the trial points and the decisions are the GPU's (rsf_fit_trial, rsf_fit_decide).  The forward-difference step is relative:
+        a coordinate that is exactly 0 has no sensitivity and its start ends STALLED where it is.  → FitResult (one observation group)."""
+        q0, lo, hi, d, fd, ftol, max_iter, _ = self._fit_args(q0, lo, hi, (1, 2, 3), fd_rel_step, ftol, max_iter, 1)
+        n = q0.shape[0]
+
+        def normal(pts):
+            pq = np.repeat(pts[None], d + 1, axis=0)
+            for p in range(d):
+                pq[p + 1, :, p] = pq[p + 1, :, p] * (1 + fd)
+            R = np.asarray(res_fn(pq.reshape(-1, d)), dtype=np.float64)
+            if R.ndim != 2 or R.shape[0] != (d + 1) * n:
+                raise ValueError(f"res_fn returned shape {R.shape} for {(d + 1) * n} points: (m, N) residuals")
+            R = R.reshape(d + 1, n, -1)
+            with np.errstate(invalid="ignore", over="ignore"):
+                X = np.stack([(R[p + 1] - R[0]) / (pq[p + 1, :, p] * fd)[:, None] for p in range(d)])
+                return (R[0] * R[0]).sum(axis=1), np.einsum("pnk,nk->np", X, R[0]), np.einsum("pnk,rnk->npr", X, X), R.shape[2]
+
+        ssq, grad, jtj, n_obs = normal(q0)
+        running = np.isfinite(ssq)
+        q, ssq, grad, jtj, lam = (self._in(x) for x in (q0, ssq, grad, jtj, np.full(n, _abi.FIT_LAM0)))
+        status, iters = self._ints(np.where(running, _abi.FIT_RUNNING, _abi.FIT_FAILED)), self._ints(np.zeros(n))
+        done = 0
+        while done < max_iter and running.any():
+            qt, ok = self.fit_trial(q, grad, jtj, lam, status, lo, hi)
+            s_n, g_n, h_n, _ = normal(_host(qt).reshape(n, d))
+            self.fit_decide(q, ssq, grad, jtj, lam, status, iters, qt, ok, self._in(s_n), self._in(g_n), self._in(h_n), ftol)
+            running = self._ints_host(status) == _abi.FIT_RUNNING
+            done += 1
+        return self._fit_result(np.arange(n), q, ssq, grad, jtj, lam, status, iters, 1, n_obs)
 
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
