@@ -549,6 +549,49 @@ class MCMC:
             eng.sync()
             return self._smc_pool(res)
 
+    @staticmethod
+    def _mala_pool(res, std2, nburn, extra=None):
+        """Engine.mala's result and the kept states' sigma^2 → the PosteriorPool of sample_mala"""
+        stats = {"accepted": int(res.accepted.sum()), "out_of_bounds": int(res.outbox.sum()), "stuck": int(res.stuck.sum()),
+                 "evaluated": int(res.n_iter * res.accepted.shape[0] - res.outbox.sum() - res.stuck.sum()), "n_iter": res.n_iter,
+                 "shape": res.shape, "ssq": res.ssq_trace}
+        stats.update(extra or {})
+        return PosteriorPool(res.samples, std2, res.accept_rate, stats, nburn)
+
+    def sample_mala(self, n_chains, n_iter, nburn=None, start="fit", seed=0, eps=1.0, lam=1e-3, mem="device", device=-1, chain_offset=0, thin=1):
+        """Gauss-Newton manifold MALA (additive; Engine.mala): n_chains chains whose proposal is rebuilt in every iteration from
+        the normal equations at the chain's point — no proposal covariance, no adaptation, an exact Metropolis-Hastings
+        correction; each iteration is one group solve of 1 + d trajectories.  The target is the n0 = 0 posterior
+        pi(q) ~ 1_box SSq^-N/2, sigma^2 drawn afterwards from its conditional.  start="fit": every chain starts at
+        self.fit(seed=seed).best()'s point; start="qstart": at qstart; chains started at one point are independent through their
+        Philox streams (seed, chain_offset + i).  nburn: iterations dropped, by default n_iter // 2; every thin-th of the others is
+        kept.  Returns a PosteriorPool (samples (n_keep, n_chains, d), std2, accept_rate) on which diagnostics, rank_diagnostics,
+        predictive, loo, joint, corner and evidence work unchanged; its stats carry the proposals accepted, out_of_bounds and stuck
+        (no proposal: the metric did not factor), evaluated, the group solves spent, and the kept states' ssq."""
+        n_chains, n_iter = int(n_chains), int(n_iter)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_chains < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1:
+            raise ValueError("n_chains >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1")
+        if start not in ("fit", "qstart"):
+            raise ValueError(f"start is 'fit' or 'qstart', not {start!r}")
+        if not self._device_model():
+            raise TypeError("sample_mala integrates the model on the device: `model` must be this package's RateStateModel")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
+        q0 = np.asarray(self.qstart, dtype=np.float64).reshape(self.n_params)
+        extra = {}
+        if start == "fit":
+            fit = self.fit(seed=seed, device=device)
+            q0 = fit.q[fit.best()]
+            extra["fit"] = fit
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            res = eng.mala(np.tile(q0, (n_chains, 1)), data, lo, hi, n_iter, eps=eps, lam=lam, seed=seed, offset=chain_offset,
+                           keep=n_iter - nburn, thin=thin)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        return self._mala_pool(res, std2, nburn, extra)
+
     def _fit_starts(self, eng, n_starts, seed):
         """start 0 is qstart, the others rsf_smc_init's uniform start in the prior box (seed, particles 0 .. n_starts - 2)"""
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]

@@ -14,12 +14,12 @@ import numpy as np
 
 if __package__:
     from . import _figures, json_save_load
-    from .engine import Engine
+    from .engine import Engine, MalaResult
     from .MCMC import MCMC, PosteriorPool
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     import json_save_load
-    from engine import Engine
+    from engine import Engine, MalaResult
     from MCMC import MCMC, PosteriorPool
 
 
@@ -172,6 +172,39 @@ class RSF:
             cov = res.covariance(i)
             out[float(dc)] = {"q": res.q[i].copy(), "ssq": float(res.ssq[i]), "cov": cov, "stderr": np.sqrt(np.diag(cov)),
                               "status": int(res.status[i]), "iters": int(res.iters[i]), "index": i}
+        return out
+
+    def inference_mala(self, n_chains=256, n_iter=200, nburn=None, start="fit", seed=0, eps=1.0, lam=1e-3, mem="device", device=-1, thin=1):
+        """Additive: the posterior of every true Dc of dc_list by Gauss-Newton manifold MALA in ONE call (Engine.mala) — each is
+        an observation group of n_chains chains, started at its group's least-squares estimate (start="fit": inference_fit) or at
+        qstart (start="qstart").  Returns {dc: PosteriorPool} as MCMC.sample_mala gives it for one group; chain j of group g draws
+        from the Philox stream (seed, g * (n_chains padded to whole workgroups) + j).  The `inference` path is not touched."""
+        n_chains, n_iter = int(n_chains), int(n_iter)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_chains < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1:
+            raise ValueError("n_chains >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1")
+        if start not in ("fit", "qstart"):
+            raise ValueError(f"start is 'fit' or 'qstart', not {start!r}")
+        n, G = self.model.num_tsteps, len(self.dc_list)
+        data = np.ascontiguousarray(np.asarray(self.data, dtype=np.float64).reshape(G, n))
+        probe = MCMC(self.model, data[0], self.dc_list[0], self.qpriors, self.qstart, nsamples=10)
+        lo, hi = probe.qstart_limits[:, 0], probe.qstart_limits[:, 1]
+        starts = np.tile(np.asarray(self.qstart, dtype=np.float64).reshape(1, probe.n_params), (G, 1))
+        if start == "fit":
+            est = self.inference_fit(seed=seed, mem=mem, device=device)
+            starts = np.stack([est[float(dc)]["q"] for dc in self.dc_list])
+        out = {}
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            res = eng.mala(np.repeat(starts, n_chains, axis=0), data, lo, hi, n_iter, eps=eps, lam=lam, seed=seed, keep=n_iter - nburn, thin=thin)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        self.mala_result = res
+        for g, dc in enumerate(self.dc_list):
+            s = slice(g * n_chains, (g + 1) * n_chains)
+            part = MalaResult(res.q[s], res.ssq[s], res.grad[s], res.jtj[s], res.accepted[s], res.outbox[s], res.stuck[s], res.n_iter,
+                              res.samples[:, s], res.ssq_trace[:, s], res.iterations, res.shape, res.seed, res.offset)
+            out[float(dc)] = MCMC._mala_pool(part, std2[:, s], nburn)
         return out
 
     @measure_execution_time

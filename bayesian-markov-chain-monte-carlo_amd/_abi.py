@@ -263,6 +263,18 @@ FIT_MAX_PARAMS = 3  # RSF_FIT_MAX_PARAMS
 FIT_MAX_ITER = 64   # RSF_FIT_MAX_ITER: iterations per rsf_fit_run call
 FIT_RUNNING, FIT_CONVERGED, FIT_STALLED, FIT_FAILED = 0, 1, 2, 3  # RSF_FIT_*: a start's status
 FIT_LAM0 = 1e-3     # RSF_FIT_LAM0: the damping a start begins with
+
+# include/rsf_mala.h: Gauss-Newton manifold MALA; exported by librsf_hip.so only, bound by load()
+MALA_PROTOTYPES = {
+    "rsf_mala_run": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, _P, _P, c_int32, _DP, _DP, c_double, c_double, c_double, c_double, c_uint64,
+                             c_int64, c_int64, c_int32, _P, _P, _P, _P, _P]),
+    "rsf_mala_propose": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, _P, _DP, _DP, c_double, c_double, c_double, c_uint64, c_int64, c_int64,
+                                 _P, _P, _P]),
+    "rsf_mala_accept": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, _P, _DP, _DP, c_double, c_double, c_double, c_uint64, c_int64, c_int64,
+                                _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+MALA_MAX_PARAMS = 3  # RSF_MALA_MAX_PARAMS
+MALA_MAX_ITER = 64   # RSF_MALA_MAX_ITER: iterations per rsf_mala_run call
 MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
 
 
@@ -310,7 +322,7 @@ def load():
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
-                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES):
+                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

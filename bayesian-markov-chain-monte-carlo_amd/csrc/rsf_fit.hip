@@ -10,40 +10,6 @@ using namespace rsfh;
 
 namespace {
 
-unsigned blocks_of(int64_t n) { return (unsigned)((n + kMaxBlock - 1) / kMaxBlock); }
-
-// The arrays of one call for an RSF_MEM_HOST caller.  These calls take more arrays than the ctx has named staging slots
-// (rsf_host.h, Slot), so they stage all of them in ONE workspace, the ctx's pool buffer: add() every array, commit() sizes the
-// workspace and copies the inputs in, dev() is the pointer the kernels take, back() copies the outputs out.  A device caller's
-// pointers pass through.
-struct Staged {
-  struct Item { void *host; size_t bytes, off; bool in, out; };
-  rsf_ctx *c;
-  Item items[12];
-  int count = 0;
-  size_t total = 0;
-  explicit Staged(rsf_ctx *ctx) : c(ctx) {}
-  int add(const void *p, size_t bytes, bool in, bool out) {
-    items[count] = {const_cast<void *>(p), bytes, total, in, out};
-    total += (bytes + 255) & ~(size_t)255;
-    return count++;
-  }
-  int commit() {
-    if (!host_mem(c)) return RSF_OK;
-    if (int rc = ensure(c->pool, total)) return rc;
-    for (int k = 0; k < count; ++k)
-      if (items[k].in) HIP_TRY(hipMemcpyAsync((char *)c->pool.p + items[k].off, items[k].host, items[k].bytes, hipMemcpyHostToDevice, c->stream));
-    return RSF_OK;
-  }
-  template <class T> T *dev(int k) const { return host_mem(c) ? (T *)((char *)c->pool.p + items[k].off) : (T *)items[k].host; }
-  int back() {
-    if (!host_mem(c)) return RSF_OK;
-    for (int k = 0; k < count; ++k)
-      if (items[k].out) HIP_TRY(hipMemcpyAsync(items[k].host, (char *)c->pool.p + items[k].off, items[k].bytes, hipMemcpyDeviceToHost, c->stream));
-    return RSF_OK;
-  }
-};
-
 int set_box(const char *fn, int d, const double *lo, const double *hi, FitArgs &A) {
   for (int p = 0; p < d; ++p) {
     if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "%s: need finite lo[%d] < hi[%d]", fn, p, p);

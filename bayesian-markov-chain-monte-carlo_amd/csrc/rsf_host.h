@@ -162,6 +162,41 @@ template <class T> int stage_out(rsf_ctx *c, Slot slot, T *dst, size_t bytes, T 
 int copy_back(rsf_ctx *c, Slot slot, void *dst, size_t bytes);
 int finish(rsf_ctx *c);  // host callers get synchronous semantics
 
+// one thread per element in workgroups of kMaxBlock
+inline unsigned blocks_of(int64_t n) { return (unsigned)((n + rsfk::kMaxBlock - 1) / rsfk::kMaxBlock); }
+
+// The arrays of one call for an RSF_MEM_HOST caller of rsf_fit.hip and rsf_mala.hip.  Their calls take more arrays than the ctx
+// has named staging slots (Slot above), so they stage all of them in ONE workspace, the ctx's pool buffer: add() every array,
+// commit() sizes the workspace and copies the inputs in, dev() is the pointer the kernels take, back() copies the outputs out.  A
+// device caller's pointers pass through.
+struct Staged {
+  struct Item { void *host; size_t bytes, off; bool in, out; };
+  rsf_ctx *c;
+  Item items[16];
+  int count = 0;
+  size_t total = 0;
+  explicit Staged(rsf_ctx *ctx) : c(ctx) {}
+  int add(const void *p, size_t bytes, bool in, bool out) {
+    items[count] = {const_cast<void *>(p), bytes, total, in, out};
+    total += (bytes + 255) & ~(size_t)255;
+    return count++;
+  }
+  int commit() {
+    if (!host_mem(c)) return RSF_OK;
+    if (int rc = ensure(c->pool, total)) return rc;
+    for (int k = 0; k < count; ++k)
+      if (items[k].in) HIP_TRY(hipMemcpyAsync((char *)c->pool.p + items[k].off, items[k].host, items[k].bytes, hipMemcpyHostToDevice, c->stream));
+    return RSF_OK;
+  }
+  template <class T> T *dev(int k) const { return host_mem(c) ? (T *)((char *)c->pool.p + items[k].off) : (T *)items[k].host; }
+  int back() {
+    if (!host_mem(c)) return RSF_OK;
+    for (int k = 0; k < count; ++k)
+      if (items[k].out) HIP_TRY(hipMemcpyAsync(items[k].host, (char *)c->pool.p + items[k].off, items[k].bytes, hipMemcpyDeviceToHost, c->stream));
+    return RSF_OK;
+  }
+};
+
 // What an entry point that touches the device begins with: its arguments (a NULL ctx, and whatever else the caller folds
 // into args_ok and names in `what`), the state it needs, and the ctx's device selected for as long as the caller's guard
 // lives.  fn: the entry point the messages name.

@@ -16,8 +16,6 @@ using namespace rsfh;
 
 namespace {
 
-unsigned blocks_of(int64_t n) { return (unsigned)((n + kMaxBlock - 1) / kMaxBlock); }
-
 // the box of a call into A.lo[], A.hi[]; fn: the entry point the message names
 int set_box(const char *fn, int d, const double *lo, const double *hi, SmcArgs &A) {
   for (int p = 0; p < d; ++p) {

@@ -8,6 +8,7 @@ device memory and streams) and the work is ordered on the current torch stream.
 The class is library-agnostic (`lib` is any handle typed by _abi.bind) so the test-suite can
 drive the CPU oracle through the very same code; the product always passes _abi.load().
 """
+import contextlib
 import ctypes
 import math
 import os
@@ -280,6 +281,35 @@ class FitResult:
         i, cov, logi, ev = self._laplace(shape, lo, hi, i)
         return {"index": i, "q": self.q[i].copy(), "ssq": float(self.ssq[i]), "cov": cov, "stderr": np.sqrt(np.diag(cov)), "log_integral": logi,
                 "log_evidence": ev, "shape": shape}
+
+
+class MalaResult:
+    """Result of Engine.mala / Engine.mala_from_residuals: per chain the final state q (n, d), ssq (n,), grad = X^T r (n, d) and
+    jtj = X^T X (n, d, d), the counters accepted, outbox (proposals outside the box) and stuck (iterations without a proposal),
+    (n,) int32, over n_iter iterations; samples (n_keep, n, d) and ssq_trace (n_keep, n), the kept states, and iterations (n_keep,),
+    the 1-based iteration of each kept row.  NumPy arrays on the host.  The target is pi(q) ~ 1_box SSq^-shape; std2 completes it."""
+
+    def __init__(self, q, ssq, grad, jtj, accepted, outbox, stuck, n_iter, samples, ssq_trace, iterations, shape, seed, offset):
+        self.q, self.ssq, self.grad, self.jtj, self.accepted, self.outbox, self.stuck = q, ssq, grad, jtj, accepted, outbox, stuck
+        self.n_iter, self.samples, self.ssq_trace, self.iterations = int(n_iter), samples, ssq_trace, iterations
+        self.shape, self.seed, self.offset = float(shape), int(seed), int(offset)
+
+    @property
+    def accept_rate(self):
+        """accepted proposals / iterations, over all chains"""
+        return float(self.accepted.sum()) / (self.n_iter * self.accepted.shape[0])
+
+    def std2(self, seed=None, engine=None, kept=False):
+        """sigma^2 | q ~ InvGamma(shape, ssq / 2) by Engine.smc_std2 (l = -shape log ssq) of the final states → (n,), or with
+        kept=True of the kept states → (n_keep, n), row r with the gamma variates of Philox iteration iterations[r].  seed: by
+        default the run's; engine: by default a host-memory Engine made for the call."""
+        seed = self.seed if seed is None else int(seed)
+        rows = self.ssq_trace if kept else self.ssq[None]
+        its = self.iterations if kept else [self.n_iter]
+        with contextlib.nullcontext(engine) if engine is not None else Engine(mem="host") as eng:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out = [_host(eng.smc_std2(-self.shape * np.log(r), self.shape, seed, self.offset, int(t))) for r, t in zip(rows, its)]
+        return np.stack(out) if kept else out[0]
 
 
 class Engine:
@@ -1462,6 +1492,190 @@ class Engine:
             running = self._ints_host(status) == _abi.FIT_RUNNING
             done += 1
         return self._fit_result(np.arange(n), q, ssq, grad, jtj, lam, status, iters, 1, n_obs)
+
+    # -- Gauss-Newton manifold MALA (include/rsf_mala.h) ----------------------------------------------------------
+    @staticmethod
+    def _mala_args(q0, lo, hi, dims, n_iter, eps, lam, shape, seed, offset, fd_rel_step, iters_per_launch, keep, thin):
+        """The checks Engine.mala and mala_from_residuals share, made before any library call → (q0 (n, d) a fresh host array, lo,
+        hi, d, fd, n_iter, eps, lam, shape, seed, offset, iters_per_launch, keep, thin)"""
+        q0 = _host(q0).copy()
+        if q0.ndim == 1:
+            q0 = q0.reshape(-1, 1)
+        if q0.ndim != 2 or q0.shape[0] < 1 or q0.shape[1] not in dims:
+            raise ValueError(f"q0 has shape {q0.shape}: (n,) or (n, d) start points, d one of {dims}")
+        d = int(q0.shape[1])
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo < hi).all()):
+            raise ValueError("the box needs finite lo < hi in every parameter")
+        if not ((q0 > lo).all() and (q0 < hi).all()):
+            raise ValueError("every start point lies strictly inside the box")
+        fd = (1e-6 if d == 1 else 1e-4) if fd_rel_step is None else float(fd_rel_step)
+        n_iter, eps, lam, ipl, keep, thin = int(n_iter), float(eps), float(lam), int(iters_per_launch), int(keep), int(thin)
+        if not (math.isfinite(fd) and fd > 0.0 and math.isfinite(eps) and eps > 0.0 and math.isfinite(lam) and lam >= 0.0):
+            raise ValueError("fd_rel_step and eps are finite and > 0, lam is finite and >= 0")
+        if shape is not None and not (math.isfinite(float(shape)) and float(shape) > 0.0):
+            raise ValueError("shape is finite and > 0")
+        if not (n_iter >= 1 and 1 <= ipl <= _abi.MALA_MAX_ITER and 0 <= keep <= n_iter and thin >= 1 and int(seed) >= 0 and int(offset) >= 0):
+            raise ValueError(f"n_iter >= 1, iters_per_launch in [1, {_abi.MALA_MAX_ITER}], 0 <= keep <= n_iter, thin >= 1, seed >= 0, offset >= 0")
+        return q0, lo, hi, d, fd, n_iter, eps, lam, None if shape is None else float(shape), int(seed), int(offset), ipl, keep, thin
+
+    def _mala_state(self, q, ssq, grad, jtj, accepted=None, outbox=None, stuck=None):
+        """The check of a chain state handed to the low-level calls, which read and write it through raw addresses: q (n, d), ssq
+        (n,), grad (n, d), jtj (n, d, d) float64 and the counters (n,) int32, each a C-contiguous array of this engine's memory
+        space → (n, d)"""
+        if getattr(q, "ndim", 0) != 2:
+            raise ValueError("q is (n, d)")
+        n, d = int(q.shape[0]), int(q.shape[1])
+        t = self._torch
+        for what, x, shape, dt in (("q", q, (n, d), "float64"), ("ssq", ssq, (n,), "float64"), ("grad", grad, (n, d), "float64"),
+                                   ("jtj", jtj, (n, d, d), "float64"), ("accepted", accepted, (n,), "int32"), ("outbox", outbox, (n,), "int32"),
+                                   ("stuck", stuck, (n,), "int32")):
+            if x is None and dt == "int32":
+                continue
+            if self.mem == "device":
+                good = isinstance(x, t.Tensor) and x.is_cuda and x.is_contiguous() and str(x.dtype) == "torch." + dt
+            else:
+                good = isinstance(x, np.ndarray) and x.flags["C_CONTIGUOUS"] and x.dtype == np.dtype(dt)
+            if not good or tuple(x.shape) != shape:
+                raise ValueError(f"{what} must be a C-contiguous {dt} array of shape {shape} in this engine's memory space ({self.mem})")
+        return n, d
+
+    def mala_run(self, q, ssq, grad, jtj, data, lo, hi, n_iter, accepted, outbox, stuck, eps=1.0, lam=_abi.FIT_LAM0, shape=None, seed=0,
+                 offset=0, iter0=1, fd_rel_step=None, trace=False):
+        """rsf_mala_run, the fused hot path: n_iter iterations IN PLACE in q (n, d), ssq, grad, jtj (as fit_normal leaves them) and
+        the int32 counters accepted, outbox and stuck, contiguous arrays of this engine's memory space; iteration k uses the draws
+        of Philox iteration iter0 + k of chain offset + i.  trace=True → (trace_q (n_iter, n, d), trace_ssq (n_iter, n)), the state
+        after each iteration."""
+        self._need_model()
+        n, d = self._mala_state(q, ssq, grad, jtj, accepted, outbox, stuck)
+        data = self._in(data)
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        fd = (1e-6 if d == 1 else 1e-4) if fd_rel_step is None else float(fd_rel_step)
+        tq, ts = (self._empty((int(n_iter), n, d)), self._empty((int(n_iter), n))) if trace else (None, None)
+        _abi.check(self.lib, self.lib.rsf_mala_run(self._ctx, n, d, self._ptr(q), self._ptr(ssq), self._ptr(grad), self._ptr(jtj), self._ptr(data), G,
+                                                   _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")), fd, float(eps), float(lam),
+                                                   float(0.5 * self.nout if shape is None else shape), int(seed), int(offset), int(iter0), int(n_iter),
+                                                   self._ptr(accepted), self._ptr(outbox), self._ptr(stuck), self._ptr(tq), self._ptr(ts)))
+        return (tq, ts) if trace else None
+
+    def mala_propose(self, q, ssq, grad, jtj, lo, hi, shape, eps=1.0, lam=_abi.FIT_LAM0, seed=0, offset=0, iteration=1):
+        """rsf_mala_propose: the proposals of one iteration → (q_new (n, d), inbox (n,) uint8, stuck (n,) uint8).  inbox is 0 for
+        a proposal outside the box and for a chain without a proposal, which stuck marks; such a chain's q_new row is its q."""
+        n, d = self._mala_state(q, ssq, grad, jtj)
+        qn, inb, stk = self._empty((n, d)), self._empty((n,), np.uint8), self._empty((n,), np.uint8)
+        _abi.check(self.lib, self.lib.rsf_mala_propose(self._ctx, n, d, self._ptr(q), self._ptr(ssq), self._ptr(grad), self._ptr(jtj),
+                                                       _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")), float(eps), float(lam), float(shape), int(seed),
+                                                       int(offset), int(iteration), self._ptr(qn), self._ptr(inb), self._ptr(stk)))
+        return qn, inb, stk
+
+    def mala_accept(self, q, ssq, grad, jtj, lo, hi, q_new, inbox, ssq_new, grad_new, jtj_new, accepted, outbox, stuck, shape, eps=1.0,
+                    lam=_abi.FIT_LAM0, seed=0, offset=0, iteration=1):
+        """rsf_mala_accept: the decision of one iteration with the caller's normal equations at mala_propose's q_new, IN PLACE in
+        q, ssq, grad, jtj and the int32 counters (contiguous arrays of this engine's memory space); q_new (n, d), inbox (n,),
+        ssq_new (n,), grad_new (n, d) and jtj_new (n, d, d) are read (the sums where inbox is 1) and may have any layout.  The
+        other arguments are mala_propose's."""
+        n, d = self._mala_state(q, ssq, grad, jtj, accepted, outbox, stuck)
+        q_new, inbox, ssq_new, grad_new, jtj_new = self._in(q_new), self._bytes(inbox), self._in(ssq_new), self._in(grad_new), self._in(jtj_new)
+        if (tuple(q_new.shape), tuple(inbox.shape), tuple(ssq_new.shape), tuple(grad_new.shape), tuple(jtj_new.shape)) != ((n, d), (n,), (n,), (n, d), (n, d, d)):
+            raise ValueError(f"q_new and grad_new are ({n}, {d}), inbox and ssq_new ({n},), jtj_new ({n}, {d}, {d})")
+        _abi.check(self.lib, self.lib.rsf_mala_accept(self._ctx, n, d, self._ptr(q), self._ptr(ssq), self._ptr(grad), self._ptr(jtj),
+                                                      _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")), float(eps), float(lam), float(shape), int(seed),
+                                                      int(offset), int(iteration), self._ptr(q_new), self._ptr(inbox), self._ptr(ssq_new),
+                                                      self._ptr(grad_new), self._ptr(jtj_new), self._ptr(accepted), self._ptr(outbox), self._ptr(stuck)))
+
+    def _mala_result(self, sel, q, ssq, grad, jtj, counters, n_iter, kept, keep, thin, shape, seed, offset):
+        d = int(q.shape[1])
+        tq = np.concatenate([_host(x)[:, sel] for x, _ in kept]) if kept else np.empty((0, sel.size, d))
+        ts = np.concatenate([_host(x)[:, sel] for _, x in kept]) if kept else np.empty((0, sel.size))
+        rows = np.arange(n_iter - keep, n_iter)[::thin]
+        pick = rows - (n_iter - tq.shape[0])  # the kept launches end at the last iteration
+        return MalaResult(_host(q)[sel], _host(ssq)[sel], _host(grad)[sel], _host(jtj)[sel], *(self._ints_host(c)[sel].astype(np.int32) for c in counters),
+                          n_iter, np.ascontiguousarray(tq[pick]), np.ascontiguousarray(ts[pick]), rows + 1, shape, seed, offset)
+
+    def mala(self, q0, data, lo, hi, n_iter, eps=1.0, lam=_abi.FIT_LAM0, shape=None, seed=0, offset=0, fd_rel_step=None, iters_per_launch=16,
+             keep=0, thin=1):
+        """Gauss-Newton manifold MALA of the device model (set_model) against `data` over the strict box (lo, hi), target
+        pi(q) ~ SSq(q)^-shape (shape: by default nout / 2): q0 (n,) or (n, d) start points inside the box, d = 1 (Dc) or 3 (Dc, a,
+        b); data (nout,), or (G, nout) with the chains split evenly over the G series in order.  rsf_fit_normal at q0, then n_iter
+        iterations on the GPU (rsf_mala_run, iters_per_launch per launch, one group solve each).  No proposal covariance, no
+        adaptation: eps is the step (1: the Gauss-Newton posterior approximation's own scale), lam the damping of the metric.
+        Chain i draws from the Philox stream (seed, offset + i), so chains started at one point are independent.  keep: the
+        trailing iterations whose states are kept, every thin-th of them → MalaResult.  With G > 1 each series' chains are padded
+        to whole workgroups with copies of its first chain (chain j of series g then has stream offset + g (n / G + pad) + j); the
+        result holds the caller's chains only."""
+        self._need_model()
+        q0, lo, hi, d, fd, n_iter, eps, lam, shape, seed, offset, ipl, keep, thin = self._mala_args(
+            q0, lo, hi, (1, 3), n_iter, eps, lam, shape, seed, offset, fd_rel_step, iters_per_launch, keep, thin)
+        shape = 0.5 * self.nout if shape is None else shape
+        obs = _host(data)
+        obs = obs.reshape(1, -1) if obs.ndim == 1 else obs
+        if obs.ndim != 2 or obs.shape[1] != self.nout:
+            raise ValueError(f"data has shape {obs.shape}: (nout,) or (G, nout), the model produces nout = {self.nout} samples")
+        n, G = q0.shape[0], obs.shape[0]
+        if n % G:
+            raise ValueError(f"{n} chains cannot be split evenly over {G} observation series")
+        per = n // G
+        pad = (-per) % self.block_threads if G > 1 else 0
+        sel = (np.arange(n) // per) * (per + pad) + np.arange(n) % per
+        if pad:
+            q0 = np.concatenate([np.concatenate([q0[g * per:(g + 1) * per], np.repeat(q0[g * per:g * per + 1], pad, axis=0)]) for g in range(G)])
+        q, obs = self._in(q0), self._in(obs)
+        ssq, grad, jtj = self.fit_normal(q, obs, fd)
+        counters = [self._ints(np.zeros(q0.shape[0])) for _ in range(3)]
+        kept, done = [], 0
+        while done < n_iter:
+            k = min(ipl, n_iter - done)
+            tr = self.mala_run(q, ssq, grad, jtj, obs, lo, hi, k, *counters, eps=eps, lam=lam, shape=shape, seed=seed, offset=offset, iter0=done + 1,
+                               fd_rel_step=fd, trace=done + k > n_iter - keep)
+            if tr is not None:
+                kept.append(tr)
+            done += k
+        return self._mala_result(sel, q, ssq, grad, jtj, counters, n_iter, kept, keep, thin, shape, seed, offset)
+
+    def mala_from_residuals(self, res_fn, q0, lo, hi, n_iter, shape, eps=1.0, lam=_abi.FIT_LAM0, seed=0, offset=0, fd_rel_step=None, keep=0, thin=1,
+                            normal_fn=None):
+        """mala with the caller's residuals: res_fn(points (m, d) float64 on the host) → residuals model - data (m, N), called for
+        the start points, the proposals inside the box and their forward-difference neighbours (parameter p times
+        (1 + fd_rel_step)), exactly as fit_from_residuals calls it.  d = 1..3, no model needed; shape has no default.  The normal
+        equations are formed on the host, the proposals and the decisions are the GPU's (rsf_mala_propose, rsf_mala_accept).
+        normal_fn(points (n, d)) → (ssq (n,), grad (n, d), jtj (n, d, d)), if given, replaces res_fn and its forward differences
+        (any deterministic function of the point with a positive definite jtj is a valid metric).  → MalaResult."""
+        if shape is None:
+            raise ValueError("shape is finite and > 0")
+        q0, lo, hi, d, fd, n_iter, eps, lam, shape, seed, offset, _, keep, thin = self._mala_args(
+            q0, lo, hi, (1, 2, 3), n_iter, eps, lam, shape, seed, offset, fd_rel_step, 1, keep, thin)
+        if (res_fn is None) == (normal_fn is None):
+            raise ValueError("one of res_fn and normal_fn")
+        n = q0.shape[0]
+
+        def normal(pts):
+            if normal_fn is not None:
+                s, g, h = (np.ascontiguousarray(x, dtype=np.float64) for x in normal_fn(pts))
+                if (s.shape, g.shape, h.shape) != ((n,), (n, d), (n, d, d)):
+                    raise ValueError(f"normal_fn returned shapes {s.shape}, {g.shape}, {h.shape} for {n} points")
+                return s, g, h
+            pq = np.repeat(pts[None], d + 1, axis=0)
+            for p in range(d):
+                pq[p + 1, :, p] = pq[p + 1, :, p] * (1 + fd)
+            R = np.asarray(res_fn(pq.reshape(-1, d)), dtype=np.float64)
+            if R.ndim != 2 or R.shape[0] != (d + 1) * n:
+                raise ValueError(f"res_fn returned shape {R.shape} for {(d + 1) * n} points: (m, N) residuals")
+            R = R.reshape(d + 1, n, -1)
+            with np.errstate(invalid="ignore", over="ignore"):
+                X = np.stack([(R[p + 1] - R[0]) / (pq[p + 1, :, p] * fd)[:, None] for p in range(d)])
+                return (R[0] * R[0]).sum(axis=1), np.einsum("pnk,nk->np", X, R[0]), np.einsum("pnk,rnk->npr", X, X)
+
+        q, ssq, grad, jtj = (self._in(x) for x in (q0, *normal(q0)))
+        counters = [self._ints(np.zeros(n)) for _ in range(3)]
+        kept = []
+        for it in range(1, n_iter + 1):
+            kw = dict(shape=shape, eps=eps, lam=lam, seed=seed, offset=offset, iteration=it)
+            qn, inb, _ = self.mala_propose(q, ssq, grad, jtj, lo, hi, **kw)
+            s_n, g_n, h_n = normal(_host(qn).reshape(n, d))
+            self.mala_accept(q, ssq, grad, jtj, lo, hi, qn, inb, s_n, g_n, h_n, *counters, **kw)
+            if it > n_iter - keep:
+                kept.append((_host(q).copy()[None], _host(ssq).copy()[None]))
+        return self._mala_result(np.arange(n), q, ssq, grad, jtj, counters, n_iter, kept, keep, thin, shape, seed, offset)
 
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
