@@ -26,11 +26,11 @@ import numpy as np
 if __package__:
     from . import _figures
     from ._abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from .engine import Engine, _host, bayes_factor  # noqa: F401
+    from .engine import Engine, _host, bayes_factor, whole_islands  # noqa: F401
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     from _abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from engine import Engine, _host, bayes_factor  # noqa: F401
+    from engine import Engine, _host, bayes_factor, whole_islands  # noqa: F401
 
 
 @contextlib.contextmanager
@@ -591,6 +591,79 @@ class MCMC:
             std2 = res.std2(engine=eng, kept=True)
             eng.sync()
         return self._mala_pool(res, std2, nburn, extra)
+
+    @staticmethod
+    def _ensemble_pool(res, std2, nburn, extra=None):
+        """Engine.ensemble's result and the kept states' sigma^2 → the PosteriorPool of sample_ensemble (superchains: the islands)"""
+        n = res.accepted.shape[0]
+        stats = {"accepted": int(res.accepted.sum()), "out_of_bounds": int(res.outbox.sum()), "stuck": int(res.stuck.sum()),
+                 "evaluated": int(res.n_iter * n - res.outbox.sum() - res.stuck.sum()), "n_iter": res.n_iter, "shape": res.shape,
+                 "l": res.trace_l, "n_walkers": n, "island_size": res.island_size, "n_islands": n // res.island_size, "logmask": res.logmask, "a": res.a}
+        stats.update(extra or {})
+        return PosteriorPool(res.trace_q, std2, res.accept_rate, stats, nburn, superchain_size=res.island_size)
+
+    @staticmethod
+    def _ensemble_mask(log_coords, d):
+        return (True, True, False)[:d] if log_coords is None and d == 3 else ((False,) * d if log_coords is None else log_coords)
+
+    @staticmethod
+    def _ensemble_ball(center, lo, hi, mask, n, rng, scale=1e-3):
+        """n points around `center` from N(0, scale^2) in the sampler's coordinates (log q_p under a mask bit), redrawn until inside the box"""
+        center, out, todo = np.asarray(center, dtype=np.float64), np.empty((n, len(center))), np.arange(n)
+        logp = np.array([(mask >> p) & 1 for p in range(len(center))], dtype=bool)
+        phi = np.where(logp, np.log(np.where(logp, center, 1.0)), center)
+        for _ in range(1000):
+            u = phi + scale * rng.standard_normal((todo.size, len(center)))
+            out[todo] = np.where(logp, np.exp(np.where(logp, u, 0.0)), u)
+            todo = todo[~((out[todo] > lo) & (out[todo] < hi)).all(axis=1)]
+            if todo.size == 0:
+                return out
+        raise ValueError("no start inside the box around the fit's point: it lies on the box's edge")
+
+    def sample_ensemble(self, n_walkers, n_iter, nburn=None, start="fit", log_coords=None, a=2.0, seed=0, mem="device", device=-1, offset=0, thin=1,
+                        iters_per_launch=16):
+        """The affine-invariant ensemble sampler in islands (additive; Engine.ensemble): walkers that take their proposals from
+        each other's positions (the stretch move) — no proposal covariance, no gradient, one forward solve per proposal.  An island
+        is an independent ensemble of Engine.island_size walkers; n_walkers is ROUNDED UP to whole islands and the pool's
+        stats["n_walkers"] reports the number run.  log_coords: per parameter, whether it moves as its logarithm; by default
+        (True, True, False) with three parameters — in (log Dc, log a, b) the ridge Dc a = const is a straight line — and (False,)
+        with one.  start="fit": the walkers start in a ball around self.fit(seed=seed).best()'s point, N(0, (1e-3)^2) in the
+        sampler's coordinates, redrawn until inside the box; start="smc": at the final particles of Engine.smc; an array
+        (n_walkers rounded, d): there.  The target is the n0 = 0 posterior pi(q) ~ 1_box SSq^-N/2, sigma^2 drawn afterwards from
+        its conditional.  nburn: iterations dropped, by default n_iter // 2; every thin-th of the others is kept.  Returns a
+        PosteriorPool (samples (n_keep, n_walkers, d), std2, accept_rate) whose superchains are the islands:
+        pool.diagnostics() gives the nested R-hat over islands."""
+        n_walkers, n_iter = int(n_walkers), int(n_iter)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_walkers < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1:
+            raise ValueError("n_walkers >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1")
+        if isinstance(start, str) and start not in ("fit", "smc"):
+            raise ValueError(f"start is 'fit', 'smc' or an array of walkers, not {start!r}")
+        if not self._device_model():
+            raise TypeError("sample_ensemble integrates the model on the device: `model` must be this package's RateStateModel")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
+        d, extra = self.n_params, {}
+        with Engine(mem=mem, device=device) as eng:
+            n = whole_islands(n_walkers, eng.island_size)
+            mask = eng._ens_mask(self._ensemble_mask(log_coords, d), d)
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            if isinstance(start, str) and start == "fit":
+                fit = self.fit(seed=seed, device=device)
+                extra["fit"] = fit
+                q0 = self._ensemble_ball(fit.q[fit.best()], lo, hi, mask, n, np.random.default_rng([int(seed), int(offset)]))
+            elif isinstance(start, str):
+                res0 = eng.smc(data, lo, hi, n, seed=seed, offset=offset)
+                q0, extra["smc_stages"] = _host(res0["q"]), len(res0["stages"])
+            else:
+                q0 = _host(start).reshape(-1, d)
+                if q0.shape[0] != n:
+                    raise ValueError(f"start holds {q0.shape[0]} walkers: {n_walkers} rounded up to whole islands of {eng.island_size} is {n}")
+            res = eng.ensemble(q0, data, lo, hi, n_iter, a=a, log_coords=mask, seed=seed, offset=offset, iters_per_launch=iters_per_launch,
+                               keep=n_iter - nburn, thin=thin)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        return self._ensemble_pool(res, std2, nburn, extra)
 
     def _fit_starts(self, eng, n_starts, seed):
         """start 0 is qstart, the others rsf_smc_init's uniform start in the prior box (seed, particles 0 .. n_starts - 2)"""

@@ -14,12 +14,12 @@ import numpy as np
 
 if __package__:
     from . import _figures, json_save_load
-    from .engine import Engine, MalaResult
+    from .engine import Engine, EnsembleResult, MalaResult, whole_islands
     from .MCMC import MCMC, PosteriorPool
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     import json_save_load
-    from engine import Engine, MalaResult
+    from engine import Engine, EnsembleResult, MalaResult, whole_islands
     from MCMC import MCMC, PosteriorPool
 
 
@@ -205,6 +205,44 @@ class RSF:
             part = MalaResult(res.q[s], res.ssq[s], res.grad[s], res.jtj[s], res.accepted[s], res.outbox[s], res.stuck[s], res.n_iter,
                               res.samples[:, s], res.ssq_trace[:, s], res.iterations, res.shape, res.seed, res.offset)
             out[float(dc)] = MCMC._mala_pool(part, std2[:, s], nburn)
+        return out
+
+    def inference_ensemble(self, n_walkers=512, n_iter=200, nburn=None, start="fit", log_coords=None, a=2.0, seed=0, mem="device", device=-1, thin=1):
+        """Additive: the posterior of every true Dc of dc_list by the affine-invariant ensemble sampler in ONE call
+        (Engine.ensemble) — each is an observation group of n_walkers walkers (rounded up to whole islands), started in a ball
+        around its group's least-squares estimate (start="fit": inference_fit) or around qstart (start="qstart").  Returns
+        {dc: PosteriorPool} as MCMC.sample_ensemble gives it for one group; walker j of group g draws from the Philox stream
+        (seed, g * n_walkers + j).  The `inference` path is not touched."""
+        n_walkers, n_iter = int(n_walkers), int(n_iter)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_walkers < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1:
+            raise ValueError("n_walkers >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1")
+        if start not in ("fit", "qstart"):
+            raise ValueError(f"start is 'fit' or 'qstart', not {start!r}")
+        n, G = self.model.num_tsteps, len(self.dc_list)
+        data = np.ascontiguousarray(np.asarray(self.data, dtype=np.float64).reshape(G, n))
+        probe = MCMC(self.model, data[0], self.dc_list[0], self.qpriors, self.qstart, nsamples=10)
+        lo, hi = probe.qstart_limits[:, 0], probe.qstart_limits[:, 1]
+        d = probe.n_params
+        starts = np.tile(np.asarray(self.qstart, dtype=np.float64).reshape(1, d), (G, 1))
+        if start == "fit":
+            est = self.inference_fit(seed=seed, mem=mem, device=device)
+            starts = np.stack([est[float(dc)]["q"] for dc in self.dc_list])
+        out = {}
+        with Engine(mem=mem, device=device) as eng:
+            per = whole_islands(n_walkers, eng.island_size)
+            mask = eng._ens_mask(MCMC._ensemble_mask(log_coords, d), d)
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            q0 = np.concatenate([MCMC._ensemble_ball(starts[g], lo, hi, mask, per, np.random.default_rng([int(seed), g])) for g in range(G)])
+            res = eng.ensemble(q0, data, lo, hi, n_iter, a=a, log_coords=mask, seed=seed, keep=n_iter - nburn, thin=thin)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        self.ensemble_result = res
+        for g, dc in enumerate(self.dc_list):
+            s = slice(g * per, (g + 1) * per)
+            part = EnsembleResult(res.q[s], res.l[s], res.accepted[s], res.outbox[s], res.stuck[s], res.n_iter, res.trace_q[:, s], res.trace_l[:, s],
+                                  res.iterations, res.island_size, res.shape, res.seed, res.offset + g * per, res.logmask, res.a)
+            out[float(dc)] = MCMC._ensemble_pool(part, std2[:, s], nburn)
         return out
 
     @measure_execution_time

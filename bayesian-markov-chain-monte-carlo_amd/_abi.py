@@ -275,6 +275,17 @@ MALA_PROTOTYPES = {
 }
 MALA_MAX_PARAMS = 3  # RSF_MALA_MAX_PARAMS
 MALA_MAX_ITER = 64   # RSF_MALA_MAX_ITER: iterations per rsf_mala_run call
+# include/rsf_ensemble.h: the affine-invariant stretch move in island ensembles; exported by librsf_hip.so only, bound by load()
+ENSEMBLE_PROTOTYPES = {
+    "rsf_ensemble_run": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, c_int32, _DP, _DP, c_double, c_uint32, c_double, c_uint64, c_int64, c_int64,
+                                 c_int32, _P, _P, _P, _P, _P]),
+    "rsf_ensemble_propose": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _DP, _DP, c_double, c_uint32, c_uint64, c_int64, c_int64, c_int32, _P, _P, _P]),
+    "rsf_ensemble_accept": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _DP, _DP, c_double, c_uint64, c_int64, c_int64, c_int32, _P, _P, _P, _P,
+                                    _P, _P, _P]),
+    "rsf_ensemble_ssq": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, c_int32, c_int32, _P]),
+}
+ENSEMBLE_MAX_PARAMS = 3  # RSF_ENSEMBLE_MAX_PARAMS
+ENSEMBLE_MAX_ITER = 64   # RSF_ENSEMBLE_MAX_ITER: iterations per rsf_ensemble_run call
 MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
 
 
@@ -322,7 +333,7 @@ def load():
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
-                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES):
+                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

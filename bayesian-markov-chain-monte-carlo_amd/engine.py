@@ -312,6 +312,53 @@ class MalaResult:
         return np.stack(out) if kept else out[0]
 
 
+def whole_islands(n_walkers, island_size):
+    """n_walkers rounded up to whole islands of island_size walkers (the ensemble sampler runs whole islands only)"""
+    n_walkers, island_size = int(n_walkers), int(island_size)
+    if n_walkers < 1 or island_size < 2 or island_size % 2:
+        raise ValueError("n_walkers >= 1 and an even island_size >= 2")
+    return -(-n_walkers // island_size) * island_size
+
+
+class EnsembleResult:
+    """Result of Engine.ensemble / Engine.ensemble_from_ssq: per walker the final state q (n, d) and l = -shape log SSq (n,), the
+    counters accepted, outbox (proposals outside the box) and stuck (half-steps without a proposal), (n,) int32, over n_iter
+    iterations; trace_q (n_keep, n, d) and trace_l (n_keep, n), the kept states, and iterations (n_keep,), the 1-based iteration of
+    each kept row.  island_size = 2 x the engine's workgroup size: walkers k island_size .. (k + 1) island_size - 1 are island k, an
+    independent replicate, so Engine.diagnostics(trace_q, superchain_size=island_size) is the nested R-hat over islands.  NumPy
+    arrays on the host.  The target is pi(q) ~ 1_box SSq^-shape; std2 completes it."""
+
+    def __init__(self, q, l, accepted, outbox, stuck, n_iter, trace_q, trace_l, iterations, island_size, shape, seed, offset, logmask, a):
+        self.q, self.l, self.accepted, self.outbox, self.stuck = q, l, accepted, outbox, stuck
+        self.n_iter, self.trace_q, self.trace_l, self.iterations = int(n_iter), trace_q, trace_l, iterations
+        self.island_size, self.shape, self.seed, self.offset, self.logmask, self.a = int(island_size), float(shape), int(seed), int(offset), int(logmask), float(a)
+
+    @property
+    def n_islands(self):
+        return self.q.shape[0] // self.island_size
+
+    @property
+    def accept_rate(self):
+        """accepted proposals / iterations, over all walkers"""
+        return float(self.accepted.sum()) / (self.n_iter * self.accepted.shape[0])
+
+    @property
+    def outbox_rate(self):
+        """proposals outside the box / iterations, over all walkers"""
+        return float(self.outbox.sum()) / (self.n_iter * self.outbox.shape[0])
+
+    def std2(self, seed=None, engine=None, kept=False):
+        """sigma^2 | q ~ InvGamma(shape, SSq / 2) by Engine.smc_std2 of the final states' l → (n,), or with kept=True of the kept
+        states → (n_keep, n), row r with the gamma variates of Philox iteration iterations[r].  seed: by default the run's;
+        engine: by default a host-memory Engine made for the call."""
+        seed = self.seed if seed is None else int(seed)
+        rows = self.trace_l if kept else self.l[None]
+        its = self.iterations if kept else [self.n_iter]
+        with contextlib.nullcontext(engine) if engine is not None else Engine(mem="host") as eng:
+            out = [_host(eng.smc_std2(r, self.shape, seed, self.offset, int(t))) for r, t in zip(rows, its)]
+        return np.stack(out) if kept else out[0]
+
+
 class Engine:
     def __init__(self, lib=None, mem="host", device=-1, block_threads=0, cpu_threads=0, stream=None, checker=False):
         if lib is None:
@@ -1676,6 +1723,225 @@ class Engine:
             if it > n_iter - keep:
                 kept.append((_host(q).copy()[None], _host(ssq).copy()[None]))
         return self._mala_result(np.arange(n), q, ssq, grad, jtj, counters, n_iter, kept, keep, thin, shape, seed, offset)
+
+    # -- the affine-invariant stretch move in island ensembles (include/rsf_ensemble.h) ------------------------------
+    @property
+    def island_size(self):
+        """walkers per island of the ensemble sampler: twice the workgroup's threads"""
+        return 2 * self.block_threads
+
+    @staticmethod
+    def _ens_mask(log_coords, d):
+        """log_coords: None (no parameter), an int bit mask, or d truth values → the bit mask (bit p: parameter p moves as log q_p)"""
+        if log_coords is None:
+            return 0
+        if isinstance(log_coords, (int, np.integer)) and not isinstance(log_coords, (bool, np.bool_)):
+            mask = int(log_coords)
+        else:
+            flags = np.atleast_1d(np.asarray(log_coords)).astype(bool)
+            if flags.shape != (d,):
+                raise ValueError(f"log_coords holds {flags.size} flags for d = {d} parameters")
+            mask = sum(1 << p for p in range(d) if flags[p])
+        if mask < 0 or mask >> d:
+            raise ValueError(f"log_coords has a bit at or beyond d = {d}")
+        return mask
+
+    def _ens_args(self, q0, lo, hi, dims, n_iter, a, log_coords, shape, seed, offset, iters_per_launch, keep, thin):
+        """The checks Engine.ensemble and ensemble_from_ssq share, made before any library call → (q0 (n, d) a fresh host array, lo,
+        hi, d, n_iter, a, logmask, shape, seed, offset, iters_per_launch, keep, thin)"""
+        q0 = _host(q0).copy()
+        if q0.ndim == 1:
+            q0 = q0.reshape(-1, 1)
+        if q0.ndim != 2 or q0.shape[0] < 1 or q0.shape[1] not in dims:
+            raise ValueError(f"q0 has shape {q0.shape}: (n,) or (n, d) walkers, d one of {dims}")
+        n, d = int(q0.shape[0]), int(q0.shape[1])
+        if n % self.island_size:
+            raise ValueError(f"{n} walkers are not whole islands of {self.island_size} (twice this engine's workgroup size)")
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo < hi).all()):
+            raise ValueError("the box needs finite lo < hi in every parameter")
+        mask = self._ens_mask(log_coords, d)
+        if any((mask >> p) & 1 and lo[p] < 0.0 for p in range(d)):
+            raise ValueError("a parameter that moves in log coordinates needs lo >= 0")
+        if not ((q0 > lo).all() and (q0 < hi).all()):
+            raise ValueError("stuck start: every walker starts strictly inside the box")
+        n_iter, a, ipl, thin = int(n_iter), float(a), int(iters_per_launch), int(thin)
+        keep = n_iter if keep is None else int(keep)
+        if not (math.isfinite(a) and a > 1.0):
+            raise ValueError("a is finite and > 1")
+        if shape is not None and not (math.isfinite(float(shape)) and float(shape) > 0.0):
+            raise ValueError("shape is finite and > 0")
+        if not (n_iter >= 1 and 1 <= ipl <= _abi.ENSEMBLE_MAX_ITER and 0 <= keep <= n_iter and thin >= 1 and int(seed) >= 0 and int(offset) >= 0):
+            raise ValueError(f"n_iter >= 1, iters_per_launch in [1, {_abi.ENSEMBLE_MAX_ITER}], 0 <= keep <= n_iter, thin >= 1, seed >= 0, offset >= 0")
+        return q0, lo, hi, d, n_iter, a, mask, None if shape is None else float(shape), int(seed), int(offset), ipl, keep, thin
+
+    def _ens_state(self, q, l, accepted=None, outbox=None, stuck=None):
+        """The check of a walker state handed to the low-level calls, which read and write it through raw addresses: q (n, d) and
+        l (n,) float64 and the counters (n,) int32, each a C-contiguous array of this engine's memory space → (n, d)"""
+        if getattr(q, "ndim", 0) != 2:
+            raise ValueError("q is (n, d)")
+        n, d = int(q.shape[0]), int(q.shape[1])
+        t = self._torch
+        for what, x, shape, dt in (("q", q, (n, d), "float64"), ("l", l, (n,), "float64"), ("accepted", accepted, (n,), "int32"),
+                                   ("outbox", outbox, (n,), "int32"), ("stuck", stuck, (n,), "int32")):
+            if x is None and dt == "int32":
+                continue
+            if self.mem == "device":
+                good = isinstance(x, t.Tensor) and x.is_cuda and x.is_contiguous() and str(x.dtype) == "torch." + dt
+            else:
+                good = isinstance(x, np.ndarray) and x.flags["C_CONTIGUOUS"] and x.dtype == np.dtype(dt)
+            if not good or tuple(x.shape) != shape:
+                raise ValueError(f"{what} must be a C-contiguous {dt} array of shape {shape} in this engine's memory space ({self.mem})")
+        return n, d
+
+    def ensemble_run(self, q, l, data, lo, hi, n_iter, accepted, outbox, stuck, a=2.0, log_coords=None, shape=None, seed=0, offset=0, iter0=1,
+                     trace=False):
+        """rsf_ensemble_run, the fused hot path: n_iter iterations (two half-steps each) IN PLACE in q (n, d), l (n,) and the int32
+        counters accepted, outbox and stuck, contiguous arrays of this engine's memory space; n is a whole number of islands
+        (island_size walkers each), iteration k uses the draws of Philox iteration iter0 + k of particle offset + j.  data (nout,)
+        or (G, nout), the walkers split evenly over the series in whole islands.  trace=True → (trace_q (n_iter, n, d), trace_l
+        (n_iter, n)), the state after each iteration."""
+        self._need_model()
+        n, d = self._ens_state(q, l, accepted, outbox, stuck)
+        data = self._in(data)
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        tq, tl = (self._empty((int(n_iter), n, d)), self._empty((int(n_iter), n))) if trace else (None, None)
+        _abi.check(self.lib, self.lib.rsf_ensemble_run(self._ctx, n, d, self._ptr(q), self._ptr(l), self._ptr(data), G, _dp(_vec(lo, d, "lo")),
+                                                       _dp(_vec(hi, d, "hi")), float(a), self._ens_mask(log_coords, d),
+                                                       float(0.5 * self.nout if shape is None else shape), int(seed), int(offset), int(iter0),
+                                                       int(n_iter), self._ptr(accepted), self._ptr(outbox), self._ptr(stuck), self._ptr(tq),
+                                                       self._ptr(tl)))
+        return (tq, tl) if trace else None
+
+    def ensemble_propose(self, q, l, lo, hi, half, a=2.0, log_coords=None, seed=0, offset=0, iteration=1):
+        """rsf_ensemble_propose: the proposals of the walkers of half `half` (0 or 1) of every island in one half-step → (q_new
+        (n, d), inbox (n,) uint8, logz_jac (n,)).  inbox is 0 for a proposal outside the box and for a stuck walker, whose q_new
+        row is its q; the rows of the other half hold q, 0 and 0."""
+        n, d = self._ens_state(q, l)
+        qn = q.clone() if hasattr(q, "clone") else q.copy()
+        inb, lj = self._bytes(np.zeros(n, dtype=np.uint8)), self._in(np.zeros(n))
+        _abi.check(self.lib, self.lib.rsf_ensemble_propose(self._ctx, n, d, self._ptr(q), self._ptr(l), _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")),
+                                                           float(a), self._ens_mask(log_coords, d), int(seed), int(offset), int(iteration), int(half),
+                                                           self._ptr(qn), self._ptr(inb), self._ptr(lj)))
+        return qn, inb, lj
+
+    def ensemble_ssq(self, q_new, inbox, data, half, ssq_new=None):
+        """rsf_ensemble_ssq: the solve of one half-step alone → ssq_new (n,), SSq of the device model at ensemble_propose's q_new
+        (n, d) for the walkers of half `half` whose inbox is 1, in ensemble_run's own arrangement — the one source of SSq with
+        which propose / accept reproduce ensemble_run bit for bit.  The other entries are ssq_new's (by default 1)."""
+        self._need_model()
+        q_new, inbox, data = self._in(q_new), self._bytes(inbox), self._in(data)
+        if q_new.ndim != 2 or tuple(inbox.shape) != (int(q_new.shape[0]),):
+            raise ValueError("q_new is (n, d), inbox (n,)")
+        n, d = int(q_new.shape[0]), int(q_new.shape[1])
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        out = self._in(np.ones(n) if ssq_new is None else ssq_new)
+        out = out.clone() if hasattr(out, "clone") else out.copy()
+        _abi.check(self.lib, self.lib.rsf_ensemble_ssq(self._ctx, n, d, self._ptr(q_new), self._ptr(inbox), self._ptr(data), G, int(half), self._ptr(out)))
+        return out
+
+    def ensemble_accept(self, q, l, lo, hi, half, q_new, inbox, logz_jac, ssq_new, accepted, outbox, stuck, shape, seed=0, offset=0, iteration=1):
+        """rsf_ensemble_accept: the decision of one half-step with the caller's sums of squares ssq_new (n,), read where inbox is 1,
+        at ensemble_propose's q_new, IN PLACE in q, l and the int32 counters (contiguous arrays of this engine's memory space);
+        only the rows of half `half` of every island are touched."""
+        n, d = self._ens_state(q, l, accepted, outbox, stuck)
+        q_new, inbox, logz_jac, ssq_new = self._in(q_new), self._bytes(inbox), self._in(logz_jac), self._in(ssq_new)
+        if (tuple(q_new.shape), tuple(inbox.shape), tuple(logz_jac.shape), tuple(ssq_new.shape)) != ((n, d), (n,), (n,), (n,)):
+            raise ValueError(f"q_new is ({n}, {d}), inbox, logz_jac and ssq_new ({n},)")
+        _abi.check(self.lib, self.lib.rsf_ensemble_accept(self._ctx, n, d, self._ptr(q), self._ptr(l), _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")),
+                                                          float(shape), int(seed), int(offset), int(iteration), int(half), self._ptr(q_new),
+                                                          self._ptr(inbox), self._ptr(logz_jac), self._ptr(ssq_new), self._ptr(accepted),
+                                                          self._ptr(outbox), self._ptr(stuck)))
+
+    def _ens_result(self, q, l, counters, n_iter, kept, keep, thin, shape, seed, offset, mask, a):
+        n, d = int(q.shape[0]), int(q.shape[1])
+        tq = np.concatenate([_host(x) for x, _ in kept]) if kept else np.empty((0, n, d))
+        tl = np.concatenate([_host(x) for _, x in kept]) if kept else np.empty((0, n))
+        rows = np.arange(n_iter - keep, n_iter)[::thin]
+        pick = rows - (n_iter - tq.shape[0])  # the kept launches end at the last iteration
+        return EnsembleResult(_host(q), _host(l), *(self._ints_host(c).astype(np.int32) for c in counters), n_iter,
+                              np.ascontiguousarray(tq[pick]), np.ascontiguousarray(tl[pick]), rows + 1, self.island_size, shape, seed, offset, mask, a)
+
+    @staticmethod
+    def _ens_refuse_stuck(l):
+        bad = ~np.isfinite(l)
+        if bad.any():
+            raise ValueError(f"stuck start: {int(bad.sum())} walkers have no finite target value (first: walker {int(np.flatnonzero(bad)[0])})")
+
+    def ensemble(self, q0, data, lo, hi, n_iter, a=2.0, log_coords=None, shape=None, seed=0, offset=0, iters_per_launch=16, keep=None, thin=1):
+        """The affine-invariant ensemble sampler (the stretch move of Goodman & Weare 2010) of the device model (set_model) against
+        `data` over the strict box (lo, hi), target pi(q) ~ SSq(q)^-shape (shape: by default nout / 2): q0 (n,) or (n, d) walkers
+        inside the box, d = 1 (Dc) or 3 (Dc, a, b), n a whole number of ISLANDS of island_size = 2 x the workgroup size walkers —
+        independent ensembles, one per workgroup, whose walkers take their proposals from each other: no proposal covariance, no
+        gradient, one forward solve per proposal, stretch scale a > 1 the only constant.  log_coords: d truth values (or a bit
+        mask); a marked parameter moves as log q_p, which needs lo_p >= 0 (in (log Dc, log a, b) the ridge Dc a = const is a
+        straight line).  data (nout,), or (G, nout) with the walkers split evenly over the G series in order, whole islands each.
+        The start's l comes from evidence_logtarget; a walker outside the box or without a finite l is refused (ValueError).
+        n_iter iterations on the GPU (rsf_ensemble_run, iters_per_launch per launch).  keep: the trailing iterations whose states
+        are kept (None: all), every thin-th of them → EnsembleResult."""
+        self._need_model()
+        q0, lo, hi, d, n_iter, a, mask, shape, seed, offset, ipl, keep, thin = self._ens_args(
+            q0, lo, hi, (1, 3), n_iter, a, log_coords, shape, seed, offset, iters_per_launch, keep, thin)
+        shape = 0.5 * self.nout if shape is None else shape
+        obs = _host(data)
+        obs = obs.reshape(1, -1) if obs.ndim == 1 else obs
+        if obs.ndim != 2 or obs.shape[1] != self.nout:
+            raise ValueError(f"data has shape {obs.shape}: (nout,) or (G, nout), the model produces nout = {self.nout} samples")
+        n, G = q0.shape[0], obs.shape[0]
+        if n % (G * self.island_size):
+            raise ValueError(f"{n} walkers cannot be split over {G} observation series in whole islands of {self.island_size}")
+        per = n // G
+        q = self._in(q0)
+        l0 = np.concatenate([_host(self.evidence_logtarget(q[g * per:(g + 1) * per], obs[g], lo, hi, np.zeros(per), shape)) for g in range(G)])
+        self._ens_refuse_stuck(l0)
+        l, obs = self._in(l0), self._in(obs)
+        counters = [self._ints(np.zeros(n)) for _ in range(3)]
+        kept, done = [], 0
+        while done < n_iter:
+            k = min(ipl, n_iter - done)
+            tr = self.ensemble_run(q, l, obs, lo, hi, k, *counters, a=a, log_coords=mask, shape=shape, seed=seed, offset=offset, iter0=done + 1,
+                                   trace=done + k > n_iter - keep)
+            if tr is not None:
+                kept.append(tr)
+            done += k
+        return self._ens_result(q, l, counters, n_iter, kept, keep, thin, shape, seed, offset, mask, a)
+
+    def ensemble_from_ssq(self, ssq_fn, q0, lo, hi, n_iter, shape, a=2.0, log_coords=None, seed=0, offset=0, keep=None, thin=1):
+        """ensemble with the caller's sum of squares: ssq_fn(points (m, d) float64 on the host) → SSq (m,), called for the start
+        and, twice per iteration, for the proposals of one half that lie inside the box.  d = 1..3, no model needed; shape has no
+        default.  The start's l is -shape log SSq on the host; the proposals and the decisions are the GPU's
+        (rsf_ensemble_propose, rsf_ensemble_accept).  → EnsembleResult."""
+        if shape is None:
+            raise ValueError("shape is finite and > 0")
+        q0, lo, hi, d, n_iter, a, mask, shape, seed, offset, _, keep, thin = self._ens_args(
+            q0, lo, hi, (1, 2, 3), n_iter, a, log_coords, shape, seed, offset, 1, keep, thin)
+        n = q0.shape[0]
+
+        def ssq_at(pts):
+            s = np.asarray(ssq_fn(pts), dtype=np.float64).reshape(-1)
+            if s.size != pts.shape[0]:
+                raise ValueError(f"ssq_fn returned {s.size} values for {pts.shape[0]} points")
+            return s
+
+        s0 = ssq_at(q0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            l0 = np.where(np.isfinite(s0) & (s0 > 0), -shape * np.log(s0), -np.inf)
+        self._ens_refuse_stuck(l0)
+        q, l = self._in(q0), self._in(l0)
+        counters = [self._ints(np.zeros(n)) for _ in range(3)]
+        kept = []
+        for it in range(1, n_iter + 1):
+            for half in (0, 1):
+                kw = dict(seed=seed, offset=offset, iteration=it)
+                qn, inb, lj = self.ensemble_propose(q, l, lo, hi, half, a=a, log_coords=mask, **kw)
+                inside = np.asarray(inb.cpu() if hasattr(inb, "cpu") else inb).astype(bool)
+                s_n = np.ones(n)
+                if inside.any():
+                    s_n[inside] = ssq_at(_host(qn)[inside])
+                self.ensemble_accept(q, l, lo, hi, half, qn, inb, lj, s_n, *counters, shape=shape, **kw)
+            if it > n_iter - keep:
+                kept.append((_host(q).copy()[None], _host(l).copy()[None]))
+        return self._ens_result(q, l, counters, n_iter, kept, keep, thin, shape, seed, offset, mask, a)
 
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
