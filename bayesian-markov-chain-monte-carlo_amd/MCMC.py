@@ -665,6 +665,29 @@ class MCMC:
             eng.sync()
         return self._ensemble_pool(res, std2, nburn, extra)
 
+    def quadrature(self, n=None, n_draws=0, seed=0, coords=None, window_sd=12.0, mem="device", device=-1):
+        """The exact posterior by quadrature on the GPU (additive; Engine.grid_posterior): the n0 = 0 target
+        pi(q) ~ 1_box SSq^-N/2 tabulated on a tensor grid over the prior box — d = 1: n = (4001,) Simpson nodes of Dc; d = 3:
+        n = (2001, 65, 65) nodes of (Dc a, a, b), the product an axis so that the ridge Dc a = const is resolved.  Returns a
+        GridPosterior: log_evidence, mean, cov, std2_mean, marginal(name), quantiles(name, probs) carry no Monte Carlo error;
+        draw(n) gives independent draws and pool(n) a PosteriorPool of them on which predictive, loo, joint, corner and the
+        diagnostics work unchanged.  n_draws > 0: that many draws are taken at once and kept as .q and .std2.  The result holds
+        its engine (result.engine.close() releases it)."""
+        if not self._device_model():
+            raise TypeError("quadrature integrates the model on the device: `model` must be this package's RateStateModel")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
+        eng = Engine(mem=mem, device=device)
+        try:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            res = eng.grid_posterior(data, lo, hi, n=n, coords=coords, window_sd=window_sd)
+            res.q, res.std2 = res.draw(int(n_draws), seed) if int(n_draws) > 0 else (None, None)
+            eng.sync()
+        except BaseException:
+            eng.close()
+            raise
+        return res
+
     def _fit_starts(self, eng, n_starts, seed):
         """start 0 is qstart, the others rsf_smc_init's uniform start in the prior box (seed, particles 0 .. n_starts - 2)"""
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]

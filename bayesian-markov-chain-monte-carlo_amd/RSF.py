@@ -207,6 +207,31 @@ class RSF:
             out[float(dc)] = MCMC._mala_pool(part, std2[:, s], nburn)
         return out
 
+    def inference_grid(self, n=None, n_draws=0, seed=0, coords=None, window_sd=12.0, mem="device", device=-1):
+        """Additive: the exact posterior of every true Dc of dc_list by quadrature on the GPU (MCMC.quadrature, one grid per
+        observation group).  Returns {dc: GridPosterior}; with n_draws > 0 each carries that many independent draws (.q, .std2),
+        group g from the Philox stream (seed, g * n_draws + j).  ALL the results hold ONE engine, self.grid_engine: draw, pool and
+        marginal('Dc') of every one of them need it open, so close it (self.grid_engine.close(), the same object as any
+        result's .engine) only when done with all of them.  An error closes it.  The `inference` path is not touched."""
+        nt, G = self.model.num_tsteps, len(self.dc_list)
+        data = np.ascontiguousarray(np.asarray(self.data, dtype=np.float64).reshape(G, nt))
+        probe = MCMC(self.model, data[0], self.dc_list[0], self.qpriors, self.qstart, nsamples=10)
+        lo, hi = probe.qstart_limits[:, 0], probe.qstart_limits[:, 1]
+        out = {}
+        eng = Engine(mem=mem, device=device)
+        try:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            for g, dc in enumerate(self.dc_list):
+                res = eng.grid_posterior(data[g], lo, hi, n=n, coords=coords, window_sd=window_sd)
+                res.q, res.std2 = res.draw(int(n_draws), seed, g * int(n_draws)) if int(n_draws) > 0 else (None, None)
+                out[float(dc)] = res
+            eng.sync()
+        except BaseException:
+            eng.close()
+            raise
+        self.grid_engine, self.grid_result = eng, out
+        return out
+
     def inference_ensemble(self, n_walkers=512, n_iter=200, nburn=None, start="fit", log_coords=None, a=2.0, seed=0, mem="device", device=-1, thin=1):
         """Additive: the posterior of every true Dc of dc_list by the affine-invariant ensemble sampler in ONE call
         (Engine.ensemble) — each is an observation group of n_walkers walkers (rounded up to whole islands), started in a ball

@@ -286,6 +286,21 @@ ENSEMBLE_PROTOTYPES = {
 }
 ENSEMBLE_MAX_PARAMS = 3  # RSF_ENSEMBLE_MAX_PARAMS
 ENSEMBLE_MAX_ITER = 64   # RSF_ENSEMBLE_MAX_ITER: iterations per rsf_ensemble_run call
+# include/rsf_grid.h: the exact posterior on a tensor quadrature grid; exported by librsf_hip.so only, bound by load()
+GRID_PROTOTYPES = {
+    "rsf_grid_logtarget": (c_int, [c_void_p, c_int32, _I32P, _DP, _P, c_double, _DP, _DP, c_int32, _P, _P]),
+    "rsf_grid_columns": (c_int, [c_void_p, c_int32, _I32P, _DP, _DP, _P, _P, c_double, _DP, _P, _P, _P]),
+    "rsf_grid_finish": (c_int, [c_int32, _I32P, _DP, _DP, c_int32, c_double, c_double, _DP, _DP, c_double, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "rsf_grid_draw": (c_int, [c_void_p, c_int32, _I32P, _DP, c_int32, _P, _DP, _DP, c_uint64, c_int64, c_int64, _P, _P]),
+    "rsf_grid_cdf": (c_int, [c_void_p, c_int32, _I32P, _DP, c_int32, _P, _DP, c_int64, _DP, _DP]),
+}
+GRID_MAX_PARAMS = 3  # RSF_GRID_MAX_PARAMS
+GRID_PLAIN, GRID_PRODUCT = 0, 1  # RSF_GRID_PLAIN, RSF_GRID_PRODUCT
+GRID_COORDS = {"plain": GRID_PLAIN, "product": GRID_PRODUCT}
+# the fields of a column (RSF_GRID_FIELDS) and rsf_grid_finish's head (RSF_GRID_HEAD entries: mean is 3, cov 3 x 3), in index order
+GRID_FIELDS = ("s0", "s1", "s2", "ssq", "ssq2", "n_neginf")
+GRID_HEAD = 20
+GRID_HEAD_SCALARS = {"Z": 0, "log_integral": 1, "log_evidence": 2, "n_neginf": 3, "x0_mean": 16, "x0_var": 17, "std2_mean": 18, "std2_var": 19}
 MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
 
 
@@ -333,7 +348,7 @@ def load():
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
-                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES):
+                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

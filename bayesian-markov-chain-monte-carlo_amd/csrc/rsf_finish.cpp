@@ -1,6 +1,7 @@
 // rsf_finish.cpp — the host arithmetic that turns the device partials into the reported statistics: rsf_diag_finish,
 // rsf_diag_rank_finish, rsf_predict_finish, rsf_predict_psis_finish, rsf_pool_joint_finish, rsf_pool_hpd_levels, rsf_evidence_finish,
-// rsf_smc_section, rsf_smc_increment, rsf_smc_log_evidence, rsf_fit_laplace.  No ctx, no GPU:
+// rsf_smc_section, rsf_smc_increment, rsf_smc_log_evidence, rsf_fit_laplace, rsf_grid_finish (and rsfh::grid_check, the grid's
+// argument check, which rsf_grid.hip shares).  No ctx, no GPU:
 // plain C++, the public headers and the standard library only.
 #include <cmath>
 #include <cstdint>
@@ -11,15 +12,36 @@
 #include "../../include/rsf_diag.h"
 #include "../../include/rsf_evidence.h"
 #include "../../include/rsf_fit.h"
+#include "../../include/rsf_grid.h"
 #include "../../include/rsf_joint.h"
 #include "../../include/rsf_predict.h"
 #include "../../include/rsf_psis.h"
 #include "../../include/rsf_smc.h"
 
 #pragma GCC visibility push(hidden)
-namespace rsfh { int fail(int code, const char *fmt, ...); }  // rsf_hip.hip: formats rsf_last_error()'s message, returns code
+namespace rsfh {
+int fail(int code, const char *fmt, ...);  // rsf_hip.hip: formats rsf_last_error()'s message, returns code
+int grid_check(const char *fn, int d, int dmin, const int32_t *n, const double *x, const double *w, int64_t *N);  // declared in rsf_host.h
+}
 #pragma GCC visibility pop
 using rsfh::fail;
+
+int rsfh::grid_check(const char *fn, int d, int dmin, const int32_t *n, const double *x, const double *w, int64_t *N) {
+  if (d < dmin || d > RSF_GRID_MAX_PARAMS) return fail(RSF_ERR_INVALID, "%s: need %d <= d <= %d", fn, dmin, RSF_GRID_MAX_PARAMS);
+  int64_t total = 1, at = 0;
+  for (int p = 0; p < d; ++p) {
+    if (n[p] < 2) return fail(RSF_ERR_INVALID, "%s: axis %d has %d nodes, fewer than 2", fn, p, (int)n[p]);
+    total *= n[p];
+    if (total >= (int64_t)1 << 31) return fail(RSF_ERR_INVALID, "%s: the grid has 2^31 nodes or more", fn);
+    for (int k = 0; k < n[p]; ++k, ++at) {
+      if (!std::isfinite(x[at]) || (k > 0 && !(x[at] > x[at - 1])))
+        return fail(RSF_ERR_INVALID, "%s: the nodes of axis %d are not finite and strictly increasing (node %d)", fn, p, k);
+      if (w && (!std::isfinite(w[at]) || !(w[at] > 0.0))) return fail(RSF_ERR_INVALID, "%s: weight %d of axis %d is not finite and > 0", fn, k, p);
+    }
+  }
+  *N = total;
+  return RSF_OK;
+}
 
 extern "C" {
 
@@ -326,6 +348,117 @@ int rsf_fit_laplace(int32_t d, int64_t n_obs, double shape, double ssq, const do
   const double logi = -shape * std::log(ssq) + 0.5 * d * std::log(two_pi) - 0.5 * (logdet + d * std::log(2.0 * shape / ssq));
   out[d * d] = logi;
   return rsf_smc_log_evidence(logi, shape, d, lo, hi, out + d * d + 1);
+}
+
+// the trapezoid CDF of the node density m[k] / w[k] on the nodes x[n], the cells added in node order, divided by its last entry; all 0
+// where there is no mass
+static void grid_cum(int n, const double *x, const double *w, const double *m, int64_t stride, double *F) {
+  double acc = 0.0;
+  F[0] = 0.0;
+  for (int k = 1; k < n; ++k) {
+    acc += 0.5 * (m[(k - 1) * stride] / w[k - 1] + m[k * stride] / w[k]) * (x[k] - x[k - 1]);
+    F[k] = acc;
+  }
+  if (acc > 0.0)
+    for (int k = 1; k < n; ++k) F[k] /= acc;
+}
+
+int rsf_grid_finish(int32_t d, const int32_t *n, const double *x, const double *w, int32_t coords, double center, double shape, const double *lo,
+                    const double *hi, double lmax, const double *fields, double *head, double *mass1, double *mass2, double *pair, double *cum1,
+                    double *cum2) {
+  if (!n || !x || !w || !lo || !hi || !fields || !head || !mass1 || !mass2 || !pair || !cum1 || !cum2)
+    return fail(RSF_ERR_INVALID, "rsf_grid_finish: NULL argument");
+  int64_t N;
+  if (int rc = rsfh::grid_check(__func__, d, 1, n, x, w, &N)) return rc;
+  if (coords != RSF_GRID_PLAIN && coords != RSF_GRID_PRODUCT) return fail(RSF_ERR_INVALID, "rsf_grid_finish: coords is neither RSF_GRID_PLAIN nor RSF_GRID_PRODUCT");
+  if (coords == RSF_GRID_PRODUCT && d != 3) return fail(RSF_ERR_INVALID, "rsf_grid_finish: RSF_GRID_PRODUCT needs d = 3");
+  if (!std::isfinite(shape) || !(shape > 0.0)) return fail(RSF_ERR_INVALID, "rsf_grid_finish: shape must be finite and > 0");
+  if (!std::isfinite(center) || std::isnan(lmax) || lmax == INFINITY) return fail(RSF_ERR_INVALID, "rsf_grid_finish: need a finite center and lmax finite or -inf");
+  double logvol = 0.0;
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "rsf_grid_finish: need finite lo[%d] < hi[%d]", p, p);
+    logvol += std::log(hi[p] - lo[p]);
+  }
+  if (coords == RSF_GRID_PRODUCT && !(lo[1] > 0.0)) return fail(RSF_ERR_INVALID, "rsf_grid_finish: RSF_GRID_PRODUCT needs lo[1] > 0");
+  // an axis the grid lacks: one node 0 of weight 1
+  const double one = 1.0, zero = 0.0;
+  const int n1 = d > 1 ? n[1] : 1, n2 = d > 2 ? n[2] : 1;
+  const double *x1 = d > 1 ? x + n[0] : &zero, *w1 = d > 1 ? w + n[0] : &one;
+  const double *x2 = d > 2 ? x + n[0] + n[1] : &zero, *w2 = d > 2 ? w + n[0] + n[1] : &one;
+  const int64_t ncol = (int64_t)n1 * n2;
+  double neginf = 0.0;
+  for (int64_t c = 0; c < ncol; ++c) neginf += fields[c * RSF_GRID_FIELDS + 5];
+  for (int f = 0; f < RSF_GRID_HEAD; ++f) head[f] = NAN;
+  head[3] = neginf;
+  auto nan_fill = [](double *p, int64_t m) { std::fill(p, p + m, NAN); };
+  double Z = 0.0;
+  if (lmax != -INFINITY)
+    for (int64_t c = 0; c < ncol; ++c) Z += (w1[c % n1] * w2[c / n1]) * fields[c * RSF_GRID_FIELDS];
+  if (!(Z > 0.0) || !std::isfinite(Z)) {  // no finite node (or sums that are not numbers): no posterior to report
+    head[1] = lmax == -INFINITY || Z == 0.0 ? -INFINITY : NAN;
+    nan_fill(mass1, n1); nan_fill(mass2, n2); nan_fill(pair, ncol); nan_fill(cum1, ncol); nan_fill(cum2, n2);
+    return RSF_OK;
+  }
+  head[0] = Z;
+  head[1] = lmax + std::log(Z);
+  head[2] = head[1] - logvol + std::lgamma(shape) - shape * std::log(3.14159265358979323846);
+  // masses of the columns and of the upper axes' nodes
+  std::fill(mass1, mass1 + n1, 0.0);
+  std::fill(mass2, mass2 + n2, 0.0);
+  double a1 = 0.0, m1 = 0.0, m2 = 0.0, sq = 0.0, sq2 = 0.0;
+  for (int64_t c = 0; c < ncol; ++c) {
+    const int i1 = (int)(c % n1), i2 = (int)(c / n1);
+    const double W = w1[i1] * w2[i2], *f = fields + c * RSF_GRID_FIELDS;
+    pair[c] = W * f[0] / Z;
+    mass1[i1] += pair[c];
+    mass2[i2] += pair[c];
+    a1 += W * f[1];
+    m1 += pair[c] * x1[i1];
+    m2 += pair[c] * x2[i2];
+    sq += W * f[3];
+    sq2 += W * f[4];
+  }
+  const double mx0 = center + a1 / Z;  // the mean of x0
+  // q0 - g summed per column: D1 = sum w0 e (q0 - g), D2 = sum w0 e (q0 - g)^2.  PLAIN: g = center.  PRODUCT: q0 = x0 / x1 and
+  // q0 - g = ((x0 - center) + (center - g x1)) / x1 with g = E x0 / E x1, close to the mean of Dc
+  const bool prod = coords == RSF_GRID_PRODUCT;
+  const double g = prod ? mx0 / m1 : center;
+  double d1 = 0.0, d2 = 0.0, c01 = 0.0, c02 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0, a2 = 0.0;
+  for (int64_t c = 0; c < ncol; ++c) {
+    const int i1 = (int)(c % n1), i2 = (int)(c / n1);
+    const double W = w1[i1] * w2[i2], *f = fields + c * RSF_GRID_FIELDS;
+    double D1 = f[1], D2 = f[2];
+    if (prod) {
+      const double e = center - g * x1[i1];
+      D1 = (f[1] + e * f[0]) / x1[i1];
+      D2 = (f[2] + 2.0 * e * f[1] + e * e * f[0]) / (x1[i1] * x1[i1]);
+    }
+    const double r1 = x1[i1] - m1, r2 = x2[i2] - m2;
+    d1 += W * D1;
+    d2 += W * D2;
+    a2 += W * f[2];
+    c01 += W * D1 * r1;
+    c02 += W * D1 * r2;
+    c11 += pair[c] * r1 * r1;
+    c12 += pair[c] * r1 * r2;
+    c22 += pair[c] * r2 * r2;
+  }
+  const double s0 = d1 / Z;  // E q0 - g
+  double *mean = head + 4, *cov = head + 7;
+  mean[0] = g + s0;
+  cov[0] = d2 / Z - s0 * s0;
+  if (d > 1) { mean[1] = m1; cov[1] = cov[3] = c01 / Z; cov[4] = c11; }
+  if (d > 2) { mean[2] = m2; cov[2] = cov[6] = c02 / Z; cov[5] = cov[7] = c12; cov[8] = c22; }
+  head[16] = mx0;
+  head[17] = a2 / Z - (a1 / Z) * (a1 / Z);
+  if (shape > 1.0) head[18] = 0.5 * (sq / Z) / (shape - 1.0);
+  if (shape > 2.0) head[19] = 0.25 * (sq2 / Z) / ((shape - 1.0) * (shape - 2.0)) - head[18] * head[18];
+  // the cumulative tables of the two upper axes
+  if (d > 1) for (int i2 = 0; i2 < n2; ++i2) grid_cum(n1, x1, w1, pair + (int64_t)i2 * n1, 1, cum1 + (int64_t)i2 * n1);
+  else cum1[0] = 0.0;
+  if (d > 2) grid_cum(n2, x2, w2, mass2, 1, cum2);
+  else cum2[0] = 0.0;
+  return RSF_OK;
 }
 
 }  // extern "C"

@@ -74,6 +74,10 @@ enum Slot : int {
   // out; q_new, inbox, ssq_new in), rsf_smc_std2 (l in, std2 in SLOT_SMC_L_OUT)
   SLOT_SMC_Q = SLOT_Z, SLOT_SMC_L = SLOT_U, SLOT_SMC_OBS = SLOT_G, SLOT_SMC_CUM = SLOT_G, SLOT_SMC_ANC = SLOT_TQ, SLOT_SMC_INBOX = SLOT_TQ,
   SLOT_SMC_Q_OUT = SLOT_TS, SLOT_SMC_L_OUT = SLOT_TA, SLOT_SMC_SSQ = SLOT_SSQ_NEW,
+  // rsf_grid_logtarget (the observation in; l, ssq out), rsf_grid_columns (l, ssq in; fields, m0, cum0 out), rsf_grid_draw (cum0 in;
+  // q, cell out), rsf_grid_cdf (cum0 in).  The axes and the other HOST tables of a grid call lie in the ctx's poolws workspace
+  SLOT_GRID_L = SLOT_TQ, SLOT_GRID_SSQ = SLOT_TS, SLOT_GRID_OBS = SLOT_G, SLOT_GRID_FIELDS = SLOT_Z, SLOT_GRID_M0 = SLOT_U, SLOT_GRID_CUM0 = SLOT_TA,
+  SLOT_GRID_Q = SLOT_Z, SLOT_GRID_CELL = SLOT_U,
   // rsf_pool_allgather[_all] / _allreduce_sum[_all] (the reduction is in place in SLOT_SEND)
   SLOT_SEND = SLOT_Z, SLOT_RECV = SLOT_U,
 };
@@ -223,6 +227,9 @@ int first_bad_prob(int n, const double *probs);
 // what rsf_destroy frees of the other units' state: the replay graph (rsf_sampler.hip), the communicator (rsf_comm.hip)
 void release_replay_graph(rsf_ctx *c);
 void release_comm(rsf_ctx *c);
+// the grid of an rsf_grid_* call (rsf_finish.cpp): d in [dmin, 3], n[p] >= 2, N = prod n[p] < 2^31, the nodes x finite and strictly
+// increasing per axis, the weights w (NULL: not checked) finite and > 0 → *N; fn: the entry point the messages name
+int grid_check(const char *fn, int d, int dmin, const int32_t *n, const double *x, const double *w, int64_t *N);
 
 // ---- kernel selection -----------------------------------------------------------------------------------------------
 // A runtime selector becomes a template argument: with<V0, V1, ...>(v, f) hands f the one of the listed values that equals

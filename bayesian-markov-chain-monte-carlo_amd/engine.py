@@ -359,6 +359,157 @@ class EnsembleResult:
         return np.stack(out) if kept else out[0]
 
 
+def _simpson_axis(lo, hi, n):
+    """n (odd) uniform nodes on [lo, hi] and their composite Simpson weights"""
+    x = np.linspace(lo, hi, n)
+    w = np.full(n, 2.0)
+    w[1::2] = 4.0
+    w[0] = w[-1] = 1.0
+    return x, w * ((hi - lo) / (n - 1) / 3.0)
+
+
+def _node_cdf(x, f):
+    """The CDF at the nodes x of the node density f → (density, cdf), both normalised by the integral.  Uniform nodes (four or
+    more): a cell integrates the cubic through the four nearest nodes (fourth order, as the Simpson rule that weighs them); else
+    the trapezoid rule."""
+    h = np.diff(x)
+    if x.size >= 4 and np.allclose(h, h[0], rtol=1e-9, atol=0.0):
+        c = np.empty(x.size - 1)
+        c[1:-1] = (-f[:-3] + 13.0 * f[1:-2] + 13.0 * f[2:-1] - f[3:]) / 24.0
+        c[0] = (9.0 * f[0] + 19.0 * f[1] - 5.0 * f[2] + f[3]) / 24.0
+        c[-1] = (9.0 * f[-1] + 19.0 * f[-2] - 5.0 * f[-3] + f[-4]) / 24.0
+        c *= h[0]
+    else:
+        c = 0.5 * (f[:-1] + f[1:]) * h
+    F = np.maximum.accumulate(np.concatenate([[0.0], np.cumsum(c)]))
+    return f / F[-1], F / F[-1]
+
+
+def _invert_cdf(x, f, F, probs, sub=16):
+    """quantiles of the CDF F with the density f at the nodes x: the cubic Hermite interpolant of (F, f), tabulated on `sub` points
+    per cell and inverted linearly"""
+    t = (np.arange(sub) / sub)[None, :]
+    h, F0, F1, f0, f1 = np.diff(x)[:, None], F[:-1, None], F[1:, None], f[:-1, None], f[1:, None]
+    Fd = (2 * t ** 3 - 3 * t ** 2 + 1) * F0 + (t ** 3 - 2 * t ** 2 + t) * h * f0 + (3 * t ** 2 - 2 * t ** 3) * F1 + (t ** 3 - t ** 2) * h * f1
+    xd = np.concatenate([(x[:-1, None] + t * h).ravel(), x[-1:]])
+    Fd = np.maximum.accumulate(np.concatenate([Fd.ravel(), F[-1:]]))
+    return np.interp(np.asarray(probs, dtype=np.float64), Fd, xd)
+
+
+class GridPosterior:
+    """Result of Engine.grid_posterior / Engine.grid_from_ssq: the posterior pi(q) ~ 1_box SSq^-shape tabulated on a tensor grid —
+    no Monte Carlo error.  x, w: the axes' nodes and weights; coords: 0 plain, 1 product (axis 0 is Dc a).  log_integral = log of
+    the integral of SSq^-shape over the box, log_evidence with the constants of Engine.evidence_finish (comparable with
+    Engine.evidence's and Engine.smc's as it stands); mean (d,) and cov (d, d) of q; std2_mean, std2_var of sigma^2's marginal;
+    x0_mean, x0_var of axis 0 (Dc a in product coordinates); n_neginf nodes without density (outside the box, or a non-finite
+    SSq); outside: the coarse scan's mass beyond the fine window; n_solves forward solves spent; lmax, fields, m0, cum0 and
+    finish (pair, mass1, mass2, cum1, cum2): the tables.  It holds the engine that made it, which serves draw, marginal('Dc') in
+    product coordinates and pool."""
+
+    def __init__(self, engine, x, w, coords, lo, hi, shape, col, fin, ltarget, outside, n_solves):
+        self.engine, self.x, self.w, self.coords, self.lo, self.hi, self.shape = engine, x, w, coords, lo, hi, shape
+        self.d, self.n = len(x), tuple(a.size for a in x)
+        self.lmax, self.fields, self.m0, self.cum0, self.finish = col["lmax"], col["fields"], col["m0"], col["cum0"], fin
+        for k in ("Z", "log_integral", "log_evidence", "n_neginf", "mean", "cov", "x0_mean", "x0_var", "std2_mean", "std2_var"):
+            setattr(self, k, fin[k])
+        self._ltarget, self.outside, self.n_solves = ltarget, outside, n_solves
+        self.names = ("Dc",) if self.d == 1 else (("Dc", "a", "b", "Dc*a") if coords == _abi.GRID_PRODUCT else ("Dc", "a", "b")[:self.d])
+        self._dc = None
+
+    def marginal(self, name):
+        """→ (x, density, cdf) of 'Dc', 'a', 'b' or (product coordinates) 'Dc*a' on that quantity's nodes: the node density from the
+        node masses, the CDF its integral (fourth order on uniform nodes, else the trapezoid rule).  'Dc' in product coordinates:
+        on 4001 points over mean +- 12 SD inside the box, the CDF from dc_cdf (rsf_grid_cdf) and the density its slope."""
+        if name not in self.names:
+            raise ValueError(f"marginal is one of {self.names}")
+        axis = {"Dc": 0, "Dc*a": 0, "a": 1, "b": 2}[name]
+        if name == "Dc" and self.coords == _abi.GRID_PRODUCT:
+            if self._dc is None:
+                sd = math.sqrt(self.cov[0, 0])
+                xs = np.linspace(max(self.lo[0], self.mean[0] - 12.0 * sd), min(self.hi[0], self.mean[0] + 12.0 * sd), 4001)
+                F = self.dc_cdf(xs)
+                self._dc = (xs, np.gradient(F, xs), F)
+            return self._dc
+        x = self.x[axis]
+        f = self.m0 / self.Z if axis == 0 else self.finish[f"mass{axis}"] / self.w[axis]
+        return (x,) + _node_cdf(x, f)
+
+    def dc_cdf(self, xs, sub=4):
+        """Product coordinates: the CDF of Dc at the points xs by rsf_grid_cdf, F(x) = sum over the columns of mass(c) F0(x a | c).
+        As a function of a, F0(x a | a, b) is a step about as wide as the posterior of Dc a is narrow, which the nodes of the a axis
+        need not resolve (at 65 nodes Dc's upper credible limit was 0.32 Monte-Carlo SE of a 262 144-draw pool off)
+        although every column is resolved along Dc a and changes slowly with a.  So on a uniform a axis of four or more nodes the
+        sum is taken on that axis refined `sub` times (even): the columns' CDFs at fixed Dc a and the node density of the column masses
+        interpolated by the cubic through the four nearest a nodes (linear interpolation of the CDFs costs 0.1 SE on the closed form), Simpson weights on the
+        refined nodes, in slabs of axis-2 nodes whose sums add.  Other axes, and sub = 1: the grid as it is."""
+        eng, (x0, x1, x2), pair = self.engine, self.x, self.finish["pair"]
+        n0, n1, n2 = self.n
+        h = np.diff(x1)
+        if int(sub) < 2 or int(sub) % 2 or n1 < 4 or not np.allclose(h, h[0], rtol=1e-9, atol=0.0):
+            return eng.grid_cdf(self.x, self.cum0, pair, xs, self.coords)
+        sub = int(sub)
+        t = np.arange(sub) / sub
+        k = np.repeat(np.arange(n1 - 1), sub)                  # the cell of each refined node but the last, and its place in it
+        tt = np.tile(t, n1 - 1)
+        x1r, w1r = _simpson_axis(x1[0], x1[-1], (n1 - 1) * sub + 1)
+        # the node density of the masses along a: the cubic through the four nearest nodes (stencil s .. s + 3)
+        st = np.clip(k - 1, 0, n1 - 4)
+        tau = k - st + tt
+        g = pair / self.w[1][None, :]
+        lag = []
+        for j in range(4):
+            lj = np.ones_like(tau)
+            for m in range(4):
+                if m != j:
+                    lj *= (tau - m) / (j - m)
+            lag.append(lj)
+        gr = np.zeros((n2, k.size + 1))
+        for j in range(4):
+            gr[:, :-1] += lag[j][None, :] * g[:, st + j]
+        gr[:, -1] = g[:, -1]
+        pr = np.maximum(gr, 0.0) * w1r[None, :]
+        pr /= pr.sum()
+        C = _host(self.cum0).reshape(n2, n1, n0)
+        F = np.zeros(np.size(xs))
+        for rows in np.array_split(np.arange(n2), max(1, n2 // 5)):
+            c = C[rows]
+            cr = sum(lag[j][None, :, None] * c[:, st + j] for j in range(4))
+            # next to a column without mass (all 0): the cell's own two columns, or the one of them that has mass
+            lo_, hi_ = c[:, k], c[:, k + 1]
+            has_lo, has_hi = lo_[..., -1:] > 0, hi_[..., -1:] > 0
+            whole = np.all(np.stack([c[:, st + j][..., -1:] > 0 for j in range(4)]), axis=0)
+            lin = np.where(has_lo & has_hi, (1.0 - tt)[None, :, None] * lo_ + tt[None, :, None] * hi_, np.where(has_lo, lo_, hi_))
+            cr = np.where(whole, np.clip(cr, 0.0, 1.0), lin)
+            cr = np.concatenate([cr, c[:, -1:]], axis=1)
+            F += eng.grid_cdf([x0, x1r, x2[rows]], np.ascontiguousarray(cr), pr[rows], xs, self.coords)
+        return F
+
+    def quantiles(self, name, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
+        """the quantiles of marginal(name) at `probs`: the cubic Hermite interpolant of its CDF and density, inverted"""
+        return _invert_cdf(*self.marginal(name), probs)
+
+    def draw(self, n, seed=0, offset=0):
+        """n independent draws (Engine.grid_draw; shards with offsets form one stream), each completed with
+        sigma^2 | q ~ InvGamma(shape, SSq / 2) from one more evaluation of the target at the draws → (q (n, d), std2 (n,)) on the
+        host.  An effective sample size of n from n solves."""
+        q = self.engine.grid_draw(self.x, self.cum0, self.finish["cum1"], self.finish["cum2"], n, self.coords, seed, offset)
+        std2 = self.engine.smc_std2(self._ltarget(q), self.shape, seed, offset, 1)
+        return _host(q), _host(std2)
+
+    def pool(self, n, seed=0):
+        """n draws as a PosteriorPool, laid out as MCMC.sample_smc lays its particles out ((16, n / 16, d) when 16 divides n):
+        predictive, loo, joint, corner, diagnostics and rank_diagnostics work on it unchanged.  Its stats carry log_integral,
+        log_evidence, n_solves and shape."""
+        if __package__:
+            from .MCMC import PosteriorPool
+        else:
+            from MCMC import PosteriorPool
+        q, std2 = self.draw(n, seed)
+        rows = 16 if q.shape[0] % 16 == 0 else 1
+        stats = {"log_integral": self.log_integral, "log_evidence": self.log_evidence, "n_solves": self.n_solves + q.shape[0], "shape": self.shape}
+        return PosteriorPool(np.ascontiguousarray(q.reshape(-1, rows, self.d).transpose(1, 0, 2)), np.ascontiguousarray(std2.reshape(-1, rows).T), 1.0, stats, 0)
+
+
 class Engine:
     def __init__(self, lib=None, mem="host", device=-1, block_threads=0, cpu_threads=0, stream=None, checker=False):
         if lib is None:
@@ -1942,6 +2093,202 @@ class Engine:
             if it > n_iter - keep:
                 kept.append((_host(q).copy()[None], _host(l).copy()[None]))
         return self._ens_result(q, l, counters, n_iter, kept, keep, thin, shape, seed, offset, mask, a)
+
+    # -- the exact posterior on a tensor quadrature grid (include/rsf_grid.h) ------------------------------
+    @staticmethod
+    def _grid_axes(x, w=None):
+        """x (and w): one array (d = 1) or a sequence of d arrays → (d, n (d,) int32, the nodes' list, x and w concatenated)"""
+        xs = [np.ascontiguousarray(x, dtype=np.float64)] if np.ndim(x[0]) == 0 else [np.ascontiguousarray(a, dtype=np.float64) for a in x]
+        d = len(xs)
+        if not 1 <= d <= _abi.GRID_MAX_PARAMS or any(a.ndim != 1 for a in xs):
+            raise ValueError(f"a grid has 1 to {_abi.GRID_MAX_PARAMS} axes, each a 1-D array of nodes")
+        ws = None
+        if w is not None:
+            ws = [np.ascontiguousarray(w, dtype=np.float64)] if np.ndim(w[0]) == 0 else [np.ascontiguousarray(a, dtype=np.float64) for a in w]
+            if [a.shape for a in ws] != [a.shape for a in xs]:
+                raise ValueError("every axis has as many weights as nodes")
+        n = np.array([a.size for a in xs], dtype=np.int32)
+        return d, n, xs, np.concatenate(xs), None if ws is None else np.concatenate(ws)
+
+    @staticmethod
+    def _grid_coords(coords, d):
+        c = _abi.GRID_COORDS.get(coords, coords) if isinstance(coords, str) else (_abi.GRID_PLAIN if coords is None else coords)
+        if c not in (_abi.GRID_PLAIN, _abi.GRID_PRODUCT) or (c == _abi.GRID_PRODUCT and d != 3):
+            raise ValueError("coords is 'plain' or, with three axes, 'product'")
+        return int(c)
+
+    def grid_logtarget(self, x, data, lo, hi, coords=None, shape=None):
+        """rsf_grid_logtarget, the fused hot path: one float64 RK4 solve per node of the tensor grid with the axes x (d = 1 or 3),
+        the node formed on the device from its flat index i0 + n0 (i1 + n1 i2) → (l (N,), ssq (N,)) in this engine's memory space.
+        l = -shape log SSq (- log x1 with coords='product', where x0 = Dc a); -inf outside the CLOSED box [lo, hi] and where SSq is
+        not finite.  shape defaults to nout / 2."""
+        self._need_model()
+        d, n, _, xc, _ = self._grid_axes(x)
+        c = self._grid_coords(coords, d)
+        obs = self._in(data)
+        if obs.ndim != 1 or int(obs.shape[0]) != self.nout:
+            raise ValueError(f"data has shape {tuple(obs.shape)}, the model produces {self.nout} samples")
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
+        N = int(np.prod(n.astype(np.int64)))
+        l, ssq = self._empty((N,)), self._empty((N,))
+        _abi.check(self.lib, self.lib.rsf_grid_logtarget(self._ctx, d, _i32p(n), _dp(xc), self._ptr(obs), float(0.5 * self.nout if shape is None else shape),
+                                                         _dp(lo), _dp(hi), c, self._ptr(l), self._ptr(ssq)))
+        return l, ssq
+
+    def grid_columns(self, x, w, l, ssq, center=None, m0=True, cum0=True):
+        """rsf_grid_columns: the fixed-order reductions of any l, ssq (N,) on the grid (x, w) → dict(lmax, center, fields
+        (ncol, len(GRID_FIELDS)) and m0 (n0,) on the host, cum0 (ncol, n0) in this engine's memory space).  center: by default
+        the middle node of axis 0."""
+        d, n, xs, xc, wc = self._grid_axes(x, w)
+        N, n0 = int(np.prod(n.astype(np.int64))), int(n[0])
+        l, ssq = self._in(l), self._in(ssq)
+        if math.prod(l.shape) != N or math.prod(ssq.shape) != N:
+            raise ValueError(f"l and ssq hold one value per node: {N}")
+        center = float(xs[0][n0 // 2]) if center is None else float(center)
+        fields, vm0, vc0 = self._empty((N // n0, len(_abi.GRID_FIELDS))), self._empty((n0,)) if m0 else None, self._empty((N // n0, n0)) if cum0 else None
+        lmax = ctypes.c_double()
+        _abi.check(self.lib, self.lib.rsf_grid_columns(self._ctx, d, _i32p(n), _dp(xc), _dp(wc), self._ptr(l), self._ptr(ssq), center, ctypes.byref(lmax),
+                                                       self._ptr(fields), self._ptr(vm0), self._ptr(vc0)))
+        return {"lmax": lmax.value, "center": center, "fields": _host(fields), "m0": None if vm0 is None else _host(vm0), "cum0": vc0}
+
+    def grid_finish(self, x, w, lo, hi, shape, lmax, fields, center, coords=None):
+        """rsf_grid_finish (host only): the column fields taken at (center, lmax) → dict(Z, log_integral, log_evidence, n_neginf,
+        mean (d,), cov (d, d), x0_mean, x0_var, std2_mean, std2_var, mass1 (n1,), mass2 (n2,), pair (n2, n1), cum1 (n2, n1),
+        cum2 (n2,)).  A grid without a finite node: log_integral -inf, the rest NaN."""
+        d, n, _, xc, wc = self._grid_axes(x, w)
+        c = self._grid_coords(coords, d)
+        n1, n2 = (int(n[1]) if d > 1 else 1), (int(n[2]) if d > 2 else 1)
+        f = _host(fields).reshape(-1)
+        if f.size != n1 * n2 * len(_abi.GRID_FIELDS):
+            raise ValueError(f"fields is ({n1 * n2}, {len(_abi.GRID_FIELDS)})")
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
+        head, mass1, mass2 = np.empty(_abi.GRID_HEAD), np.empty(n1), np.empty(n2)
+        pair, cum1, cum2 = np.empty((n2, n1)), np.empty((n2, n1)), np.empty(n2)
+        _abi.check(self.lib, self.lib.rsf_grid_finish(d, _i32p(n), _dp(xc), _dp(wc), c, float(center), float(shape), _dp(lo), _dp(hi), float(lmax), _dp(f),
+                                                      _dp(head), _dp(mass1), _dp(mass2), _dp(pair), _dp(cum1), _dp(cum2)))
+        out = {k: float(head[i]) for k, i in _abi.GRID_HEAD_SCALARS.items()}
+        out["n_neginf"] = int(head[3])
+        out.update(mean=head[4:4 + d].copy(), cov=head[7:16].reshape(3, 3)[:d, :d].copy(), mass1=mass1, mass2=mass2, pair=pair, cum1=cum1, cum2=cum2)
+        return out
+
+    def grid_draw(self, x, cum0, cum1, cum2, n, coords=None, seed=0, offset=0, cells=False):
+        """rsf_grid_draw: n independent draws by inverting the cumulative tables with the uniforms of smc_init's stream
+        (seed, offset + j) → q (n, d) in this engine's memory space; with cells=True also the cell of each axis, (n, d) int32 on
+        the host."""
+        d, nn, _, xc, _ = self._grid_axes(x)
+        c = self._grid_coords(coords, d)
+        n = int(n)
+        cum0 = self._in(cum0)
+        if math.prod(cum0.shape) != int(np.prod(nn.astype(np.int64))):
+            raise ValueError("cum0 holds one value per node")
+        c1 = _host(cum1).reshape(-1) if d > 1 else None
+        c2 = _host(cum2).reshape(-1) if d > 2 else None
+        if (d > 1 and c1.size != int(nn[1]) * (int(nn[2]) if d > 2 else 1)) or (d > 2 and c2.size != int(nn[2])):
+            raise ValueError("cum1 is (n2, n1) and cum2 (n2,)")
+        q = self._empty((max(n, 0), d))
+        cell = None
+        if cells:
+            cell = self._torch.empty((max(n, 0), d), dtype=self._torch.int32, device=f"cuda:{self.device}") if self.mem == "device" else np.empty((max(n, 0), d), dtype=np.int32)
+        _abi.check(self.lib, self.lib.rsf_grid_draw(self._ctx, d, _i32p(nn), _dp(xc), c, self._ptr(cum0), None if c1 is None else _dp(c1),
+                                                    None if c2 is None else _dp(c2), int(seed), int(offset), n, self._ptr(q), self._ptr(cell)))
+        return (q, np.asarray(cell.cpu() if hasattr(cell, "cpu") else cell)) if cells else q
+
+    def grid_cdf(self, x, cum0, pair, xs, coords=None):
+        """rsf_grid_cdf: the CDF of q0 (Dc, also where the grid's axis is Dc a) at the points xs → (len(xs),) on the host."""
+        d, nn, _, xc, _ = self._grid_axes(x)
+        c = self._grid_coords(coords, d)
+        cum0, pr = self._in(cum0), _host(pair).reshape(-1)
+        xs = np.ascontiguousarray(np.atleast_1d(np.asarray(xs, dtype=np.float64)))
+        if math.prod(cum0.shape) != int(np.prod(nn.astype(np.int64))) or pr.size * int(nn[0]) != math.prod(cum0.shape) or xs.ndim != 1:
+            raise ValueError("cum0 holds one value per node, pair one per column, xs is 1-D")
+        F = np.empty(xs.size)
+        _abi.check(self.lib, self.lib.rsf_grid_cdf(self._ctx, d, _i32p(nn), _dp(xc), c, self._ptr(cum0), _dp(pr), int(xs.size), _dp(xs), _dp(F)))
+        return F
+
+    def _grid_result(self, x, w, l, ssq, lo, hi, shape, coords, ltarget, outside=0.0, n_solves=0):
+        d, n, xs, _, wc = self._grid_axes(x, w)
+        ws = np.split(wc, np.cumsum(n)[:-1])
+        c = self._grid_coords(coords, d)
+        col = self.grid_columns(xs, ws, l, ssq)
+        fin = self.grid_finish(xs, ws, lo, hi, shape, col["lmax"], col["fields"], col["center"], c)
+        return GridPosterior(self, xs, ws, c, _vec(lo, d, "lo"), _vec(hi, d, "hi"), float(shape), col, fin, ltarget, float(outside), int(n_solves))
+
+    def grid_from_ssq(self, ssq_fn, x, w, lo, hi, shape, coords=None, outside=0.0):
+        """The grid posterior with the caller's sum of squares (the duck-typed model contract, the closed forms): ssq_fn(points
+        (m, d) float64 on the host, natural coordinates q) → SSq (m,), called for the nodes inside the closed box.  d = 1..3, no
+        model needed; the reductions, the tables, the draws and the CDF are the GPU's.  → GridPosterior."""
+        d, n, xs, _, _ = self._grid_axes(x, w)
+        c = self._grid_coords(coords, d)
+        lo, hi, shape = _vec(lo, d, "lo"), _vec(hi, d, "hi"), float(shape)
+        q = np.stack([np.ravel(a, order="F") for a in np.meshgrid(*xs, indexing="ij")], axis=1)
+        jac = 0.0
+        if c == _abi.GRID_PRODUCT:
+            jac = -np.log(q[:, 1])
+            q[:, 0] = q[:, 0] / q[:, 1]
+
+        def ltarget(pts, jac=0.0):
+            pts = np.asarray(pts, dtype=np.float64).reshape(-1, d)
+            inb = ((pts >= lo) & (pts <= hi)).all(axis=1)
+            s = np.full(pts.shape[0], np.nan)
+            if inb.any():
+                s[inb] = np.asarray(ssq_fn(pts[inb]), dtype=np.float64).reshape(-1)
+            ok = inb & np.isfinite(s) & (s > 0)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return np.where(ok, -shape * np.log(np.where(ok, s, 1.0)) + jac, -np.inf), s
+
+        l, ssq = ltarget(q, jac)
+        return self._grid_result(xs, w, l, ssq, lo, hi, shape, c, lambda pts: self._in(ltarget(_host(pts))[0]), outside, int(np.isfinite(ssq).sum()))
+
+    def grid_posterior(self, data, lo, hi, n=None, coords=None, window_sd=12.0, shape=None, n_coarse=None):
+        """The exact posterior of the device model (set_model) given `data` over the closed box [lo, hi], d = 1 (Dc) or 3 (Dc, a, b),
+        by quadrature on the GPU in two stages (the procedure of the test-suite's reference quadrature).  A coarse scan of the whole
+        box — d = 1: n_coarse (4001) linearly and as many logarithmically spaced nodes strictly inside, trapezoid weights; d = 3: a
+        coarse axis (801 + 801) in Dc a at the first, middle and last (a, b) nodes — finds the mass: the window is mean +- window_sd
+        SD (of the widest column at d = 3), clipped to the box, and `outside` the coarse mass beyond it.  The fine grid: d = 1,
+        n = (4001,) Simpson nodes on the window; d = 3, n = (2001, 65, 65): coords 'product' (axis 0 is Dc a, which straightens the
+        ridge Dc a = const), axes 1 and 2 uniform over [lo, hi] with the faces, Simpson on every axis (odd n).  → GridPosterior."""
+        self._need_model()
+        blo, bhi, d = self._smc_box(lo, hi)
+        if d not in (1, 3):
+            raise ValueError("the box has d = 1 (Dc) or 3 (Dc, a, b) parameters")
+        shape = 0.5 * self.nout if shape is None else float(shape)
+        n = ((4001,) if d == 1 else (2001, 65, 65)) if n is None else tuple(int(v) for v in np.atleast_1d(n))
+        if len(n) != d or any(v < 3 or v % 2 == 0 for v in n):
+            raise ValueError(f"n holds {d} odd node counts >= 3 (composite Simpson)")
+        c = self._grid_coords(("product" if d == 3 else "plain") if coords is None else coords, d)
+        obs = self._in(data)
+        ltarget = lambda pts: self.evidence_logtarget(pts, obs, blo, bhi, self._in(np.zeros(int(math.prod(pts.shape)) // d)), shape)
+        nc = (4001 if d == 1 else 801) if n_coarse is None else int(n_coarse)
+        prod = c == _abi.GRID_PRODUCT
+        alo, ahi = (blo[0] * blo[1], bhi[0] * bhi[1]) if prod else (blo[0], bhi[0])  # the range of axis 0
+        xc = np.linspace(alo, ahi, nc)
+        if alo >= 0:
+            xc = np.union1d(xc, np.geomspace(max(alo, 1e-6 * ahi), ahi, nc))
+        xc = xc[(xc > alo) & (xc < ahi)]
+        wc = np.zeros_like(xc)
+        wc[:-1] += 0.5 * np.diff(xc)
+        wc[1:] += 0.5 * np.diff(xc)
+        fine = [_simpson_axis(blo[p], bhi[p], n[p]) for p in range(1, d)]
+        sel = [a[0][[0, a[0].size // 2, a[0].size - 1]] for a in fine]
+        cx, cw = [xc] + sel, [wc] + [np.ones(3)] * (d - 1)
+        l, ssq = self.grid_logtarget(cx, obs, blo, bhi, c, shape)
+        col = self.grid_columns(cx, cw, l, ssq, m0=False, cum0=False)
+        f = col["fields"]
+        if not (f[:, 0] > 0).any():
+            raise _abi.RsfError(-1, "Engine.grid_posterior: the target has no mass inside the box")
+        ok = f[:, 0] > 0
+        mc = col["center"] + f[ok, 1] / f[ok, 0]
+        sc = np.sqrt(np.maximum(f[ok, 2] / f[ok, 0] - (f[ok, 1] / f[ok, 0]) ** 2, 0.0))
+        wlo, whi = max(float((mc - window_sd * sc).min()), alo), min(float((mc + window_sd * sc).max()), ahi)
+        if not wlo < whi:
+            raise _abi.RsfError(-1, "Engine.grid_posterior: the coarse scan does not resolve the posterior (no spread on the coarse axis)")
+        e = np.exp(np.where(np.isfinite(_host(l)), _host(l) - col["lmax"], -np.inf)).reshape(-1, xc.size)
+        out = (xc < wlo) | (xc > whi)
+        outside = float(((wc * e)[:, out].sum(axis=1)[ok] / f[ok, 0]).max()) if out.any() else 0.0
+        x0 = _simpson_axis(wlo, whi, n[0])
+        xs, ws = [x0[0]] + [a[0] for a in fine], [x0[1]] + [a[1] for a in fine]
+        l, ssq = self.grid_logtarget(xs, obs, blo, bhi, c, shape)
+        return self._grid_result(xs, ws, l, ssq, blo, bhi, shape, c, ltarget, outside, int(xc.size * 3 ** (d - 1) + math.prod(n)))
 
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
     def _diag_trace(self, trace):
