@@ -665,6 +665,72 @@ class MCMC:
             eng.sync()
         return self._ensemble_pool(res, std2, nburn, extra)
 
+    @staticmethod
+    def _dr_pool(res, std2, nburn, extra=None):
+        """Engine.dr's result and the kept states' sigma^2 → the PosteriorPool of sample_dr"""
+        n = res.q.shape[0]
+        first, second = res.accept_rates
+        stats = {"accepted": int(res.accepted1.sum() + res.accepted2.sum()), "accepted1": int(res.accepted1.sum()), "accepted2": int(res.accepted2.sum()),
+                 "out_of_bounds": int(res.outbox1.sum()), "out_of_bounds2": int(res.outbox2.sum()), "stuck": int(res.stuck.sum()),
+                 "accept_rate1": first, "accept_rate2": second, "n_solves": res.n_solves, "n_iter": res.n_iter, "shape": res.shape, "l": res.trace_l,
+                 "n_chains": n, "gamma": res.gamma, "stages": res.stages, "chol": res.chol}
+        stats.update(extra or {})
+        return PosteriorPool(res.trace_q, std2, res.accept_rate, stats, nburn)
+
+    def _dr_init_factor(self, eng, q0):
+        """the lower Cholesky factor of the init kernel's proposal covariance at the point q0 (d,): what sample_batched proposes from"""
+        self._init_chains(eng, np.asarray(q0, dtype=np.float64).reshape(1, -1), adapt_mode="none")
+        V = _host(eng.get_state()[3]).reshape(self.n_params, self.n_params)
+        return np.linalg.cholesky(V)
+
+    def sample_dr(self, n_chains, n_iter, nburn=None, start="qstart", factor="init", gamma=0.2, stages=2, adapt=True, seed=0, mem="device", device=-1,
+                  chain_offset=0, thin=1, iters_per_launch=16):
+        """Two-stage delayed-rejection Metropolis (additive; Engine.dr): n_chains random-walk chains that, when their proposal
+        q + L z is rejected — outside the box it is, without a forward solve — propose q + gamma L z' in the same iteration, with
+        the correction that keeps the target exact.  No gradient, no fit and no other chain is needed.  start="qstart": every
+        chain at qstart; "fit": at self.fit(seed=seed).best()'s point; an array (n_chains, d): there.  factor="init": the init
+        kernel's covariance at the start point (chain 0's for an array), which sample_batched proposes from; "fit":
+        FitResult.covariance(); an array (d, d): that lower triangular factor.  adapt=True: during burn-in, after every launch, L
+        becomes chol(2.38^2 / d cov + eps) of every burn-in state so far, pooled over the chains (Engine.dr's adapt_launches); it is
+        frozen for the kept iterations: the nburn // iters_per_launch launches that lie wholly inside the burn-in adapt.  The target is the n0 = 0 posterior
+        pi(q) ~ 1_box SSq^-N/2, sigma^2 drawn afterwards from its conditional at each kept state's own Philox iteration.  nburn:
+        iterations dropped, by default n_iter // 2; every thin-th of the others is kept.  Returns a PosteriorPool; its stats carry
+        both stages' acceptance (accepted1, accepted2, accept_rate1, accept_rate2), both out-of-box counts (out_of_bounds,
+        out_of_bounds2), stuck, n_solves — the forward solves spent — and the factor in use at the end (chol)."""
+        n_chains, n_iter, ipl = int(n_chains), int(n_iter), int(iters_per_launch)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_chains < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1 or ipl < 1:
+            raise ValueError("n_chains >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1, iters_per_launch >= 1")
+        if isinstance(start, str) and start not in ("qstart", "fit"):
+            raise ValueError(f"start is 'qstart', 'fit' or an array of chains, not {start!r}")
+        if isinstance(factor, str) and factor not in ("init", "fit"):
+            raise ValueError(f"factor is 'init', 'fit' or a (d, d) array, not {factor!r}")
+        if not self._device_model():
+            raise TypeError("sample_dr integrates the model on the device: `model` must be this package's RateStateModel")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
+        d, extra = self.n_params, {}
+        fit = self.fit(seed=seed, device=device) if "fit" in (start if isinstance(start, str) else "", factor if isinstance(factor, str) else "") else None
+        if fit is not None:
+            extra["fit"] = fit
+        if isinstance(start, str):
+            q0 = np.tile((fit.q[fit.best()] if start == "fit" else np.asarray(self.qstart, dtype=np.float64)).reshape(1, d), (n_chains, 1))
+        else:
+            q0 = _host(start).reshape(-1, d)
+            if q0.shape[0] != n_chains:
+                raise ValueError(f"start holds {q0.shape[0]} chains, not {n_chains}")
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            if isinstance(factor, str):
+                L = self._dr_init_factor(eng, q0[0]) if factor == "init" else np.linalg.cholesky(fit.covariance())
+            else:
+                L = np.asarray(factor, dtype=np.float64).reshape(d, d)
+            res = eng.dr(q0, data, lo, hi, L, n_iter, gamma=gamma, stages=stages, seed=seed, offset=chain_offset, iters_per_launch=ipl,
+                         keep=n_iter - nburn, thin=thin, adapt_launches=nburn // ipl if adapt else 0)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        return self._dr_pool(res, std2, nburn, extra)
+
     def quadrature(self, n=None, n_draws=0, seed=0, coords=None, window_sd=12.0, mem="device", device=-1):
         """The exact posterior by quadrature on the GPU (additive; Engine.grid_posterior): the n0 = 0 target
         pi(q) ~ 1_box SSq^-N/2 tabulated on a tensor grid over the prior box — d = 1: n = (4001,) Simpson nodes of Dc; d = 3:

@@ -14,12 +14,12 @@ import numpy as np
 
 if __package__:
     from . import _figures, json_save_load
-    from .engine import Engine, EnsembleResult, MalaResult, whole_islands
+    from .engine import DrResult, Engine, EnsembleResult, MalaResult, whole_islands
     from .MCMC import MCMC, PosteriorPool
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     import json_save_load
-    from engine import Engine, EnsembleResult, MalaResult, whole_islands
+    from engine import DrResult, Engine, EnsembleResult, MalaResult, whole_islands
     from MCMC import MCMC, PosteriorPool
 
 
@@ -268,6 +268,52 @@ class RSF:
             part = EnsembleResult(res.q[s], res.l[s], res.accepted[s], res.outbox[s], res.stuck[s], res.n_iter, res.trace_q[:, s], res.trace_l[:, s],
                                   res.iterations, res.island_size, res.shape, res.seed, res.offset + g * per, res.logmask, res.a)
             out[float(dc)] = MCMC._ensemble_pool(part, std2[:, s], nburn)
+        return out
+
+    def inference_dr(self, n_chains=256, n_iter=200, nburn=None, start="qstart", factor="init", gamma=0.2, stages=2, adapt=True, seed=0, mem="device",
+                     device=-1, thin=1, iters_per_launch=16):
+        """Additive: the posterior of every true Dc of dc_list by two-stage delayed-rejection Metropolis in ONE call (Engine.dr) —
+        each is an observation group of n_chains chains (rounded up to whole workgroups when there is more than one group) with
+        its own proposal factor, started at qstart (start="qstart") or at its group's least-squares estimate (start="fit":
+        inference_fit).  factor="init": each group's init-kernel covariance at its start point; "fit": its least-squares
+        covariance.  Returns {dc: PosteriorPool} as MCMC.sample_dr gives it for one group; chain j of group g draws from the Philox
+        stream (seed, g * n_chains (rounded) + j).  The `inference` path is not touched."""
+        n_chains, n_iter, ipl = int(n_chains), int(n_iter), int(iters_per_launch)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_chains < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1 or ipl < 1:
+            raise ValueError("n_chains >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1, iters_per_launch >= 1")
+        if start not in ("fit", "qstart"):
+            raise ValueError(f"start is 'fit' or 'qstart', not {start!r}")
+        if factor not in ("init", "fit"):
+            raise ValueError(f"factor is 'init' or 'fit', not {factor!r}")
+        n, G = self.model.num_tsteps, len(self.dc_list)
+        data = np.ascontiguousarray(np.asarray(self.data, dtype=np.float64).reshape(G, n))
+        probes = [MCMC(self.model, data[g], self.dc_list[g], self.qpriors, self.qstart, nsamples=10) for g in range(G)]
+        lo, hi = probes[0].qstart_limits[:, 0], probes[0].qstart_limits[:, 1]
+        d = probes[0].n_params
+        starts = np.tile(np.asarray(self.qstart, dtype=np.float64).reshape(1, d), (G, 1))
+        est = self.inference_fit(seed=seed, mem=mem, device=device) if "fit" in (start, factor) else None
+        if start == "fit":
+            starts = np.stack([est[float(dc)]["q"] for dc in self.dc_list])
+        out = {}
+        with Engine(mem=mem, device=device) as eng:
+            per = -(-n_chains // eng.block_threads) * eng.block_threads if G > 1 else n_chains
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            if factor == "init":
+                L = np.stack([probes[g]._dr_init_factor(eng, starts[g]) for g in range(G)])
+            else:
+                L = np.stack([np.linalg.cholesky(est[float(dc)]["cov"]) for dc in self.dc_list])
+            res = eng.dr(np.repeat(starts, per, axis=0), data, lo, hi, L, n_iter, gamma=gamma, stages=stages, seed=seed, iters_per_launch=ipl,
+                         keep=n_iter - nburn, thin=thin, adapt_launches=nburn // ipl if adapt else 0)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        self.dr_result = res
+        for g, dc in enumerate(self.dc_list):
+            s = slice(g * per, (g + 1) * per)
+            part = DrResult(res.q[s], res.l[s], [c[s] for c in (res.accepted1, res.accepted2, res.outbox1, res.outbox2, res.stuck)], res.n_iter,
+                            res.trace_q[:, s], res.trace_l[:, s], res.iterations, res.chol[g:g + 1], res.gamma, res.stages, res.shape, res.seed,
+                            res.offset + g * per, res.iter0)
+            out[float(dc)] = MCMC._dr_pool(part, std2[:, s], nburn)
         return out
 
     @measure_execution_time

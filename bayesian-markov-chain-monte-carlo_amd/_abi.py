@@ -286,6 +286,18 @@ ENSEMBLE_PROTOTYPES = {
 }
 ENSEMBLE_MAX_PARAMS = 3  # RSF_ENSEMBLE_MAX_PARAMS
 ENSEMBLE_MAX_ITER = 64   # RSF_ENSEMBLE_MAX_ITER: iterations per rsf_ensemble_run call
+# include/rsf_dr.h: two-stage delayed-rejection Metropolis; exported by librsf_hip.so only, bound by load()
+DR_PROTOTYPES = {
+    "rsf_dr_run": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, c_int32, _DP, _DP, _DP, c_double, c_int32, c_double, c_uint64, c_int64, c_int64,
+                           c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "rsf_dr_propose": (c_int, [c_void_p, c_int64, c_int32, _P, _P, c_int32, _DP, _DP, _DP, c_double, c_int32, c_uint64, c_int64, c_int64, _P, _P, _P]),
+    "rsf_dr_accept": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _DP, _DP, c_double, c_int32, c_double, c_uint64, c_int64, c_int64, _P, _P, _P, _P,
+                              _P, _P, _P, _P, _P, _P]),
+    "rsf_dr_ssq": (c_int, [c_void_p, c_int64, c_int32, _P, _P, _P, c_int32, _P]),
+}
+DR_MAX_PARAMS = 3   # RSF_DR_MAX_PARAMS
+DR_MAX_ITER = 64    # RSF_DR_MAX_ITER: iterations per rsf_dr_run call
+DR_MAX_GROUPS = 64  # RSF_DR_MAX_GROUPS: observation series, and factors, per call
 # include/rsf_grid.h: the exact posterior on a tensor quadrature grid; exported by librsf_hip.so only, bound by load()
 GRID_PROTOTYPES = {
     "rsf_grid_logtarget": (c_int, [c_void_p, c_int32, _I32P, _DP, _P, c_double, _DP, _DP, c_int32, _P, _P]),
@@ -348,7 +360,8 @@ def load():
         ctypes.CDLL(hip_runtime_path(), mode=ctypes.RTLD_GLOBAL)  # resolves the library's hip* symbols
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
-                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES):
+                      SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
+                      DR_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -1,0 +1,178 @@
+// rsf_dr.hip — two-stage delayed-rejection Metropolis (include/rsf_dr.h): rsf_dr_run / _propose / _accept / _ssq (kernels:
+// rsf_kernels_dr.h).
+#include <cmath>
+
+#include "rsf_host.h"
+#include "rsf_kernels_dr.h"
+
+using namespace rsfk;
+using namespace rsfh;
+
+namespace {
+
+// what the calls share: the chains and their groups, the box and the Philox stream; iterations first .. first + count - 1.
+// whole_blocks: a group's chains are whole workgroups (the calls that solve)
+int set_chains(const char *fn, const rsf_ctx *c, int64_t n, int32_t d, bool solve, int32_t n_groups, const double *lo, const double *hi, uint64_t seed,
+               int64_t offset, int64_t first, int64_t count, DrArgs &A) {
+  if (solve ? (d != 1 && d != 3) : (d < 1 || d > RSF_DR_MAX_PARAMS)) return fail(RSF_ERR_INVALID, "%s: need %s", fn, solve ? "d = 1 or 3" : "1 <= d <= 3");
+  if (n < 1) return fail(RSF_ERR_INVALID, "%s: need n >= 1", fn);
+  if (n_groups < 1 || n_groups > RSF_DR_MAX_GROUPS) return fail(RSF_ERR_INVALID, "%s: need 1 <= n_groups <= %d", fn, RSF_DR_MAX_GROUPS);
+  if (n_groups > 1 && (n % n_groups || (solve && (n / n_groups) % c->block)))
+    return fail(RSF_ERR_INVALID, "%s: with n_groups > 1, n / n_groups must be a whole number%s", fn, solve ? " of workgroups (the ctx's block_threads)" : "");
+  if (offset < 0) return fail(RSF_ERR_INVALID, "%s: offset must be >= 0", fn);
+  if (first < 1 || first + count > ((int64_t)1 << 32)) return fail(RSF_ERR_INVALID, "%s: the Philox iterations must lie in 1 .. 2^32 - 1", fn);
+  for (int p = 0; p < d; ++p) {
+    if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "%s: need finite lo[%d] < hi[%d]", fn, p, p);
+    A.lo[p] = lo[p]; A.hi[p] = hi[p];
+  }
+  A.n = n; A.offset = offset; A.seed = seed; A.iter = (uint32_t)first;
+  A.group_chains = n_groups > 1 ? n / n_groups : 0;
+  return RSF_OK;
+}
+
+// chol[n_groups][d (d + 1) / 2], HOST: every entry finite, every diagonal entry positive → the ctx's poolws workspace, in A.chol.
+// One copy; the stream is synchronised before the caller's array may go away.
+int set_factors(const char *fn, rsf_ctx *c, int32_t d, int32_t n_groups, const double *chol, DrArgs &A) {
+  const int ne = d * (d + 1) / 2;
+  for (int g = 0; g < n_groups; ++g)
+    for (int p = 0, e = 0; p < d; ++p)
+      for (int r = 0; r <= p; ++r, ++e) {
+        const double v = chol[g * ne + e];
+        if (!std::isfinite(v) || (r == p && !(v > 0.0)))
+          return fail(RSF_ERR_INVALID, "%s: chol of group %d is not a lower triangular factor with a positive finite diagonal (entry [%d][%d])", fn, g, p, r);
+      }
+  const size_t bytes = (size_t)n_groups * ne * sizeof(double);
+  if (int rc = ensure(c->poolws, bytes)) return rc;
+  HIP_TRY(hipMemcpyAsync(c->poolws.p, chol, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  A.chol = (const double *)c->poolws.p;
+  return RSF_OK;
+}
+
+bool good_gamma(double gamma) { return std::isfinite(gamma) && gamma > 0.0 && gamma <= 1.0; }
+
+auto run_fn(const rsf_ctx *c, int d) {
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return dr_kernel<D, DAMP>; }); });
+}
+auto ssq_fn(const rsf_ctx *c, int d) {
+  return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return dr_ssq_kernel<D, DAMP>; }); });
+}
+auto propose_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return dr_propose_kernel<D>; }); }
+auto accept_fn(int d) { return with<1, 2, 3>(d, [](auto D) { return dr_accept_kernel<D>; }); }
+
+}  // namespace
+
+extern "C" {
+
+int rsf_dr_run(rsf_ctx *c, int64_t n, int32_t d, double *q, double *l, const double *data, int32_t n_groups, const double *lo, const double *hi,
+               const double *chol, double gamma, int32_t stages, double shape, uint64_t seed, int64_t offset, int64_t iter0, int32_t n_iter,
+               int32_t *accepted1, int32_t *accepted2, int32_t *outbox1, int32_t *outbox2, int32_t *stuck, double *trace_q, double *trace_l) {
+  RSF_ENTER(c, NEED_MODEL, q && l && data && lo && hi && chol && accepted1 && accepted2 && outbox1 && outbox2 && stuck, "NULL argument");
+  if (n_iter < 1 || n_iter > RSF_DR_MAX_ITER) return fail(RSF_ERR_INVALID, "rsf_dr_run: need 1 <= n_iter <= %d", RSF_DR_MAX_ITER);
+  if (!trace_q != !trace_l) return fail(RSF_ERR_INVALID, "rsf_dr_run: trace_q and trace_l are both NULL or both given");
+  if (stages != 1 && stages != 2) return fail(RSF_ERR_INVALID, "rsf_dr_run: stages is 1 or 2");
+  if (!good_gamma(gamma) || !std::isfinite(shape) || !(shape > 0.0))
+    return fail(RSF_ERR_INVALID, "rsf_dr_run: gamma must lie in (0, 1], shape be finite and > 0");
+  int rc;
+  DrArgs A{};
+  if ((rc = set_chains(__func__, c, n, d, true, n_groups, lo, hi, seed, offset, iter0, n_iter, A))) return rc;
+  if (c->m.flags & RSF_FLAG_DOP853)
+    return fail(RSF_ERR_UNSUPPORTED, "rsf_dr_run: a model flagged RSF_FLAG_DOP853 is not supported (the solve is the float64 RK4)");
+  if ((rc = set_factors(__func__, c, d, n_groups, chol, A))) return rc;
+  A.gamma = gamma; A.shape = shape; A.stages = stages; A.n_iter = n_iter;
+  const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int32_t);
+  Staged s(c);
+  const int iq = s.add(q, nb * d, true, true), il = s.add(l, nb, true, true);
+  const int idata = s.add(data, (size_t)n_groups * c->nout * sizeof(double), true, false);
+  const int ia1 = s.add(accepted1, ni, true, true), ia2 = s.add(accepted2, ni, true, true), io1 = s.add(outbox1, ni, true, true);
+  const int io2 = s.add(outbox2, ni, true, true), ist = s.add(stuck, ni, true, true);
+  const int itq = trace_q ? s.add(trace_q, nb * d * n_iter, false, true) : -1, itl = trace_q ? s.add(trace_l, nb * n_iter, false, true) : -1;
+  if ((rc = s.commit())) return rc;
+  A.q = s.dev<double>(iq); A.l = s.dev<double>(il);
+  A.accepted1 = s.dev<int32_t>(ia1); A.accepted2 = s.dev<int32_t>(ia2); A.outbox1 = s.dev<int32_t>(io1); A.outbox2 = s.dev<int32_t>(io2);
+  A.stuck = s.dev<int32_t>(ist);
+  if (trace_q) { A.tq = s.dev<double>(itq); A.tl = s.dev<double>(itl); }
+  // the shared chunking of the float64 tables (c->kc, c->lds_bytes), as rsf_smc_move's solve
+  if ((rc = launch(c, run_fn(c, d), grid_for(c, n), c->block, c->lds_bytes, make_consts(c, s.dev<const double>(idata)), A))) return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+int rsf_dr_propose(rsf_ctx *c, int64_t n, int32_t d, const double *q, const double *l, int32_t n_groups, const double *lo, const double *hi,
+                   const double *chol, double gamma, int32_t stage, uint64_t seed, int64_t offset, int64_t iter, const uint8_t *pending, double *y,
+                   uint8_t *mask) {
+  RSF_ENTER(c, NEED_NOTHING, q && l && lo && hi && chol && y && mask, "NULL argument");
+  if (stage != 1 && stage != 2) return fail(RSF_ERR_INVALID, "rsf_dr_propose: stage is 1 or 2");
+  if (stage == 2 && !pending) return fail(RSF_ERR_INVALID, "rsf_dr_propose: stage 2 needs pending");
+  if (!good_gamma(gamma)) return fail(RSF_ERR_INVALID, "rsf_dr_propose: gamma must lie in (0, 1]");
+  int rc;
+  DrArgs A{};
+  if ((rc = set_chains(__func__, c, n, d, false, n_groups, lo, hi, seed, offset, iter, 1, A))) return rc;
+  if ((rc = set_factors(__func__, c, d, n_groups, chol, A))) return rc;
+  A.gamma = gamma; A.stages = stage;
+  const size_t nb = (size_t)n * sizeof(double);
+  Staged s(c);
+  const int iq = s.add(q, nb * d, true, false), il = s.add(l, nb, true, false);
+  const int ip = stage == 2 ? s.add(pending, (size_t)n, true, false) : -1;
+  const int iy = s.add(y, nb * d, false, true), im = s.add(mask, (size_t)n, false, true);
+  if ((rc = s.commit())) return rc;
+  A.q = s.dev<double>(iq); A.l = s.dev<double>(il);
+  if ((rc = launch(c, propose_fn(d), blocks_of(n), kMaxBlock, 0, A, stage == 2 ? s.dev<const uint8_t>(ip) : nullptr, s.dev<double>(iy),
+                   s.dev<uint8_t>(im))))
+    return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+int rsf_dr_accept(rsf_ctx *c, int64_t n, int32_t d, double *q, double *l, const double *lo, const double *hi, double gamma, int32_t stage, double shape,
+                  uint64_t seed, int64_t offset, int64_t iter, const double *y, const uint8_t *mask, const double *ssq, double *l1, uint8_t *pending,
+                  int32_t *accepted1, int32_t *accepted2, int32_t *outbox1, int32_t *outbox2, int32_t *stuck) {
+  RSF_ENTER(c, NEED_NOTHING, q && l && lo && hi && y && mask && ssq && l1 && pending && accepted1 && accepted2 && outbox1 && outbox2 && stuck,
+            "NULL argument");
+  if (stage != 1 && stage != 2) return fail(RSF_ERR_INVALID, "rsf_dr_accept: stage is 1 or 2");
+  if (!good_gamma(gamma) || !std::isfinite(shape) || !(shape > 0.0))
+    return fail(RSF_ERR_INVALID, "rsf_dr_accept: gamma must lie in (0, 1], shape be finite and > 0");
+  int rc;
+  DrArgs A{};
+  if ((rc = set_chains(__func__, c, n, d, false, 1, lo, hi, seed, offset, iter, 1, A))) return rc;
+  A.gamma = gamma; A.shape = shape; A.stages = stage;
+  const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int32_t);
+  const bool first = stage == 1;
+  Staged s(c);
+  const int iq = s.add(q, nb * d, true, true), il = s.add(l, nb, true, true), iy = s.add(y, nb * d, true, false);
+  const int im = s.add(mask, (size_t)n, true, false), is = s.add(ssq, nb, true, false);
+  const int il1 = s.add(l1, nb, !first, first), ip = s.add(pending, (size_t)n, !first, first);
+  const int ia1 = s.add(accepted1, ni, true, true), ia2 = s.add(accepted2, ni, true, true), io1 = s.add(outbox1, ni, true, true);
+  const int io2 = s.add(outbox2, ni, true, true), ist = s.add(stuck, ni, true, true);
+  if ((rc = s.commit())) return rc;
+  A.q = s.dev<double>(iq); A.l = s.dev<double>(il);
+  A.accepted1 = s.dev<int32_t>(ia1); A.accepted2 = s.dev<int32_t>(ia2); A.outbox1 = s.dev<int32_t>(io1); A.outbox2 = s.dev<int32_t>(io2);
+  A.stuck = s.dev<int32_t>(ist);
+  if ((rc = launch(c, accept_fn(d), blocks_of(n), kMaxBlock, 0, A, s.dev<const double>(iy), s.dev<const uint8_t>(im), s.dev<const double>(is),
+                   s.dev<double>(il1), s.dev<uint8_t>(ip))))
+    return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+int rsf_dr_ssq(rsf_ctx *c, int64_t n, int32_t d, const double *y, const uint8_t *mask, const double *data, int32_t n_groups, double *ssq) {
+  RSF_ENTER(c, NEED_MODEL, y && mask && data && ssq, "NULL argument");
+  const double box[2][RSF_DR_MAX_PARAMS] = {{0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};  // the solve takes no box
+  int rc;
+  DrArgs A{};
+  if ((rc = set_chains(__func__, c, n, d, true, n_groups, box[0], box[1], 0, 0, 1, 1, A))) return rc;
+  if (c->m.flags & RSF_FLAG_DOP853)
+    return fail(RSF_ERR_UNSUPPORTED, "rsf_dr_ssq: a model flagged RSF_FLAG_DOP853 is not supported (the solve is the float64 RK4)");
+  const size_t nb = (size_t)n * sizeof(double);
+  Staged s(c);
+  const int iy = s.add(y, nb * d, true, false), im = s.add(mask, (size_t)n, true, false);
+  const int idata = s.add(data, (size_t)n_groups * c->nout * sizeof(double), true, false), is = s.add(ssq, nb, true, true);
+  if ((rc = s.commit())) return rc;
+  if ((rc = launch(c, ssq_fn(c, d), grid_for(c, n), c->block, c->lds_bytes, make_consts(c, s.dev<const double>(idata)), A, s.dev<const double>(iy),
+                   s.dev<const uint8_t>(im), s.dev<double>(is))))
+    return rc;
+  if ((rc = s.back())) return rc;
+  return finish(c);
+}
+
+}  // extern "C"

@@ -312,6 +312,57 @@ class MalaResult:
         return np.stack(out) if kept else out[0]
 
 
+class DrResult:
+    """Result of Engine.dr / Engine.dr_from_ssq: per chain the final state q (n, d) and l = -shape log SSq (n,), the counters
+    accepted1, accepted2 (proposals accepted at stage 1 and 2), outbox1, outbox2 (proposals outside the box) and stuck (iterations
+    without a proposal), (n,) int32, over n_iter iterations; trace_q (n_keep, n, d) and trace_l (n_keep, n), the kept states, and
+    iterations (n_keep,), the Philox iteration of each kept row; chol (G, d, d), the factor of each group in use at the end (the
+    start's unless adapt_launches replaced it).  NumPy arrays on the host.  The target is pi(q) ~ 1_box SSq^-shape; std2 completes it."""
+
+    def __init__(self, q, l, counters, n_iter, trace_q, trace_l, iterations, chol, gamma, stages, shape, seed, offset, iter0=1):
+        self.q, self.l, self.iter0 = q, l, int(iter0)
+        self.accepted1, self.accepted2, self.outbox1, self.outbox2, self.stuck = counters
+        self.n_iter, self.trace_q, self.trace_l, self.iterations, self.chol = int(n_iter), trace_q, trace_l, iterations, chol
+        self.gamma, self.stages, self.shape, self.seed, self.offset = float(gamma), int(stages), float(shape), int(seed), int(offset)
+
+    def _rate(self, c):
+        return float(c.sum()) / (self.n_iter * c.shape[0])
+
+    @property
+    def accept_rate(self):
+        """iterations that moved the chain (at either stage) / iterations, over all chains"""
+        return self._rate(self.accepted1) + self._rate(self.accepted2)
+
+    @property
+    def accept_rates(self):
+        """(stage 1 accepted / iterations, stage 2 accepted / second proposals made)"""
+        second = self.n_iter * self.q.shape[0] - int(self.stuck.sum()) - int(self.accepted1.sum())
+        return self._rate(self.accepted1), (float(self.accepted2.sum()) / second if second and self.stages == 2 else 0.0)
+
+    @property
+    def outbox_rates(self):
+        """(first, second) proposals outside the box / iterations, over all chains"""
+        return self._rate(self.outbox1), self._rate(self.outbox2)
+
+    @property
+    def n_solves(self):
+        """forward solves of the run: every first proposal inside the box, and (stages = 2) every second one inside the box"""
+        c = [np.asarray(x, dtype=np.int64) for x in (self.accepted1, self.outbox1, self.outbox2, self.stuck)]
+        first = int((self.n_iter - c[3] - c[1]).sum())
+        return first + (int((self.n_iter - c[3] - c[0] - c[2]).sum()) if self.stages == 2 else 0)
+
+    def std2(self, seed=None, engine=None, kept=False):
+        """sigma^2 | q ~ InvGamma(shape, SSq / 2) by Engine.smc_std2 of the final states' l → (n,), or with kept=True of the kept
+        states → (n_keep, n), row r with the gamma variates of Philox iteration iterations[r].  seed: by default the run's;
+        engine: by default a host-memory Engine made for the call."""
+        seed = self.seed if seed is None else int(seed)
+        rows = self.trace_l if kept else self.l[None]
+        its = self.iterations if kept else [self.iter0 + self.n_iter - 1]
+        with contextlib.nullcontext(engine) if engine is not None else Engine(mem="host") as eng:
+            out = [_host(eng.smc_std2(r, self.shape, seed, self.offset, int(t))) for r, t in zip(rows, its)]
+        return np.stack(out) if kept else out[0]
+
+
 def whole_islands(n_walkers, island_size):
     """n_walkers rounded up to whole islands of island_size walkers (the ensemble sampler runs whole islands only)"""
     n_walkers, island_size = int(n_walkers), int(island_size)
@@ -2093,6 +2144,281 @@ class Engine:
             if it > n_iter - keep:
                 kept.append((_host(q).copy()[None], _host(l).copy()[None]))
         return self._ens_result(q, l, counters, n_iter, kept, keep, thin, shape, seed, offset, mask, a)
+
+    # -- two-stage delayed-rejection Metropolis (include/rsf_dr.h) ------------------------------
+    @staticmethod
+    def _dr_factors(chol, d, G=None):
+        """chol: (d, d), or (G, d, d) lower triangular factors (a scalar or (G,) values at d = 1) → (G, d, d) float64; every entry
+        finite, nothing above the diagonal, every diagonal entry > 0"""
+        L = np.asarray(chol, dtype=np.float64)
+        if d == 1 and L.ndim <= 1:
+            L = L.reshape(-1, 1, 1)
+        if L.ndim == 2:
+            L = L[None]
+        if L.ndim != 3 or L.shape[1:] != (d, d) or L.shape[0] < 1:
+            raise ValueError(f"chol has shape {np.shape(chol)}: ({d}, {d}) or (G, {d}, {d})")
+        if G is not None and L.shape[0] != G:
+            L = np.broadcast_to(L, (G, d, d)) if L.shape[0] == 1 else L
+            if L.shape[0] != G:
+                raise ValueError(f"chol holds {L.shape[0]} factors for {G} groups")
+        if not (np.isfinite(L).all() and (np.triu(L, 1) == 0.0).all() and (np.diagonal(L, axis1=1, axis2=2) > 0.0).all()):
+            raise ValueError("chol is not a lower triangular factor with a positive finite diagonal")
+        return np.ascontiguousarray(L)
+
+    @staticmethod
+    def _dr_pack(L):
+        """(G, d, d) factors → (G, d (d + 1) / 2) row-major lower triangles, rsf_dr_run's layout"""
+        d = L.shape[1]
+        r, c = np.tril_indices(d)
+        return np.ascontiguousarray(L[:, r, c])
+
+    def _dr_state(self, q, l, counters=()):
+        """The check of a chain state handed to the low-level calls, which read and write it through raw addresses: q (n, d) and
+        l (n,) float64 and the five counters (n,) int32, each a C-contiguous array of this engine's memory space → (n, d)"""
+        if getattr(q, "ndim", 0) != 2:
+            raise ValueError("q is (n, d)")
+        n, d = int(q.shape[0]), int(q.shape[1])
+        names = ("accepted1", "accepted2", "outbox1", "outbox2", "stuck")
+        if len(counters) not in (0, 5):
+            raise ValueError("the counters are accepted1, accepted2, outbox1, outbox2 and stuck")
+        t = self._torch
+        for what, x, shape, dt in [("q", q, (n, d), "float64"), ("l", l, (n,), "float64")] + [(k, c, (n,), "int32") for k, c in zip(names, counters)]:
+            if self.mem == "device":
+                good = isinstance(x, t.Tensor) and x.is_cuda and x.is_contiguous() and str(x.dtype) == "torch." + dt
+            else:
+                good = isinstance(x, np.ndarray) and x.flags["C_CONTIGUOUS"] and x.dtype == np.dtype(dt)
+            if not good or tuple(x.shape) != shape:
+                raise ValueError(f"{what} must be a C-contiguous {dt} array of shape {shape} in this engine's memory space ({self.mem})")
+        return n, d
+
+    def dr_run(self, q, l, data, lo, hi, chol, n_iter, counters, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iter0=1, trace=False):
+        """rsf_dr_run, the fused hot path: n_iter iterations IN PLACE in q (n, d), l (n,) and the five int32 counters (accepted1,
+        accepted2, outbox1, outbox2, stuck), contiguous arrays of this engine's memory space; iteration k uses the draws of Philox
+        iteration iter0 + k of particle offset + j.  data (nout,) or (G, nout) and chol (d, d) or (G, d, d): the chains split
+        evenly over the groups in whole workgroups.  trace=True → (trace_q (n_iter, n, d), trace_l (n_iter, n)), the state after
+        each iteration."""
+        self._need_model()
+        n, d = self._dr_state(q, l, counters)
+        data = self._in(data)
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        tri = self._dr_pack(self._dr_factors(chol, d, G))
+        tq, tl = (self._empty((int(n_iter), n, d)), self._empty((int(n_iter), n))) if trace else (None, None)
+        _abi.check(self.lib, self.lib.rsf_dr_run(self._ctx, n, d, self._ptr(q), self._ptr(l), self._ptr(data), G, _dp(_vec(lo, d, "lo")),
+                                                 _dp(_vec(hi, d, "hi")), _dp(tri), float(gamma), int(stages),
+                                                 float(0.5 * self.nout if shape is None else shape), int(seed), int(offset), int(iter0), int(n_iter),
+                                                 *(self._ptr(c) for c in counters), self._ptr(tq), self._ptr(tl)))
+        return (tq, tl) if trace else None
+
+    def dr_propose(self, q, l, lo, hi, chol, stage, gamma=0.2, pending=None, seed=0, offset=0, iteration=1):
+        """rsf_dr_propose: the proposals of one stage (1 or 2) of one iteration → (y (n, d), mask (n,) uint8).  Stage 1: every chain
+        inside the box with a finite l proposes y1; stage 2: the chains whose `pending` byte (dr_accept's of stage 1) is 1 propose
+        y2.  mask is 1 for a proposal inside the box; a chain that does not propose has y = q and mask 0.  chol (d, d), or
+        (G, d, d) with the chains split evenly over the G factors."""
+        n, d = self._dr_state(q, l)
+        L = self._dr_factors(chol, d)
+        y, mask = self._empty((n, d)), self._bytes(np.zeros(n, dtype=np.uint8))
+        pend = None if pending is None else self._bytes(pending)
+        _abi.check(self.lib, self.lib.rsf_dr_propose(self._ctx, n, d, self._ptr(q), self._ptr(l), int(L.shape[0]), _dp(_vec(lo, d, "lo")),
+                                                     _dp(_vec(hi, d, "hi")), _dp(self._dr_pack(L)), float(gamma), int(stage), int(seed), int(offset),
+                                                     int(iteration), self._ptr(pend), self._ptr(y), self._ptr(mask)))
+        return y, mask
+
+    def dr_ssq(self, y, mask, data, ssq=None):
+        """rsf_dr_ssq: the solve of one stage alone → ssq (n,), SSq of the device model at dr_propose's y (n, d) for the chains
+        whose mask is 1, in dr_run's own arrangement — the one source of SSq with which propose / accept reproduce dr_run bit for
+        bit.  The other entries are ssq's (by default 1)."""
+        self._need_model()
+        y, mask, data = self._in(y), self._bytes(mask), self._in(data)
+        if y.ndim != 2 or tuple(mask.shape) != (int(y.shape[0]),):
+            raise ValueError("y is (n, d), mask (n,)")
+        n, d = int(y.shape[0]), int(y.shape[1])
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        out = self._in(np.ones(n) if ssq is None else ssq)
+        out = out.clone() if hasattr(out, "clone") else out.copy()
+        _abi.check(self.lib, self.lib.rsf_dr_ssq(self._ctx, n, d, self._ptr(y), self._ptr(mask), self._ptr(data), G, self._ptr(out)))
+        return out
+
+    def dr_accept(self, q, l, lo, hi, stage, y, mask, ssq, counters, shape, gamma=0.2, l1=None, pending=None, seed=0, offset=0, iteration=1):
+        """rsf_dr_accept: the decision of one stage with the caller's sums of squares ssq (n,), read where mask is 1, at dr_propose's
+        y, IN PLACE in q, l and the five int32 counters.  Stage 1 → (l1 (n,), pending (n,) uint8): l(y1) (-inf outside the box) and
+        1 for the chains that go on to stage 2, which stage 2 takes back."""
+        n, d = self._dr_state(q, l, counters)
+        y, mask, ssq = self._in(y), self._bytes(mask), self._in(ssq)
+        if (tuple(y.shape), tuple(mask.shape), tuple(ssq.shape)) != ((n, d), (n,), (n,)):
+            raise ValueError(f"y is ({n}, {d}), mask and ssq ({n},)")
+        if int(stage) == 1:
+            l1, pending = self._empty((n,)), self._bytes(np.zeros(n, dtype=np.uint8))
+        else:
+            if l1 is None or pending is None:
+                raise ValueError("stage 2 takes l1 and pending of stage 1's dr_accept")
+            l1, pending = self._in(l1), self._bytes(pending)
+            if (tuple(l1.shape), tuple(pending.shape)) != ((n,), (n,)):
+                raise ValueError(f"l1 and pending are ({n},)")
+        _abi.check(self.lib, self.lib.rsf_dr_accept(self._ctx, n, d, self._ptr(q), self._ptr(l), _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")),
+                                                    float(gamma), int(stage), float(shape), int(seed), int(offset), int(iteration), self._ptr(y),
+                                                    self._ptr(mask), self._ptr(ssq), self._ptr(l1), self._ptr(pending),
+                                                    *(self._ptr(c) for c in counters)))
+        return l1, pending
+
+    def _dr_args(self, q0, lo, hi, chol, dims, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches, iter0):
+        """The checks Engine.dr and dr_from_ssq share, made before any library call → (q0 (n, d) a fresh host array, lo, hi, d,
+        chol (G or 1, d, d), n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches, iter0)"""
+        q0 = _host(q0).copy()
+        if q0.ndim == 1:
+            q0 = q0.reshape(-1, 1)
+        if q0.ndim != 2 or q0.shape[0] < 1 or q0.shape[1] not in dims:
+            raise ValueError(f"q0 has shape {q0.shape}: (n,) or (n, d) chains, d one of {dims}")
+        d = int(q0.shape[1])
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo < hi).all()):
+            raise ValueError("the box needs finite lo < hi in every parameter")
+        if not ((q0 > lo).all() and (q0 < hi).all()):
+            raise ValueError("stuck start: every chain starts strictly inside the box")
+        L = self._dr_factors(chol, d)
+        n_iter, gamma, stages, ipl, thin, adapt, iter0 = int(n_iter), float(gamma), int(stages), int(iters_per_launch), int(thin), int(adapt_launches), int(iter0)
+        keep = n_iter if keep is None else int(keep)
+        if not (math.isfinite(gamma) and 0.0 < gamma <= 1.0):
+            raise ValueError("gamma lies in (0, 1]")
+        if stages not in (1, 2):
+            raise ValueError("stages is 1 or 2")
+        if shape is not None and not (math.isfinite(float(shape)) and float(shape) > 0.0):
+            raise ValueError("shape is finite and > 0")
+        if not (n_iter >= 1 and 1 <= ipl <= _abi.DR_MAX_ITER and 0 <= keep <= n_iter and thin >= 1 and int(seed) >= 0 and int(offset) >= 0
+                and adapt >= 0 and iter0 >= 1 and iter0 + n_iter <= 2 ** 32):
+            raise ValueError(f"n_iter >= 1, iters_per_launch in [1, {_abi.DR_MAX_ITER}], 0 <= keep <= n_iter, thin >= 1, seed >= 0, offset >= 0, "
+                             "adapt_launches >= 0, iter0 >= 1 and every iteration below 2^32")
+        return q0, lo, hi, d, L, n_iter, gamma, stages, None if shape is None else float(shape), int(seed), int(offset), ipl, keep, thin, adapt, iter0
+
+    def dr_adapted_factor(self, states, lo, hi, old):
+        """The burn-in adaptation of one group: states (m, d), every state traced so far pooled over chains and iterations →
+        chol((2.38^2 / d) cov + diag((1e-6 (hi - lo))^2)), cov by pool_joint (ddof 1, as np.cov); `old` where the matrix has no
+        Cholesky factor (or cov is not finite)."""
+        d = int(states.shape[-1])
+        cov = self.pool_joint(states)["cov"]
+        M = (2.38 ** 2 / d) * cov + np.diag((1e-6 * (_vec(hi, d, "hi") - _vec(lo, d, "lo"))) ** 2)
+        try:
+            if not np.isfinite(M).all():
+                raise np.linalg.LinAlgError
+            return np.linalg.cholesky(M)
+        except np.linalg.LinAlgError:
+            return np.asarray(old, dtype=np.float64)
+
+    def _dr_result(self, q, l, counters, n_iter, kept, keep, thin, L, gamma, stages, shape, seed, offset, iter0):
+        n, d = int(q.shape[0]), int(q.shape[1])
+        tq = np.concatenate([_host(x) for x, _ in kept]) if kept else np.empty((0, n, d))
+        tl = np.concatenate([_host(x) for _, x in kept]) if kept else np.empty((0, n))
+        rows = np.arange(n_iter - keep, n_iter)[::thin]
+        pick = rows - (n_iter - tq.shape[0])  # the kept launches end at the last iteration
+        return DrResult(_host(q), _host(l), [self._ints_host(c).astype(np.int32) for c in counters], n_iter, np.ascontiguousarray(tq[pick]),
+                        np.ascontiguousarray(tl[pick]), rows + iter0, L.copy(), gamma, stages, shape, seed, offset, iter0)
+
+    def dr(self, q0, data, lo, hi, chol, n_iter, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iters_per_launch=16, keep=None, thin=1,
+           adapt_launches=0, iter0=1, l0=None):
+        """Two-stage delayed-rejection Metropolis (Mira 2001) of the device model (set_model) against `data` over the strict box
+        (lo, hi), target pi(q) ~ SSq(q)^-shape (shape: by default nout / 2): q0 (n,) or (n, d) chains inside the box, d = 1 (Dc) or
+        3 (Dc, a, b).  A chain proposes q + L z; when that is rejected — a proposal outside the box is, without a solve — it
+        proposes q + gamma L z' in the same iteration, accepted with the probability that keeps pi exact.  No gradient, no fit, no
+        other chain.  stages=1 is the plain random walk.  data (nout,), or (G, nout) with the chains split evenly over the G series
+        in order (whole workgroups each); chol (d, d) lower triangular, or (G, d, d), one factor per series.
+        The start's l comes from evidence_logtarget; a chain outside the box or without a finite l is refused (ValueError).
+        n_iter iterations on the GPU (rsf_dr_run, iters_per_launch per launch) at the Philox iterations iter0 .. iter0 + n_iter - 1.
+        adapt_launches = k: after each of the first k launches every group's factor becomes dr_adapted_factor of every state traced
+        so far; then it is frozen.  Iterations of an adapting launch are burn-in: a sample of pi is what the launches after them
+        give (MCMC.sample_dr adapts inside its burn-in only).  l0 (n,): the chains' l at q0, for a run that continues an earlier one
+        bit for bit (DrResult.q, .l and .chol, iter0 = the next Philox iteration); by default evidence_logtarget's.  keep: the
+        trailing iterations whose states are kept (None: all), every thin-th of them → DrResult."""
+        self._need_model()
+        q0, lo, hi, d, L, n_iter, gamma, stages, shape, seed, offset, ipl, keep, thin, adapt, iter0 = self._dr_args(
+            q0, lo, hi, chol, (1, 3), n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches, iter0)
+        shape = 0.5 * self.nout if shape is None else shape
+        obs = _host(data)
+        obs = obs.reshape(1, -1) if obs.ndim == 1 else obs
+        if obs.ndim != 2 or obs.shape[1] != self.nout or not 1 <= obs.shape[0] <= _abi.DR_MAX_GROUPS:
+            raise ValueError(f"data has shape {obs.shape}: (nout,) or (G, nout), G <= {_abi.DR_MAX_GROUPS}; the model produces nout = {self.nout} samples")
+        n, G = q0.shape[0], obs.shape[0]
+        if G > 1 and n % (G * self.block_threads):
+            raise ValueError(f"{n} chains cannot be split over {G} observation series in whole workgroups of {self.block_threads}")
+        L = self._dr_factors(L, d, G).copy()
+        per = n // G
+        q = self._in(q0)
+        if l0 is None:
+            l0 = np.concatenate([_host(self.evidence_logtarget(q[g * per:(g + 1) * per], obs[g], lo, hi, np.zeros(per), shape)) for g in range(G)])
+        else:
+            l0 = _host(l0).reshape(-1).copy()
+            if l0.shape != (n,):
+                raise ValueError(f"l0 holds {l0.size} values for {n} chains")
+        self._ens_refuse_stuck(l0)
+        l, obs = self._in(l0), self._in(obs)
+        counters = [self._ints(np.zeros(n)) for _ in range(5)]
+        kept, seen, done, launch = [], [], 0, 0
+        while done < n_iter:
+            k = min(ipl, n_iter - done)
+            adapting = launch < adapt
+            tr = self.dr_run(q, l, obs, lo, hi, L, k, counters, gamma=gamma, stages=stages, shape=shape, seed=seed, offset=offset, iter0=iter0 + done,
+                             trace=adapting or done + k > n_iter - keep)
+            if adapting:
+                seen.append(tr[0])
+                for g in range(G):
+                    L[g] = self.dr_adapted_factor(self._dr_pool(seen, g * per, (g + 1) * per), lo, hi, L[g])
+            if done + k > n_iter - keep:
+                kept.append(tr)
+            done += k
+            launch += 1
+        return self._dr_result(q, l, counters, n_iter, kept, keep, thin, L, gamma, stages, shape, seed, offset, iter0)
+
+    @staticmethod
+    def _dr_pool(traces, first, last):
+        """the rows first .. last - 1 of every traced iteration (k, n, d) → (m, d), contiguous, in the traces' memory space"""
+        parts = [t[:, first:last].reshape(-1, t.shape[-1]) for t in traces]
+        if isinstance(parts[0], np.ndarray):
+            return np.concatenate(parts)
+        import torch
+
+        return torch.cat(parts).contiguous()
+
+    def dr_from_ssq(self, ssq_fn, q0, lo, hi, chol, n_iter, shape, gamma=0.2, stages=2, seed=0, offset=0, keep=None, thin=1, iter0=1):
+        """dr with the caller's sum of squares: ssq_fn(points (m, d) float64 on the host) → SSq (m,), called for the start and, up to
+        twice per iteration, for the proposals of one stage that lie inside the box.  d = 1..3, no model needed; shape has no
+        default; one factor chol (d, d).  The start's l is -shape log SSq on the host; the proposals and the decisions are the
+        GPU's (rsf_dr_propose, rsf_dr_accept).  → DrResult."""
+        if shape is None:
+            raise ValueError("shape is finite and > 0")
+        q0, lo, hi, d, L, n_iter, gamma, stages, shape, seed, offset, _, keep, thin, _, iter0 = self._dr_args(
+            q0, lo, hi, chol, (1, 2, 3), n_iter, gamma, stages, shape, seed, offset, 1, keep, thin, 0, iter0)
+        if L.shape[0] != 1:
+            raise ValueError("dr_from_ssq takes one factor (d, d)")
+        n = q0.shape[0]
+
+        def ssq_at(pts):
+            s = np.asarray(ssq_fn(pts), dtype=np.float64).reshape(-1)
+            if s.size != pts.shape[0]:
+                raise ValueError(f"ssq_fn returned {s.size} values for {pts.shape[0]} points")
+            return s
+
+        def solved(y, mask):
+            inside = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(bool)
+            s = np.ones(n)
+            if inside.any():
+                s[inside] = ssq_at(_host(y)[inside])
+            return s
+
+        s0 = ssq_at(q0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            l0 = np.where(np.isfinite(s0) & (s0 > 0), -shape * np.log(s0), -np.inf)
+        self._ens_refuse_stuck(l0)
+        q, l = self._in(q0), self._in(l0)
+        counters = [self._ints(np.zeros(n)) for _ in range(5)]
+        kept = []
+        for k in range(n_iter):
+            kw = dict(gamma=gamma, seed=seed, offset=offset, iteration=iter0 + k)
+            y, mask = self.dr_propose(q, l, lo, hi, L, 1, **kw)
+            l1, pend = self.dr_accept(q, l, lo, hi, 1, y, mask, solved(y, mask), counters, shape, **kw)
+            if stages == 2:
+                y, mask = self.dr_propose(q, l, lo, hi, L, 2, pending=pend, **kw)
+                self.dr_accept(q, l, lo, hi, 2, y, mask, solved(y, mask), counters, shape, l1=l1, pending=pend, **kw)
+            if k >= n_iter - keep:
+                kept.append((_host(q).copy()[None], _host(l).copy()[None]))
+        return self._dr_result(q, l, counters, n_iter, kept, keep, thin, L, gamma, stages, shape, seed, offset, iter0)
 
     # -- the exact posterior on a tensor quadrature grid (include/rsf_grid.h) ------------------------------
     @staticmethod
