@@ -26,11 +26,11 @@ import numpy as np
 if __package__:
     from . import _figures
     from ._abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from .engine import Engine, _host, bayes_factor, whole_islands  # noqa: F401
+    from .engine import Engine, _host, bayes_factor, law_name, state_law_of, whole_islands  # noqa: F401
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     from _abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from engine import Engine, _host, bayes_factor, whole_islands  # noqa: F401
+    from engine import Engine, _host, bayes_factor, law_name, state_law_of, whole_islands  # noqa: F401
 
 
 @contextlib.contextmanager
@@ -216,7 +216,18 @@ class MCMC:
             return "am"
         return "reference_dict" if self._prior_is_dict() else "none"
 
+    def _law(self):
+        """the model's state evolution law, "aging" or "slip" """
+        return state_law_of(self.model)
+
+    def _ageing_only(self, what):
+        """`what` runs kernels that integrate the ageing law: refuse a model with another law instead of running the ageing law"""
+        if self._law() != "aging":
+            raise NotImplementedError(f"{what} integrates the ageing law only and the model's state_law is {self._law()!r}: under the slip "
+                                      "law quadrature, compare_laws, sample_smc and sample_dr run")
+
     def _init_chains(self, eng, q0, seed=0, chain_offset=0, adapt_mode=None):
+        self._ageing_only("the fused sampler (sample, sample_batched and the reference's sub-methods)")
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         # forward-difference step of the initial sensitivities: the reference's 1e-6 for its one parameter (MCMC.py:251); 1e-4 for
@@ -244,6 +255,8 @@ class MCMC:
             return np.sum((acc.reshape(1, -1) - np.asarray(self.data, dtype=np.float64).reshape(1, -1)) ** 2, axis=1, keepdims=True)
         eng = self._engine()
         dc = float(np.asarray(self.model.Dc, dtype=np.float64).reshape(-1)[0])
+        if self._law() == "slip":
+            return eng.law_ssq_fn("slip", np.asarray(self.data, dtype=np.float64).reshape(-1))([[dc]]).reshape(1, 1)
         ssq, _ = eng.forward([dc], data=np.asarray(self.data, dtype=np.float64).reshape(-1), want_ssq=True, want_acc=False)
         return ssq.reshape(1, 1)
 
@@ -322,6 +335,8 @@ class MCMC:
     def compute_initial_covariance(self):
         """std2[0] and Vstart (MCMC.py:244-266): from the device init kernel, or — for a model that is not this package's
         RateStateModel — from two `model.evaluate()` calls on the host, the reference's own steps."""
+        if self._device_model():
+            self._ageing_only("compute_initial_covariance")
         eng = self._engine()
         if self._device_model():
             self._init_chains(eng, np.array([[float(self.qstart)]]))
@@ -346,6 +361,8 @@ class MCMC:
         if self._multi_parameter():
             raise NotImplementedError("sample() is the reference's one-parameter loop (MCMC.py:98, 381); joint (Dc, a, b) chains run "
                                       "through sample_batched")
+        if self._device_model():
+            self._ageing_only("sample()")
         eng = self._engine()
         if not self._device_model():
             return self._sample_host_model(eng, MAKE_ANIMATIONS)
@@ -471,6 +488,7 @@ class MCMC:
         if not self._device_model():
             raise TypeError("sample_batched integrates the model on the device: `model` must be this package's RateStateModel "
                             "(sample() takes any model object with .Dc and .evaluate())")
+        self._ageing_only("sample_batched")
         eng = Engine(mem=mem, device=device)
         try:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
@@ -538,6 +556,14 @@ class MCMC:
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         with Engine(mem=mem, device=device) as eng:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            if self._law() == "slip":  # the split path: the GPU's weights, resampling, proposals and accept tests on law_forward's SSq
+                if int(replicates) > 1:
+                    raise NotImplementedError("sample_smc(replicates > 1) runs the batched kernels, which integrate the ageing law; the model's "
+                                              "state_law is 'slip'")
+                res = eng.smc_from_ssq(eng.law_ssq_fn("slip", data), lo, hi, int(n_particles), 0.5 * eng.nout, seed=seed, offset=offset,
+                                       ess_fraction=ess_fraction, steps=steps, max_stages=max_stages)
+                eng.sync()
+                return self._smc_pool(res)
             if int(replicates) > 1:
                 out = eng.smc_batch(data, lo, hi, int(n_particles), seeds=int(seed), offsets=int(offset), replicates=int(replicates),
                                     ess_fraction=ess_fraction, steps=steps, max_stages=max_stages)
@@ -576,6 +602,7 @@ class MCMC:
             raise ValueError(f"start is 'fit' or 'qstart', not {start!r}")
         if not self._device_model():
             raise TypeError("sample_mala integrates the model on the device: `model` must be this package's RateStateModel")
+        self._ageing_only("sample_mala")
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         q0 = np.asarray(self.qstart, dtype=np.float64).reshape(self.n_params)
@@ -641,6 +668,7 @@ class MCMC:
             raise ValueError(f"start is 'fit', 'smc' or an array of walkers, not {start!r}")
         if not self._device_model():
             raise TypeError("sample_ensemble integrates the model on the device: `model` must be this package's RateStateModel")
+        self._ageing_only("sample_ensemble")
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         d, extra = self.n_params, {}
@@ -683,7 +711,7 @@ class MCMC:
         V = _host(eng.get_state()[3]).reshape(self.n_params, self.n_params)
         return np.linalg.cholesky(V)
 
-    def sample_dr(self, n_chains, n_iter, nburn=None, start="qstart", factor="init", gamma=0.2, stages=2, adapt=True, seed=0, mem="device", device=-1,
+    def sample_dr(self, n_chains, n_iter, nburn=None, start="qstart", factor="init", gamma=0.2, stages=2, adapt=None, seed=0, mem="device", device=-1,
                   chain_offset=0, thin=1, iters_per_launch=16):
         """Two-stage delayed-rejection Metropolis (additive; Engine.dr): n_chains random-walk chains that, when their proposal
         q + L z is rejected — outside the box it is, without a forward solve — propose q + gamma L z' in the same iteration, with
@@ -693,7 +721,10 @@ class MCMC:
         FitResult.covariance(); an array (d, d): that lower triangular factor.  adapt=True: during burn-in, after every launch, L
         becomes chol(2.38^2 / d cov + eps) of every burn-in state so far, pooled over the chains (Engine.dr's adapt_launches); it is
         frozen for the kept iterations: the nburn // iters_per_launch launches that lie wholly inside the burn-in adapt.  The target is the n0 = 0 posterior
-        pi(q) ~ 1_box SSq^-N/2, sigma^2 drawn afterwards from its conditional at each kept state's own Philox iteration.  nburn:
+        pi(q) ~ 1_box SSq^-N/2, sigma^2 drawn afterwards from its conditional at each kept state's own Philox iteration.  A model with
+        state_law="slip" runs the split path (Engine.dr_from_ssq on Engine.law_forward's sums of squares): factor is then a (d, d)
+        array, start 'qstart' or an array, and nothing adapts: adapt=True raises there.  adapt=None (the default) is True under the
+        ageing law and False under the slip law; the pool's stats["adapt"] says which ran.  nburn:
         iterations dropped, by default n_iter // 2; every thin-th of the others is kept.  Returns a PosteriorPool; its stats carry
         both stages' acceptance (accepted1, accepted2, accept_rate1, accept_rate2), both out-of-box counts (out_of_bounds,
         out_of_bounds2), stuck, n_solves — the forward solves spent — and the factor in use at the end (chol)."""
@@ -710,6 +741,15 @@ class MCMC:
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         d, extra = self.n_params, {}
+        slip = self._law() == "slip"
+        if slip and adapt:
+            raise NotImplementedError("sample_dr(adapt=True) under state_law='slip': the split path (Engine.dr_from_ssq) does not adapt the "
+                                      "factor; pass adapt=False or leave it out")
+        adapt = (not slip) if adapt is None else bool(adapt)
+        extra["adapt"] = adapt
+        if slip and (isinstance(factor, str) or (isinstance(start, str) and start == "fit")):
+            raise NotImplementedError("sample_dr under state_law='slip' takes factor as a (d, d) array and start 'qstart' or an array: the init "
+                                      "kernel and the fit integrate the ageing law")
         fit = self.fit(seed=seed, device=device) if "fit" in (start if isinstance(start, str) else "", factor if isinstance(factor, str) else "") else None
         if fit is not None:
             extra["fit"] = fit
@@ -725,6 +765,12 @@ class MCMC:
                 L = self._dr_init_factor(eng, q0[0]) if factor == "init" else np.linalg.cholesky(fit.covariance())
             else:
                 L = np.asarray(factor, dtype=np.float64).reshape(d, d)
+            if slip:  # the split path on law_forward's SSq; the factor stays as given (no adaptation)
+                res = eng.dr_from_ssq(eng.law_ssq_fn("slip", data), q0, lo, hi, L, n_iter, 0.5 * eng.nout, gamma=gamma, stages=stages, seed=seed,
+                                      offset=chain_offset, keep=n_iter - nburn, thin=thin)
+                std2 = res.std2(engine=eng, kept=True)
+                eng.sync()
+                return self._dr_pool(res, std2, nburn, extra)
             res = eng.dr(q0, data, lo, hi, L, n_iter, gamma=gamma, stages=stages, seed=seed, offset=chain_offset, iters_per_launch=ipl,
                          keep=n_iter - nburn, thin=thin, adapt_launches=nburn // ipl if adapt else 0)
             std2 = res.std2(engine=eng, kept=True)
@@ -746,13 +792,39 @@ class MCMC:
         eng = Engine(mem=mem, device=device)
         try:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
-            res = eng.grid_posterior(data, lo, hi, n=n, coords=coords, window_sd=window_sd)
+            if self._law() == "slip":  # the same two stages, the nodes solved by law_forward
+                if self.n_params != 1:
+                    raise NotImplementedError("quadrature under state_law='slip' is one-parameter (Dc)")
+                res = eng.grid_posterior(data, lo, hi, n=n, coords=coords, window_sd=window_sd, ssq_fn=eng.law_ssq_fn("slip", data))
+            else:
+                res = eng.grid_posterior(data, lo, hi, n=n, coords=coords, window_sd=window_sd)
             res.q, res.std2 = res.draw(int(n_draws), seed) if int(n_draws) > 0 else (None, None)
             eng.sync()
         except BaseException:
             eng.close()
             raise
         return res
+
+    def compare_laws(self, laws=("aging", "slip"), **quadrature_kw):
+        """Ageing law or slip law?  The exact posterior of Dc under each state law by quadrature() (one parameter) and the log
+        Bayes factor between them → dict with a GridPosterior per entry of `laws` (keyed as given) and log_bayes_factor, the slip
+        law's log evidence minus the ageing law's.  quadrature_kw: quadrature's arguments.  The model's state_law is restored
+        afterwards.  Under the reference's built-in loading history the slider stays at steady state and the two laws give the
+        same series (log Bayes factor 0): the laws separate under a velocity-step or slide-hold-slide history (model.loading)."""
+        if self._multi_parameter():
+            raise NotImplementedError("compare_laws is one-parameter (Dc)")
+        if sorted(law_name(law) for law in laws) != ["aging", "slip"]:
+            raise ValueError(f"laws names the ageing and the slip law once each, not {laws!r}")
+        before, out, ev = getattr(self.model, "state_law", "aging"), {}, {}
+        try:
+            for law in laws:
+                self.model.state_law = law
+                out[law] = self.quadrature(**quadrature_kw)
+                ev[self._law()] = out[law].log_evidence
+        finally:
+            self.model.state_law = before
+        out["log_bayes_factor"] = ev["slip"] - ev["aging"]
+        return out
 
     def _fit_starts(self, eng, n_starts, seed):
         """start 0 is qstart, the others rsf_smc_init's uniform start in the prior box (seed, particles 0 .. n_starts - 2)"""
@@ -773,6 +845,7 @@ class MCMC:
         Dc a are reproducible.  kw: Engine.fit's fd_rel_step, ftol, max_iter, iters_per_launch."""
         if not self._device_model():
             raise TypeError("fit integrates the model on the device: `model` must be this package's RateStateModel")
+        self._ageing_only("fit")
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         with Engine(mem=mem, device=device) as eng:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))

@@ -6,14 +6,16 @@ solve runs on the GPU through the C ABI (rsf_forward_batch) as a fixed-step RK4 
 (`substeps` steps per output interval) instead of the reference's SciPy dop853 call.  DESIGN.md
 states the resulting tolerance ladder against the reference trajectory.
 
-Additive surface: `substeps`, `precision`, `integrator`, `evaluate_batch(dc, a=None, b=None)`.
+Additive surface: `substeps`, `precision`, `integrator`, `loading`, `state_law`, `evaluate_batch(dc, a=None, b=None)`.
 """
+import zlib
+
 import numpy as np
 
 if __package__:
-    from .engine import Engine
+    from .engine import Engine, check_law_options
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
-    from engine import Engine
+    from engine import Engine, check_law_options
 
 # RateStateModel.py:5-11
 A = 0.011
@@ -47,13 +49,26 @@ class RateStateModel:
         self.substeps = 1  # RK4 steps per delta_t (additive knob; 1 = BASELINE's "fixed-step RK4 nsteps")
         self.precision = "float64"  # additive: "float32" integrates the ODE in single precision (tolerance sweeps)
         self.integrator = "rk4"     # additive: "dop853" = the reference's own adaptive scheme (scipy ode, rtol 1e-6, atol 1e-10)
+        # additive: the loading history V_l(t) — None (the reference's V_ref (1 + exp(-t/20) sin 10t)), a callable t -> V_l
+        # (vectorised over the RK4 stage times) or an array of one value per stage time (Engine.loading_times()) — and the
+        # state evolution law, "aging" (the reference's; "ageing" is accepted) or "slip".  float64 RK4 only
+        self.loading = None
+        self.state_law = "aging"
         self._engine = None
         self._engine_key = None
 
     # ---- engine plumbing ----------------------------------------------------------------
+    def _loading_key(self):
+        """what re-arms the engine when the loading changes: a callable by identity, an array by its values"""
+        if self.loading is None or callable(self.loading):
+            return self.loading if self.loading is None else id(self.loading)
+        v = np.ascontiguousarray(np.asarray(self.loading, dtype=np.float64))
+        return (v.shape, zlib.crc32(v.tobytes()))
+
     def _model_key(self):
         return (self.a, self.b, self.mu_ref, self.V_ref, self.k1, self.t_start, self.t_final, self.num_tsteps, self.delta_t,
-                self.mu_t_zero, bool(self.RadiationDamping), int(self.substeps), self.precision, self.integrator)
+                self.mu_t_zero, bool(self.RadiationDamping), int(self.substeps), self.precision, self.integrator, self._loading_key(),
+                self.state_law)
 
     def engine(self):
         """Host-memory Engine bound to the HIP library, re-armed when an attribute changed."""
@@ -83,7 +98,7 @@ class RateStateModel:
         (RateStateModel.py:392), so a seeded caller sees the reference's draw order."""
         if self.Dc is None:
             raise ValueError("RateStateModel.Dc must be set before evaluate()")
-        _, acc = self.engine().forward([_scalar(self.Dc)], want_acc=True)
+        _, acc = self._forward([_scalar(self.Dc)])
         acc = np.ascontiguousarray(acc[:, 0])
         acc_noise = acc + 1.0 * np.abs(acc) * np.random.randn(acc.shape[0])
         return self.time_axis(), acc, acc_noise
@@ -91,5 +106,12 @@ class RateStateModel:
     # ---- batched surface (additive) -----------------------------------------------------
     def evaluate_batch(self, dc, a=None, b=None):
         """Clean acceleration for C parameter sets in one launch → ndarray (C, nout)."""
-        _, acc = self.engine().forward(np.asarray(dc, dtype=np.float64).reshape(-1), a=a, b=b, want_acc=True)
+        _, acc = self._forward(np.asarray(dc, dtype=np.float64).reshape(-1), a=a, b=b)
         return np.ascontiguousarray(acc.T)
+
+    def _forward(self, dc, a=None, b=None):
+        """the clean series under the model's loading history and state law: the tier kernels (rsf_forward_batch) for the ageing
+        law, the plain float64 RK4 of rsf_law_forward for the slip law"""
+        if check_law_options(self) == "slip":
+            return self.engine().law_forward("slip", dc, a=a, b=b, want_acc=True)
+        return self.engine().forward(dc, a=a, b=b, want_acc=True)

@@ -313,6 +313,15 @@ GRID_COORDS = {"plain": GRID_PLAIN, "product": GRID_PRODUCT}
 GRID_FIELDS = ("s0", "s1", "s2", "ssq", "ssq2", "n_neginf")
 GRID_HEAD = 20
 GRID_HEAD_SCALARS = {"Z": 0, "log_integral": 1, "log_evidence": 2, "n_neginf": 3, "x0_mean": 16, "x0_var": 17, "std2_mean": 18, "std2_var": 19}
+# include/rsf_law.h: the caller's loading history and the state law; exported by librsf_hip.so only, bound by load()
+LAW_PROTOTYPES = {
+    "rsf_set_loading": (c_int, [c_void_p, _DP, c_int64]),
+    "rsf_get_loading": (c_int, [c_void_p, _DP, c_int64]),
+    "rsf_loading_size": (c_int, [c_void_p, _I64P]),
+    "rsf_law_forward": (c_int, [c_void_p, c_int32, c_int64, _P, _P, _P, _P, _P, _P]),
+}
+LAW_AGEING, LAW_SLIP = 0, 1  # RSF_LAW_AGEING, RSF_LAW_SLIP
+LAWS = {"aging": LAW_AGEING, "ageing": LAW_AGEING, "slip": LAW_SLIP}
 MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
 
 
@@ -361,7 +370,7 @@ def load():
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
                       SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
-                      DR_PROTOTYPES):
+                      DR_PROTOTYPES, LAW_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -111,6 +111,21 @@ int first_bad_prob(int n, const double *probs) {
   return -1;
 }
 
+void free_chains(rsf_ctx *c) {
+  release(c->data); release(c->q); release(c->ssq); release(c->std2); release(c->V);
+  release(c->wref); release(c->wsum); release(c->wsq); release(c->wn); release(c->wbuf); release(c->stats);
+  c->have_chains = false;
+  c->external_chains = false;
+}
+
+// chain-independent loading velocity at every RK4 stage time, RateStateModel.py:327-329
+void builtin_loading(const rsf_model &m, double hh, double *vl, size_t n) {
+  for (size_t j = 0; j < n; ++j) {
+    const double t = m.t_start + (double)j * hh;
+    vl[j] = m.V_ref * (1 + std::exp(-t / 20) * std::sin(10 * t));
+  }
+}
+
 }  // namespace rsfh
 
 namespace {
@@ -159,13 +174,6 @@ int put_q_V(rsf_ctx *c, int64_t C, int d, const double *q, const double *V) {
   if (q && (rc = transpose(c, C, d, dq, (double *)c->q.p, true))) return rc;
   if (V && (rc = transpose(c, C, d * d, dV, (double *)c->V.p, true))) return rc;
   return RSF_OK;
-}
-
-void free_chains(rsf_ctx *c) {
-  release(c->data); release(c->q); release(c->ssq); release(c->std2); release(c->V);
-  release(c->wref); release(c->wsum); release(c->wsq); release(c->wn); release(c->wbuf); release(c->stats);
-  c->have_chains = false;
-  c->external_chains = false;
 }
 
 // RK4 table chunk: the output intervals kc whose (2*S*kc + 1) loading values + kc observations + the observation's sample
@@ -285,12 +293,8 @@ int rsf_set_model(rsf_ctx *c, const rsf_model *m) {
   } else {
     kc = rk4_chunk_len((int64_t)words, S, nout, m->flags & RSF_FLAG_FP32_SOLVE);
     if (kc < 1) return fail(RSF_ERR_UNSUPPORTED, "rsf_set_model: substeps=%d does not fit the LDS staging budget", S);
-    // chain-independent loading velocity at every RK4 stage time, RateStateModel.py:327-329
     vl.resize(2 * (size_t)S * (size_t)(nout - 1) + 1);
-    for (size_t j = 0; j < vl.size(); ++j) {
-      const double t = m->t_start + (double)j * hh;
-      vl[j] = m->V_ref * (1 + std::exp(-t / 20) * std::sin(10 * t));
-    }
+    builtin_loading(*m, hh, vl.data(), vl.size());
   }
   const size_t nvl = vl.size();
   if ((rc = ensure(c->vl, nvl * sizeof(double)))) return rc;

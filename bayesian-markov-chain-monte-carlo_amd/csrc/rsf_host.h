@@ -224,6 +224,10 @@ bool damped(const rsf_ctx *c, int mode);
 int chains_per_lane(const rsf_ctx *c);
 // the first probability outside [0, 1] (NaN included), or -1
 int first_bad_prob(int n, const double *probs);
+// the chains' state goes with the model, or the loading history (rsf_law.hip), they were made under
+void free_chains(rsf_ctx *c);
+// the built-in loading history V_ref (1 + exp(-t / 20) sin 10 t) at t_start + j hh, j = 0 .. n - 1 (rsf_set_model's RK4 table)
+void builtin_loading(const rsf_model &m, double hh, double *vl, size_t n);
 // what rsf_destroy frees of the other units' state: the replay graph (rsf_sampler.hip), the communicator (rsf_comm.hip)
 void release_replay_graph(rsf_ctx *c);
 void release_comm(rsf_ctx *c);

@@ -128,6 +128,30 @@ def _model_struct(model, substeps):
     return m
 
 
+def law_name(law):
+    """'aging' or 'slip' of a state law's name ('ageing' is accepted)"""
+    if not isinstance(law, str) or law not in _abi.LAWS:
+        raise ValueError(f"state_law is 'aging' (or 'ageing') or 'slip', not {law!r}")
+    return "slip" if _abi.LAWS[law] == _abi.LAW_SLIP else "aging"
+
+
+def state_law_of(model):
+    """The model's state evolution law, "aging" (the default) or "slip"."""
+    return law_name(getattr(model, "state_law", "aging"))
+
+
+def check_law_options(model):
+    """The slip law and a caller's loading history run the float64 RK4 only → the model's law."""
+    law = state_law_of(model)
+    integrator, precision = getattr(model, "integrator", "rk4"), getattr(model, "precision", "float64")
+    for what, on in ((f"state_law={law!r}", law == "slip"), ("a custom loading history", getattr(model, "loading", None) is not None)):
+        if on and integrator == "dop853":
+            raise NotImplementedError(f"{what} with integrator='dop853': the adaptive steps evaluate the built-in history and the ageing law")
+        if on and precision == "float32":
+            raise NotImplementedError(f"{what} with precision='float32': the float32 solve runs the built-in history and the ageing law")
+    return law
+
+
 def _pop_array(x, P, dtype, what):
     """x, a scalar or P values, as a contiguous (P,) array of dtype: one entry per SMC population."""
     x = np.asarray(x)
@@ -596,6 +620,7 @@ class Engine:
         self._ctx = ctypes.c_void_p()
         _abi.check(lib, lib.rsf_create(ctypes.byref(cfg), ctypes.byref(self._ctx)))
         self.nout = None
+        self.state_law = "aging"  # the model's (set_model)
         self.n_chains = self.n_params = None
         self.world = self.rank = 0  # set by comm_init
 
@@ -644,18 +669,112 @@ class Engine:
 
     # -- forward model --------------------------------------------------------------------
     def set_model(self, model, substeps=1):
+        """rsf_set_model, then the model's own loading history (model.loading, if it has one: set_loading).  model.state_law
+        is kept as self.state_law: the kernels of every family integrate the ageing law, so with 'slip' only law_forward and
+        the calls built on it run (_need_model)."""
+        law = check_law_options(model)
         m = _model_struct(model, substeps)
         _abi.check(self.lib, self.lib.rsf_set_model(self._ctx, ctypes.byref(m)))
         n = ctypes.c_int32()
         _abi.check(self.lib, self.lib.rsf_model_nout(self._ctx, ctypes.byref(n)))
         self.nout = n.value
         self.model_args = (model, substeps)
+        self.state_law = law
         self.n_chains = self.n_params = None  # a new model invalidates the chains (rsf_abi.h: rsf_set_model)
+        if getattr(model, "loading", None) is not None:
+            try:
+                self.set_loading(model.loading)
+            except BaseException:
+                self.nout = None  # no model rather than this one under the built-in history: every call asks for set_model again
+                raise
         return self.nout
 
-    def _need_model(self):
+    def _need_model(self, law_aware=False):
         if self.nout is None:
             raise _abi.RsfError(-3, "call set_model first")
+        if not law_aware and getattr(self, "state_law", "aging") != "aging":
+            raise NotImplementedError(f"this call integrates the ageing law only, and the model's state_law is {self.state_law!r}: "
+                                      "the slip law runs through law_forward and the calls that take an ssq_fn")
+
+    # -- the loading history and the state law (include/rsf_law.h) ---------------------------------------
+    def _law_fn(self, name):
+        """a function of include/rsf_law.h, which librsf_hip.so alone exports"""
+        try:
+            return getattr(self.lib, name)
+        except AttributeError:
+            raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
+                                    "symbol (include/rsf_law.h)") from None
+
+    def loading_size(self):
+        """the loading table's length, 2 substeps (nout - 1) + 1"""
+        self._need_model(law_aware=True)
+        n = ctypes.c_int64()
+        _abi.check(self.lib, self._law_fn("rsf_loading_size")(self._ctx, ctypes.byref(n)))
+        return n.value
+
+    def loading_times(self):
+        """the RK4 stage times t_start + j (delta_t / substeps) / 2 of the loading table, as rsf_set_model forms them"""
+        self._need_model(law_aware=True)
+        model, substeps = self.model_args
+        hh = 0.5 * (((float(model.t_final) - float(model.t_start)) / int(model.num_tsteps)) / int(substeps))
+        return float(model.t_start) + np.arange(2 * int(substeps) * (self.nout - 1) + 1, dtype=np.float64) * hh
+
+    def set_loading(self, values):
+        """rsf_set_loading: the loading history V_l of every float64 RK4 solve from here on, until the next set_model.  values: an
+        array of loading_size() values at loading_times(), a callable t -> V_l (called once with loading_times()), or None for the
+        built-in history.  The chains of an earlier mcmc_init are discarded."""
+        self._need_model(law_aware=True)
+        v = None
+        if values is not None:
+            t = self.loading_times()
+            v = values(t) if callable(values) else values
+            v = np.ascontiguousarray(np.asarray(v.cpu() if hasattr(v, "cpu") else v, dtype=np.float64))
+            if v.shape != t.shape:
+                raise ValueError(f"the loading history has shape {v.shape}: one value per RK4 stage time, {t.shape} (loading_times())")
+            if not np.isfinite(v).all():
+                raise ValueError("the loading history holds a value that is not finite")
+        _abi.check(self.lib, self._law_fn("rsf_set_loading")(self._ctx, None if v is None else _dp(v), 0 if v is None else v.size))
+        self.n_chains = self.n_params = None
+
+    def loading(self):
+        """rsf_get_loading: the loading table in use → (loading_size(),) on the host"""
+        v = np.empty(self.loading_size())
+        _abi.check(self.lib, self._law_fn("rsf_get_loading")(self._ctx, _dp(v), v.size))
+        return v
+
+    def law_forward(self, law, dc, a=None, b=None, data=None, want_ssq=False, want_acc=True):
+        """rsf_law_forward: forward's arguments and results, → (ssq[C] | None, acc[nout, C] | None), under the state law `law`
+        ('aging', 'ageing' or 'slip'; an integer goes to the library as it is) and the loading table in use, by the plain float64
+        RK4 with a full evaluation at every stage."""
+        self._need_model(law_aware=True)
+        if isinstance(law, str):
+            if law not in _abi.LAWS:
+                raise ValueError(f"law is 'aging' (or 'ageing') or 'slip', not {law!r}")
+            law = _abi.LAWS[law]
+        dc = self._in(np.atleast_1d(dc) if not hasattr(dc, "data_ptr") else dc)
+        C = int(dc.shape[0])
+        a, b, data = self._in(a), self._in(b), self._in(data)
+        if want_ssq and data is None:
+            raise ValueError("want_ssq needs data")
+        if data is not None and int(data.shape[0]) != self.nout:
+            raise ValueError(f"data has {int(data.shape[0])} entries, the model produces {self.nout}")
+        ssq = self._empty((C,)) if want_ssq else None
+        acc = self._empty((self.nout, C)) if want_acc else None
+        _abi.check(self.lib, self._law_fn("rsf_law_forward")(self._ctx, int(law), C, self._ptr(dc), self._ptr(a), self._ptr(b), self._ptr(data), self._ptr(ssq), self._ptr(acc)))
+        return ssq, acc
+
+    def law_ssq_fn(self, law, data):
+        """The ssq_fn of smc_from_ssq, dr_from_ssq, grid_from_ssq and grid_posterior for the device model under `law`: points
+        (m, 1) of Dc or (m, 3) of (Dc, a, b) on the host → SSq (m,) on the host, solved by law_forward."""
+        obs = self._in(data)
+
+        def ssq_fn(pts):
+            pts = np.asarray(pts, dtype=np.float64)
+            pts = pts.reshape(-1, 1) if pts.ndim < 2 else pts
+            ab = [np.ascontiguousarray(pts[:, p]) for p in (1, 2)] if pts.shape[1] == 3 else [None, None]
+            return _host(self.law_forward(law, np.ascontiguousarray(pts[:, 0]), ab[0], ab[1], data=obs, want_ssq=True, want_acc=False)[0])
+
+        return ssq_fn
 
     def _need_chains(self):
         if self.n_chains is None:
@@ -2565,25 +2684,43 @@ class Engine:
         l, ssq = ltarget(q, jac)
         return self._grid_result(xs, w, l, ssq, lo, hi, shape, c, lambda pts: self._in(ltarget(_host(pts))[0]), outside, int(np.isfinite(ssq).sum()))
 
-    def grid_posterior(self, data, lo, hi, n=None, coords=None, window_sd=12.0, shape=None, n_coarse=None):
+    def grid_posterior(self, data, lo, hi, n=None, coords=None, window_sd=12.0, shape=None, n_coarse=None, ssq_fn=None):
         """The exact posterior of the device model (set_model) given `data` over the closed box [lo, hi], d = 1 (Dc) or 3 (Dc, a, b),
         by quadrature on the GPU in two stages (the procedure of the test-suite's reference quadrature).  A coarse scan of the whole
         box — d = 1: n_coarse (4001) linearly and as many logarithmically spaced nodes strictly inside, trapezoid weights; d = 3: a
         coarse axis (801 + 801) in Dc a at the first, middle and last (a, b) nodes — finds the mass: the window is mean +- window_sd
         SD (of the widest column at d = 3), clipped to the box, and `outside` the coarse mass beyond it.  The fine grid: d = 1,
         n = (4001,) Simpson nodes on the window; d = 3, n = (2001, 65, 65): coords 'product' (axis 0 is Dc a, which straightens the
-        ridge Dc a = const), axes 1 and 2 uniform over [lo, hi] with the faces, Simpson on every axis (odd n).  → GridPosterior."""
-        self._need_model()
+        ridge Dc a = const), axes 1 and 2 uniform over [lo, hi] with the faces, Simpson on every axis (odd n).  → GridPosterior.
+        ssq_fn (d = 1 only; data is then not read): the same two stages with the nodes' sums of squares from the caller — ssq_fn(points
+        (m, 1) float64 on the host) → SSq (m,), as grid_from_ssq calls it; law_ssq_fn(law, data) makes one for either state law."""
+        self._need_model(law_aware=ssq_fn is not None)
         blo, bhi, d = self._smc_box(lo, hi)
         if d not in (1, 3):
             raise ValueError("the box has d = 1 (Dc) or 3 (Dc, a, b) parameters")
+        if ssq_fn is not None and d != 1:
+            raise NotImplementedError("grid_posterior takes an ssq_fn at d = 1 only (d = 3: grid_from_ssq on the caller's grid)")
         shape = 0.5 * self.nout if shape is None else float(shape)
         n = ((4001,) if d == 1 else (2001, 65, 65)) if n is None else tuple(int(v) for v in np.atleast_1d(n))
         if len(n) != d or any(v < 3 or v % 2 == 0 for v in n):
             raise ValueError(f"n holds {d} odd node counts >= 3 (composite Simpson)")
         c = self._grid_coords(("product" if d == 3 else "plain") if coords is None else coords, d)
-        obs = self._in(data)
-        ltarget = lambda pts: self.evidence_logtarget(pts, obs, blo, bhi, self._in(np.zeros(int(math.prod(pts.shape)) // d)), shape)
+        if ssq_fn is None:
+            obs = self._in(data)
+            ltarget = lambda pts: self.evidence_logtarget(pts, obs, blo, bhi, self._in(np.zeros(int(math.prod(pts.shape)) // d)), shape)
+            nodes = lambda x: self.grid_logtarget(x, obs, blo, bhi, c, shape)
+        else:
+            def host_target(pts):  # grid_from_ssq's: -inf outside the closed box and where SSq is not finite and > 0
+                pts = np.asarray(pts, dtype=np.float64).reshape(-1, 1)
+                inb = ((pts >= blo) & (pts <= bhi)).all(axis=1)
+                s = np.full(pts.shape[0], np.nan)
+                if inb.any():
+                    s[inb] = np.asarray(ssq_fn(pts[inb]), dtype=np.float64).reshape(-1)
+                ok = inb & np.isfinite(s) & (s > 0)
+                return np.where(ok, -shape * np.log(np.where(ok, s, 1.0)), -np.inf), s
+
+            ltarget = lambda pts: self._in(host_target(_host(pts))[0])
+            nodes = lambda x: tuple(self._in(v) for v in host_target(x[0]))
         nc = (4001 if d == 1 else 801) if n_coarse is None else int(n_coarse)
         prod = c == _abi.GRID_PRODUCT
         alo, ahi = (blo[0] * blo[1], bhi[0] * bhi[1]) if prod else (blo[0], bhi[0])  # the range of axis 0
@@ -2597,7 +2734,7 @@ class Engine:
         fine = [_simpson_axis(blo[p], bhi[p], n[p]) for p in range(1, d)]
         sel = [a[0][[0, a[0].size // 2, a[0].size - 1]] for a in fine]
         cx, cw = [xc] + sel, [wc] + [np.ones(3)] * (d - 1)
-        l, ssq = self.grid_logtarget(cx, obs, blo, bhi, c, shape)
+        l, ssq = nodes(cx)
         col = self.grid_columns(cx, cw, l, ssq, m0=False, cum0=False)
         f = col["fields"]
         if not (f[:, 0] > 0).any():
@@ -2613,7 +2750,7 @@ class Engine:
         outside = float(((wc * e)[:, out].sum(axis=1)[ok] / f[ok, 0]).max()) if out.any() else 0.0
         x0 = _simpson_axis(wlo, whi, n[0])
         xs, ws = [x0[0]] + [a[0] for a in fine], [x0[1]] + [a[1] for a in fine]
-        l, ssq = self.grid_logtarget(xs, obs, blo, bhi, c, shape)
+        l, ssq = nodes(xs)
         return self._grid_result(xs, ws, l, ssq, blo, bhi, shape, c, ltarget, outside, int(xc.size * 3 ** (d - 1) + math.prod(n)))
 
     # -- convergence diagnostics of a kept trace (include/rsf_diag.h) --------------------------
