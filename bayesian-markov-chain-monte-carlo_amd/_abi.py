@@ -26,7 +26,7 @@ MAX_PARAMS = 3
 ERR_NOT_POSDEF = -6
 # rsf_mcmc_counters: index = RSF_CNT_* of include/rsf_abi.h
 COUNTERS = ("accepted", "evaluated", "nonfinite", "out_of_bounds", "early_rejected", "wave_solves", "wave_skips",
-            "steps_tight", "steps_narrow", "steps_wide", "steps_full", "steps_redone", "lane_steps")
+            "steps_tight", "steps_narrow", "steps_wide", "steps_full", "steps_redone", "lane_steps", "steps_unguarded")
 
 
 class RsfError(RuntimeError):

@@ -38,6 +38,8 @@ struct Consts {
   int32_t S;                      // RK4 steps per output interval
   int32_t kc;                     // output intervals per LDS chunk
   int32_t nchunks;                // ceil((nout-1)/kc); 1 => tables stay resident in LDS
+  double vl_lo, vl_hi;            // smallest and largest value of vl over the whole series (the host's, where it writes the table):
+                                  //   what tight_needs_guard knows of the loading.  Last, so that no other field moves.
 };
 
 // select the observation series of this workgroup (all its chains belong to one group)
@@ -318,17 +320,22 @@ __device__ __forceinline__ double rk4_cold(State &s, double vl0, double vlm, dou
 // SHORT (the in-step mode's half-step stages, TIGHT): expm1 to dlt^3/6.  Their w is a stage value, not the carried state: at
 // the stage guard's edge, |dlt| = 2^-10, the dropped dlt^4/24 is 3.8e-14 of it, which reaches the step's sample with weight 1/3
 // and the carried state through another factor |dlt|; at the increments of a Dc ~ 1000 chain (|dlt| ~ 1e-4) it is 4e-18.
-template <int T, bool HALF, bool SHORT = false>
+// GUARD = false (all three functions of the step): the Guard updates are compiled out — the arithmetic of the step is the same
+// instruction for instruction; for a trip whose start state proves that no increment can reach a threshold (tight_needs_guard).
+template <int T, bool HALF, bool SHORT = false, bool GUARD = true>
 __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L, double w0, double &w, double &q, Guard &g) {
   static_assert(!SHORT || (T == TIGHT && HALF), "the short series is for TIGHT's half-step stages");
-  g.rho = __builtin_fmaxf(g.rho, __builtin_fabsf(hi_as_float(rho)));
+  static_assert(GUARD || T == TIGHT, "only TIGHT has an a-priori bound");
+  if constexpr (GUARD) g.rho = __builtin_fmaxf(g.rho, __builtin_fabsf(hi_as_float(rho)));
   double pb = L.nhboa;  // (b/a)(1 - rho/2 [+ rho^2/3 [- rho^3/4]])
   if (T == NARROW) pb = __builtin_fma(rho, L.c_l1p, pb);
   if (T == WIDE) pb = __builtin_fma(rho, __builtin_fma(rho, L.c_l1q, L.c_l1p), pb);
   const double dlt = __builtin_fma(-rho, __builtin_fma(rho, pb, L.boa), dk);
   // TIGHT: expm1 to dlt^4/24 at every stage, half-step stages held to |dlt| < 2^-10, the others to 2^-9
-  if (T == TIGHT && HALF) g.dlt_h = __builtin_fmaxf(g.dlt_h, __builtin_fabsf(hi_as_float(dlt)));
-  else g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
+  if constexpr (GUARD) {
+    if (T == TIGHT && HALF) g.dlt_h = __builtin_fmaxf(g.dlt_h, __builtin_fabsf(hi_as_float(dlt)));
+    else g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
+  }
   double e = SHORT ? 1.0 / 6.0 : L.c_em1;
   if (T == WIDE) {
     e = fm::hfma(e, dlt, 1.0 / 5040.0);
@@ -351,10 +358,11 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
 // TIGHT's full-step stage fed with c1 = rho / 2, the previous stage's d1' as it stands (the in-step mode): the doublings are
 // exact, so dlt and w are tight_incr<TIGHT, false>(c1 + c1, ...)'s to the bit; brx = bh (1 + q) comes out of one Horner
 // pass in c1 instead of q and a product (one rounding placed differently), and the sum c1 + c1 is never formed.
+template <bool GUARD = true>
 __device__ __forceinline__ void tight_incr_doubled(double c1, double dk, const Lane &L, double w0, double &w, double &brx, Guard &g) {
-  g.rho_f = __builtin_fmaxf(g.rho_f, __builtin_fabsf(hi_as_float(c1)));
+  if constexpr (GUARD) g.rho_f = __builtin_fmaxf(g.rho_f, __builtin_fabsf(hi_as_float(c1)));
   const double dlt = __builtin_fma(-c1, __builtin_fma(-c1, L.boa2, L.boa2), dk);
-  g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
+  if constexpr (GUARD) g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
   double e = fm::hfma(L.c_em1, dlt, 1.0 / 6.0);
   e = __builtin_fma(e, dlt, 0.5);
   e = __builtin_fma(e, dlt, 1.0);
@@ -385,24 +393,25 @@ __device__ __forceinline__ void rhs_tight(double w, double xr, double Rh, double
 // *ssq itself (`first`: starts that sum), r = cv sv + (2 cv sm - obs), and returns nothing of use — no per-step sample leaves the step, so a trip keeps
 // neither its samples nor, beyond each step, its observations in registers.  Its half-step stages take the expm1 series
 // one term shorter (tight_incr, SHORT) and its full-step stage the half increment (tight_incr_doubled).
-template <bool DAMP, int T, bool INSTEP = false>
+template <bool DAMP, int T, bool INSTEP = false, bool GUARD = true>
 __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, double vl1, const Lane &L, const Consts &K, Guard &g,
                                             double obs = 0.0, double *ssq = nullptr, bool first = false) {
   static_assert(!INSTEP || T == TIGHT, "the in-step sum of squares is the TIGHT step's");
+  static_assert(GUARD || INSTEP, "the unguarded step is the in-step mode's");
   double a0, a1, a2, b0, b1, b2, c0, c1, c2, e0, e1, e2, w, q;
   const double Rh = s.rx;
   const double vr = L.vrw, xh = L.hhdw, xf = L.hdw;  // (V_ref, hhd, hd) / kvk with damping: s.w is W (Lane::vrw)
   rhs_tight<DAMP>(s.w, xh, Rh, vl0, L.bh, vr, a0, a1, a2);
   double sv = s.w * a2;  // k1 + k4 of dV/dt (in units of vk, vk/kvk with damping), and k2 + k3 below: 5 instructions for the weighted sum
-  tight_incr<T, true, INSTEP>(a1, L.khh * a0, L, s.w, w, q, g);
+  tight_incr<T, true, INSTEP, GUARD>(a1, L.khh * a0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, a1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, b0, b1, b2);
   double sm = w * b2;
-  tight_incr<T, true, INSTEP>(b1, L.khh * b0, L, s.w, w, q, g);
+  tight_incr<T, true, INSTEP, GUARD>(b1, L.khh * b0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, b1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, c0, c1, c2);
   sm = __builtin_fma(w, c2, sm);
   if constexpr (INSTEP) {
     double brx;
-    tight_incr_doubled(c1, L.kh * c0, L, s.w, w, brx, g);
+    tight_incr_doubled<GUARD>(c1, L.kh * c0, L, s.w, w, brx, g);
     rhs_tight<DAMP>(w, __builtin_fma(xf, c1, xh), Rh, vl1, brx, vr, e0, e1, e2);
   } else {
     tight_incr<T, false>(c1 + c1, L.kh * c0, L, s.w, w, q, g);
@@ -412,7 +421,7 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
   const double t0 = a0 + 2.0 * b0 + 2.0 * c0 + e0;
   const double t1 = a1 + 2.0 * b1 + 2.0 * c1 + e1;
   const double rho = t1 * (1.0 / 3.0);  // (h/6Dc)/x times the unscaled sum
-  tight_incr<T, false>(rho, L.kh6 * t0, L, s.w, w, q, g);
+  tight_incr<T, false, false, GUARD>(rho, L.kh6 * t0, L, s.w, w, q, g);
   s.ms = __builtin_fma(K.h6, t0, s.ms);
   s.w = w;
   s.rx = __builtin_fma(Rh, q, Rh);  // x' = x (1 + rho), exact to rounding for |rho| < 2^-20; like w, resynced
@@ -590,6 +599,24 @@ struct Wave {
   // statistics of this solve (rsf_mcmc_counters): wave-steps per tier, wave-steps of fast trips thrown away by a tripped
   // guard, and the sum over steps of the number of alive lanes (lane utilisation = lane_steps / (64 * all steps))
   uint32_t steps[4], redone, lane_steps;
+  // Consts::vl_lo / vl_hi as scalars of their own (wave_begin), for tight_needs_guard.  Read from K at every trip they kept the
+  // 16-dword kernel-argument tuple that holds them live through the TIGHT loop: the compiler spilled the tuple and reloaded 16
+  // scalars per trip (22 lane moves in the loop; 6 with the copies).
+  double vl_lo, vl_hi;
+  // lanes that tight_needs_guard cannot be expected to free at any trip of this solve (wave_begin): while one of them is alive the
+  // wave does not evaluate the bound at all.  At one wave per SIMD a trip waits out the bound's whole dependency chain and the
+  // branch on it: +1.9 % at configs[1] (h = 0.1, Dc ~ 1000: the bound never holds there), nothing with this mask.
+  unsigned long long never;
+  bool guard_next;  // the bound just failed at this trip: one guarded trip before it is asked again (integrate_multi, UNGUARD)
+  uint32_t unguarded;  // the wave-steps among steps[TIGHT] whose trip ran without the guard (tight_needs_guard)
+};
+
+// the constants of tight_needs_guard, for trips of NU steps
+template <int NU>
+struct TightBound {
+  static constexpr double R = 0x1.0p-20, B = 0x1.0p-21, Dmax = 0.9 * 0x1.0p-9, gm1 = 1.02 * NU * Dmax;
+  static constexpr double G = 1.02 * NU, kap = (NU + 1) * R, Bmax = 0.9 * B;
+  static_assert(NU * Dmax < 0.035, "exp(x) - 1 <= 1.02 x needs x < 0.035");
 };
 
 __device__ __forceinline__ unsigned long long ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
@@ -604,8 +631,18 @@ __device__ __forceinline__ double dpp_move(double v) {
 }
 
 // (the statistics members are the caller's to zero: they accumulate over the solves of a launch)
+// NU: steps per whole TIGHT trip of the solve (W.never)
+template <int NU>
 __device__ __forceinline__ void wave_begin(Wave &W, bool active, const Lane &L, const Consts &K) {
   const double dk = 1.2 * K.V_ref * K.h * L.kia;
+  // W.never: what tight_needs_guard's two figures are AT LEAST, whatever the state — |V_l - v| ranges over half the table's range
+  // or more, and Rh0 = hhd / x — taken at x = 1, the steady state at V_ref.  (A gate on speed alone: a lane it names keeps the
+  // guard, which is always right; a lane it misses fails the bound itself.)
+  using TB = TightBound<NU>;
+  const double dmin = __builtin_fma(__builtin_fabs(L.kh), 0.5 * (K.vl_hi - K.vl_lo), __builtin_fabs(L.boa) * TB::R);
+  const double rmin = __builtin_fabs(L.hhd) * __builtin_fma(dmin, TB::G, TB::kap);
+  W.never = ballot(active && !(dmin < TB::Dmax && rmin < TB::Bmax));
+  W.guard_next = false;
   W.alive = ballot(active);
   W.need[0] = ballot(active && !(dk < 0x1.0p-9));
   W.need[1] = ballot(active && !(dk < 0x1.0p-7));
@@ -613,6 +650,9 @@ __device__ __forceinline__ void wave_begin(Wave &W, bool active, const Lane &L, 
   W.next_resync = kResync;
   W.full_run = 0;
   W.calm = 0;
+  W.vl_lo = K.vl_lo;
+  W.vl_hi = K.vl_hi;
+  asm volatile("" : "+s"(W.vl_lo), "+s"(W.vl_hi));  // opaque: values of their own, no longer parts of K's tuple (struct Wave)
 }
 
 __device__ __forceinline__ int wave_tier(const Wave &W) {
@@ -623,13 +663,48 @@ __device__ __forceinline__ int wave_tier(const Wave &W) {
 // tsum = the trip's sum of them, from zero, so that the caller's running sum is not touched by a trip whose lane left the
 // guard region (one add per trip, no copy kept for a restore).  Returns the wave's lanes that left it: the guard's compares
 // as ballots, OR-ed as scalars — the same set as ballot(!guard_ok), without forming the per-lane flag.
-template <bool DAMP, int NU>
+// GUARD = false: the same steps with nothing measured (rk4_tight) — returns 0.
+template <bool DAMP, int NU, bool GUARD = true>
 __device__ __forceinline__ unsigned long long trip_fast_ssq(const double *v, const double (&obs)[NU], const Lane &L, const Consts &K, State &s,
                                                             double &tsum) {
   Guard g = {0, 0, 0, 0};
 #pragma unroll
-  for (int j = 0; j < NU; ++j) rk4_tight<DAMP, TIGHT, true>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K, g, obs[j], &tsum, j == 0);
+  for (int j = 0; j < NU; ++j) rk4_tight<DAMP, TIGHT, true, GUARD>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K, g, obs[j], &tsum, j == 0);
+  if constexpr (!GUARD) return 0ull;
   return ballot(!(g.rho < hi_pow2(-20))) | ballot(!(g.rho_f < hi_pow2(-21))) | ballot(!(g.dlt < hi_pow2(-9))) | ballot(!(g.dlt_h < hi_pow2(-10)));
+}
+
+// Can a lane's increments reach TIGHT's guard anywhere in the NU steps that start at s?  An A-PRIORI bound from the trip's start
+// state (W0, Rh0) = (s.w, s.rx), the lane's constants and the range [vl_lo, vl_hi] of the loading table: where no lane of the wave
+// needs the guard, the trip runs without it (trip_fast_ssq, GUARD = false) and is the guarded trip's to the bit.  Returns the
+// lanes that DO need it.  Stated with R = 2^-20, B = 2^-21, Dmax = 0.9 * 2^-9 and, by induction over the trip's evaluations
+// in order, the hypotheses that every stage derivative so far has |d1'| <= 0.9 B and every increment |dlt| <= D <= Dmax:
+//   W    every step's end and every stage multiply the carried W by exp(dlt) to 4e-14 (the short series' truncation), so at any
+//        stage of the trip W = W0 (1 + om) with |om| <= exp(NU D) - 1 + 1e-12 <= 1.02 NU D  (NU D <= NU Dmax < 0.035);
+//   rho  a half-step stage's rho is a d1', the full-step stage's 2 c1, the step's end t1/3 with |t1| <= 6 max|d1'|: all <= 0.9 R;
+//   Rh   moves by (1 + q) per step, |q| <= |rho| (1 + |rho|): over NU - 1 steps Rh = Rh0 (1 + rr), |rr| < NU 0.9 R (1 + 1e-5);
+//   d0   = vl - vr W before the damping pass: |d0| <= max(|vl_hi - p|, |vl_lo - p|) + |p| gm1 =: D0,  p = vr W0, gm1 = 1.02 NU Dmax;
+//        the pass, d0 -= W (d0 - brx d1') with |brx| <= |bh| (1 + 2 R): |d0| <= D0 + Wm (D0 + |bh| B),  Wm = (1 + gm1) |W0|;
+//   dlt  = dk - rho (b/a) (1 - rho/2) (the full-step stage: - 2 c1 (b/a)(1 - c1)) with |dk| <= |kh| max|d0| — the step's end takes
+//        kh/6 times a sum of weight 6 —: |dlt| <= |kh| D0 + |b/a| R =: D.  Half-step stages: |khh| = |kh|/2 and |rho| <= 0.9 B: <= D/2;
+//   d1'  = Rh - W xr, xr = xh (1 + dl) with dl in {0, a1, b1, 2 c1}, |dl| <= 0.9 R.  With c = Rh0 - W0 xh (the cancellation kept:
+//        |Rh0| + |W0 xh| is thirty times too crude):  d1' = c + Rh0 rr - W0 xh (om + dl + om dl), and |W0 xh| <= |Rh0| + |c|, so
+//        |d1'| <= |c| + (|Rh0| + |c|) (1.02 NU D + (NU + 1) R)    [0.9 (NU + 1.03 (1 + 1e-5)) <= NU + 1].
+// D < Dmax and that last bound < 0.9 B close the induction: |dlt| < 0.9 * 2^-9 (half-step stages 0.9 * 2^-10), |c1| < 0.9 * 2^-21,
+// every |rho| < 0.9 * 2^-20 in exact arithmetic; float64 rounding of the step and of these dozen operations is 1e-13 of that.
+// Every quantity enters through its absolute value, so no sign of a constant is assumed, and a NaN anywhere makes a compare
+// false: that lane needs the guard — today's path, whose guard lets NaN pass.
+template <bool DAMP, int NU>
+__device__ __forceinline__ unsigned long long tight_needs_guard(const State &s, const Lane &L, const Wave &W) {
+  using TB = TightBound<NU>;
+  constexpr double R = TB::R, B = TB::B, Dmax = TB::Dmax, gm1 = TB::gm1;
+  const double p = L.vrw * s.w;
+  const double c = __builtin_fma(-s.w, L.hhdw, s.rx);  // (the first step's a1)
+  double D0 = __builtin_fma(__builtin_fabs(p), gm1, __builtin_fmax(__builtin_fabs(W.vl_hi - p), __builtin_fabs(W.vl_lo - p)));
+  if (DAMP) D0 = __builtin_fma((1.0 + gm1) * __builtin_fabs(s.w), __builtin_fma(__builtin_fabs(L.bh), B, D0), D0);
+  const double D = __builtin_fma(__builtin_fabs(L.kh), D0, __builtin_fabs(L.boa) * R);
+  const double rb = __builtin_fma(__builtin_fabs(s.rx) + __builtin_fabs(c), __builtin_fma(D, TB::G, TB::kap), __builtin_fabs(c));
+  return ballot(!(D < Dmax)) | ballot(!(rb < TB::Bmax));
 }
 
 // samples completed by a trip of NU steps starting at chunk step r (dv[j]: the steps' V-derivative sums).  S1: every step
@@ -670,13 +745,22 @@ constexpr int kNarrowUnroll = 8, kWiderUnroll = 4;  // NARROW; WIDE
 // its step.  The trip's sum joins ssq after the guard branch: the lanes in badmask drop it, restore the state and run the cold
 // trip, whose samples join ssq one by one (trip_cold_ssq: observations read again); the others add the sum they hold.  The early-rejection compare
 // reads ssq as the previous trip left it either way.
-template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU, bool INSTEP = false>
+// UNGUARD (INSTEP, whole trips): the loop of the trips whose start state proves the guard idle (tight_needs_guard) — they run
+// without it; at the first trip that does need it the loop sets W.guard_next and comes back without having taken that trip.
+// The caller (integrate_tier) enters it only while no alive lane is in W.never.  The instance without UNGUARD is the guarded loop
+// as it always was; for the whole trips of the in-step mode it comes back when the last lane of W.never has died, and after one
+// trip when none held it in the first place (W.guard_next).  Two loops with one copy of the trip each: with both trips in one
+// loop the guarded path lost 1.7 % at configs[1], with a third copy the kernels spilled to scratch memory.
+template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU, bool INSTEP = false, bool UNGUARD = false>
 __device__ __forceinline__ int integrate_multi(const double *lds, const double *ld, const Consts &K, Lane L, int k0, int kn, int r,
                                                int nsteps, State &s, Emit &em, double &ssq, double thr, bool active, double *acc_out,
                                                int64_t stride, Wave &W) {
   static_assert(NU >= 1 && (kResync % NU) == 0, "trip lengths divide the resync interval");
   static_assert(!INSTEP || (T == TIGHT && WANT_SSQ && !WANT_ACC && S1), "the in-step sum of squares: TIGHT, SSq alone, one step per sample");
+  static_assert(!UNGUARD || (INSTEP && NU > 2), "whole trips of the in-step mode; the remainder's pairs keep the guard");
+  constexpr bool HELD = INSTEP && NU > 2 && !UNGUARD;  // the guarded loop of whole in-step trips
   set_tier<T>(L);
+  const bool held = HELD && (W.never & W.alive) != 0;  // (loop-invariant: W.never is read again only where a lane dies)
   for (; r + NU <= nsteps; r += NU) {
     const unsigned long long deadmask = WANT_SSQ ? ballot(ssq > thr) : 0ull;  // NaN compares false: such a lane runs on
     const double *v = lds + 2 * r;
@@ -689,6 +773,22 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
       resync_t<DAMP, T>(s, L, K);
       W.next_resync = (r & ~(kResync - 1)) + kResync;
     }
+    if constexpr (UNGUARD) {
+      // no alive lane can reach the guard from here: the trip without it — no saved state, nothing to compare afterwards, and
+      // the branch back waits for nothing the trip computed.  The sum joins ssq as the guarded trip's does.
+      if ((tight_needs_guard<DAMP, NU>(s, L, W) & W.alive) != 0) {
+        W.guard_next = true;
+        return r;
+      }
+      double usum = 0.0;
+      trip_fast_ssq<DAMP, NU, false>(v, obs, L, K, s, usum);
+      W.steps[T] += NU;
+      W.unguarded += NU;
+      W.lane_steps += NU * (uint32_t)__builtin_popcountll(W.alive);
+      ssq += usum;
+      W.alive &= ~deadmask;
+      if (W.alive == 0) return r + NU;
+    } else {
     const State save = s;
     bool calm = false;
     double tsum = 0.0;
@@ -718,6 +818,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
     }
     if constexpr (INSTEP) ssq += tsum;
     else emit_trip<WANT_SSQ, WANT_ACC, S1, NU>(dv, obs, ld, r, s, em, L, K, k0, ssq, active, acc_out, stride);
+    const bool died = HELD && (deadmask & W.alive) != 0;
     W.alive &= ~deadmask;
     if constexpr (T != TIGHT) {
       if (W.calm >= kCalmSteps && badmask == 0) {  // demote: constant index (a run-time one would put the Wave in scratch memory)
@@ -726,6 +827,10 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
       }
     }
     if (badmask != 0 || W.alive == 0 || (T != TIGHT && (W.need[T - 1] & W.alive) == 0)) return r + NU;
+    if constexpr (HELD) {
+      if (!held || (died && (W.never & W.alive) == 0)) return r + NU;
+    }
+    }
   }
   return r;
 }
@@ -839,7 +944,13 @@ template <bool DAMP, bool WANT_SSQ, bool WANT_ACC, int T, bool S1, int NU, bool 
 __device__ __forceinline__ int integrate_tier(const double *lds, const double *ld, const Consts &K, const Lane &L, int k0, int kn, int r,
                                               int nsteps, State &s, Emit &em, double &ssq, double thr, bool active, double *acc_out,
                                               int64_t stride, Wave &W) {
-  if (r + NU <= nsteps) return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, NU, INSTEP>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
+  if (r + NU <= nsteps) {
+    if constexpr (INSTEP) {  // the trips that may drop the guard, unless a lane of W.never holds the wave to the guarded loop
+      if ((W.never & W.alive) == 0 && !W.guard_next) return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, NU, true, true>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
+    }
+    W.guard_next = false;
+    return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, NU, INSTEP>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
+  }
   return integrate_multi<DAMP, WANT_SSQ, WANT_ACC, T, S1, 2, INSTEP>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
 }
 
@@ -894,7 +1005,7 @@ __device__ __forceinline__ double solve(double *lds, const Consts &K, bool resid
                                         double b, double thr, double *acc_out, int64_t stride, Wave &W) {
   const Lane L = make_lane<DAMP>(dc, a, b, K);
   State s = initial_state(dc, L, K);
-  wave_begin(W, active, L, K);
+  wave_begin<NUT>(W, active, L, K);
   double ssq = 0.0;
   if (WANT_ACC && active) acc_out[0] = 0.0;
   for (int k0 = 1; k0 < K.nout; k0 += K.kc) {

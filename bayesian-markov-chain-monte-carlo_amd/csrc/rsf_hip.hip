@@ -86,6 +86,7 @@ Consts make_consts(const rsf_ctx *c, const double *data, int64_t group_chains) {
   K.data = data;
   K.nout = c->nout; K.S = c->m.substeps; K.kc = c->kc; K.nchunks = c->nchunks;
   K.group_chains = group_chains;
+  K.vl_lo = c->vl_lo; K.vl_hi = c->vl_hi;
   return K;
 }
 
@@ -124,6 +125,16 @@ void builtin_loading(const rsf_model &m, double hh, double *vl, size_t n) {
     const double t = m.t_start + (double)j * hh;
     vl[j] = m.V_ref * (1 + std::exp(-t / 20) * std::sin(10 * t));
   }
+}
+
+void set_loading_range(rsf_ctx *c, const double *vl, size_t n) {
+  double lo = vl[0], hi = vl[0];
+  for (size_t j = 1; j < n; ++j) {
+    lo = vl[j] < lo ? vl[j] : lo;
+    hi = vl[j] > hi ? vl[j] : hi;
+  }
+  c->vl_lo = lo;
+  c->vl_hi = hi;
 }
 
 }  // namespace rsfh
@@ -300,6 +311,7 @@ int rsf_set_model(rsf_ctx *c, const rsf_model *m) {
   if ((rc = ensure(c->vl, nvl * sizeof(double)))) return rc;
   HIP_TRY(hipMemcpyAsync(c->vl.p, vl.data(), nvl * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // vl (host vector) goes out of scope
+  set_loading_range(c, vl.data(), nvl);
   if (c->have_chains) free_chains(c);  // chain state (SSq, sigma^2, covariance) belongs to the previous model
   c->m = *m;
   c->delta_t = delta_t; c->h = h; c->nout = nout;

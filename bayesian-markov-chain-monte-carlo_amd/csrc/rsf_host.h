@@ -98,6 +98,7 @@ struct rsf_ctx {
   int32_t kc32 = 0, nchunks32 = 0;  // the float32 SAMPLER's own chunking: its tables are floats, twice as many fit the budget
   size_t lds_bytes = 0;
   rsfh::DevBuf vl;
+  double vl_lo = 0, vl_hi = 0;  // smallest and largest value of the table in vl (rsfh::set_loading_range): Consts::vl_lo / vl_hi
   // chains
   bool have_chains = false;
   bool external_chains = false;  // made by rsf_mcmc_init_state: no observation, advanced by rsf_mcmc_replay_ssq only
@@ -228,6 +229,9 @@ int first_bad_prob(int n, const double *probs);
 void free_chains(rsf_ctx *c);
 // the built-in loading history V_ref (1 + exp(-t / 20) sin 10 t) at t_start + j hh, j = 0 .. n - 1 (rsf_set_model's RK4 table)
 void builtin_loading(const rsf_model &m, double hh, double *vl, size_t n);
+// the range of the table about to become c->vl — whoever writes that table calls this with the host copy (rsf_set_model,
+// rsf_set_loading): the float64 sampler's a-priori bound on a TIGHT trip's increments rests on it (rsf_device.h, tight_needs_guard)
+void set_loading_range(rsf_ctx *c, const double *vl, size_t n);
 // what rsf_destroy frees of the other units' state: the replay graph (rsf_sampler.hip), the communicator (rsf_comm.hip)
 void release_replay_graph(rsf_ctx *c);
 void release_comm(rsf_ctx *c);

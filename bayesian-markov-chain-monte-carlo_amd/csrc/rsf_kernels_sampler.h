@@ -28,12 +28,12 @@ struct WaveCounters {
   rsf::Wave W;  // the running solve's control, and steps per tier / redone / lane_steps accumulated over the solves
   __device__ __forceinline__ void reset() {
     accepted = evaluated = nonfinite = oob = early = wave_solves = wave_skips = 0;
-    W.steps[0] = W.steps[1] = W.steps[2] = W.steps[3] = W.redone = W.lane_steps = 0;
+    W.steps[0] = W.steps[1] = W.steps[2] = W.steps[3] = W.redone = W.lane_steps = W.unguarded = 0;
   }
   __device__ __forceinline__ void flush(unsigned long long *stats) {
     if ((threadIdx.x & 63) == 0) {
       const uint32_t v[RSF_CNT_COUNT] = {accepted, evaluated, nonfinite, oob, early, wave_solves, wave_skips,
-                                         W.steps[0], W.steps[1], W.steps[2], W.steps[3], W.redone, W.lane_steps};
+                                         W.steps[0], W.steps[1], W.steps[2], W.steps[3], W.redone, W.lane_steps, W.unguarded};
 #pragma unroll
       for (int k = 0; k < RSF_CNT_COUNT; ++k)
         if (v[k]) atomicAdd(&stats[k], (unsigned long long)v[k]);

@@ -53,6 +53,7 @@ int rsf_set_loading(rsf_ctx *c, const double *vl, int64_t n) {
   // the table keeps its size (rsf_set_model allocated it): the copy is ordered on the ctx stream behind every earlier launch
   HIP_TRY(hipMemcpyAsync(c->vl.p, vl, (size_t)len * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's array, or `builtin`, may go away
+  set_loading_range(c, vl, (size_t)len);
   if (c->have_chains) free_chains(c);        // chain state (SSq, sigma^2, covariance) belongs to the previous history
   return RSF_OK;
 }

@@ -230,7 +230,10 @@ int rsf_mcmc_stats(rsf_ctx *ctx, int64_t *n_accepted, int64_t *n_evaluated, int6
                                     NARROW / WIDE / EARLY_REJECTED / LANE_STEPS stay 0 there */
 #define RSF_CNT_LANE_STEPS 12    /* sum over wave-steps of the lanes still integrating: lane utilisation =
                                     LANE_STEPS / (64 * (STEPS_TIGHT + STEPS_NARROW + STEPS_WIDE + STEPS_FULL)) */
-#define RSF_CNT_COUNT 13
+#define RSF_CNT_STEPS_UNGUARDED 13 /* float64 RK4: the wave-steps among STEPS_TIGHT whose trip ran without measuring its increments,
+                                      because a bound from the trip's start state showed that no lane could leave TIGHT's guard
+                                      region in it.  The result is the guarded trip's to the bit; 0 elsewhere. */
+#define RSF_CNT_COUNT 14
 int rsf_mcmc_counters(rsf_ctx *ctx, int64_t *out, int32_t n);
 
 /* ---- the sampler as an operator over a caller-evaluated likelihood ------------------------------------------

@@ -78,7 +78,9 @@ def main():
         line = f"  {name:16s} median {med:9.3f} ms  min {mn:9.3f} ms   {work / (med * 1e-3):.4e} steps*chains/s"
         try:   # where the wave-steps went (builds that have rsf_mcmc_counters)
             c = engines[name].counters()
-            line += "   wave-steps " + " ".join(f"{k[6:]}={c[k]:.3g}" for k in ("steps_tight", "steps_narrow", "steps_wide", "steps_full", "steps_redone") if c.get(k))
+            line += "   wave-steps " + " ".join(f"{k[6:]}={c[k]:.3g}" for k in ("steps_tight", "steps_narrow", "steps_wide", "steps_full", "steps_redone", "steps_unguarded") if c.get(k))
+            if c.get("steps_tight"):  # the share of the TIGHT wave-steps that ran without the guard (0 on builds before the counter)
+                line += f" unguarded/tight={c.get('steps_unguarded', 0) / c['steps_tight']:.4f}"
         except Exception:
             pass
         print(line)
