@@ -79,9 +79,9 @@ struct Lane {
   double c_l1p, c_l1q;  // series coefficients of the active tier kept in VGPRs (a VOP3 takes one SGPR source and the first Horner
   double c_em1;         //   term has two non-inline constants), see set_tier: b/3a and -b/4a of log1p, expm1's leading coefficient
   // the in-step sum of squares (rk4_tight, INSTEP): the sample's residual straight from the step's two partial sums, and the
-  // full-step stage fed with the half increment c1 (rho = 2 c1) through doubled constants
+  // full-step stage fed with the half increment c1 (rho = 2 c1) through doubled constants (the step's other in-step constants
+  // are formed where its loops are entered: struct Series)
   double cv2;           // 2 cv
-  double boa2;          // 2 b/a     : (b/a) log1p(2 c1) = c1 (2b/a - (2b/a) c1)
   double bh2, bh4;      // -2 bh, 4 bh: bh (1 - rho + rho^2) = bh + c1 (-2 bh + 4 bh c1)
 };
 
@@ -121,7 +121,6 @@ __device__ __forceinline__ Lane make_lane(double dc, double a, double b, const C
   L.nhboa = -0.5 * L.boa;
   L.bh = L.beta * fm::rcp(L.hhd);
   L.cv2 = 2.0 * L.cv;  // (exact doublings; formed only where an instantiation reads them)
-  L.boa2 = 2.0 * L.boa;
   L.bh2 = -2.0 * L.bh;
   L.bh4 = 4.0 * L.bh;
   set_tier<2>(L);
@@ -226,7 +225,12 @@ __device__ __forceinline__ void resync_t(State &s, const Lane &L, const Consts &
 struct Guard {
   float rho, dlt;
   float dlt_h;  // TIGHT: |dlt| of the two half-step stages, held to 2^-10 (truncation of their expm1 series < 8e-18)
-  float rho_f;  // INSTEP: |c1| = |rho| / 2 of the full-step stage, held to 2^-21 — the same bound on rho (tight_incr_doubled)
+  float rho_f;  // INSTEP: |c1| = |rho| / 2 of the full-step stage, held to 2^-21 — the same bound on rho (tight_incr_scaled)
+  float del;    // INSTEP: |del| = |dlt| / k of the two half-step stages and of the full-step stage, held to Series::lim (tight_incr_scaled)
+  float del_e;  // INSTEP: |del| of the step's end, held to Series::lim_e
+  // INSTEP: a figure that comes once per step waits here for the next step's, and the two fold into their maximum with one
+  // v_max3_f32 (guard_note): four instructions per step for the eight figures, as before the series was rescaled
+  float p_rho, p_rho_f, p_del, p_del_e;
 };
 
 __device__ __forceinline__ float hi_as_float(double x) { return __builtin_bit_cast(float, __double2hiint(x)); }
@@ -317,26 +321,17 @@ __device__ __forceinline__ double rk4_cold(State &s, double vl0, double vlm, dou
 // instructions more per evaluation — and WIDE one and two more again — rho^4/4, dlt^8/40320, ... + rho^4: |rho| < 2^-11,
 // |dlt| < 2^-5 (7e-18, 2.4e-18, 2.8e-17).  (Until round 3 they were an unscaled form with Newton steps on 1/x: 131 and 144
 // instructions per step against 102 and 118, and their a-priori bounds reached less far down in Dc.)
-// SHORT (the in-step mode's half-step stages, TIGHT): expm1 to dlt^3/6.  Their w is a stage value, not the carried state: at
-// the stage guard's edge, |dlt| = 2^-10, the dropped dlt^4/24 is 3.8e-14 of it, which reaches the step's sample with weight 1/3
-// and the carried state through another factor |dlt|; at the increments of a Dc ~ 1000 chain (|dlt| ~ 1e-4) it is 4e-18.
-// GUARD = false (all three functions of the step): the Guard updates are compiled out — the arithmetic of the step is the same
-// instruction for instruction; for a trip whose start state proves that no increment can reach a threshold (tight_needs_guard).
-template <int T, bool HALF, bool SHORT = false, bool GUARD = true>
+template <int T, bool HALF>
 __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L, double w0, double &w, double &q, Guard &g) {
-  static_assert(!SHORT || (T == TIGHT && HALF), "the short series is for TIGHT's half-step stages");
-  static_assert(GUARD || T == TIGHT, "only TIGHT has an a-priori bound");
-  if constexpr (GUARD) g.rho = __builtin_fmaxf(g.rho, __builtin_fabsf(hi_as_float(rho)));
+  g.rho = __builtin_fmaxf(g.rho, __builtin_fabsf(hi_as_float(rho)));
   double pb = L.nhboa;  // (b/a)(1 - rho/2 [+ rho^2/3 [- rho^3/4]])
   if (T == NARROW) pb = __builtin_fma(rho, L.c_l1p, pb);
   if (T == WIDE) pb = __builtin_fma(rho, __builtin_fma(rho, L.c_l1q, L.c_l1p), pb);
   const double dlt = __builtin_fma(-rho, __builtin_fma(rho, pb, L.boa), dk);
   // TIGHT: expm1 to dlt^4/24 at every stage, half-step stages held to |dlt| < 2^-10, the others to 2^-9
-  if constexpr (GUARD) {
-    if (T == TIGHT && HALF) g.dlt_h = __builtin_fmaxf(g.dlt_h, __builtin_fabsf(hi_as_float(dlt)));
-    else g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
-  }
-  double e = SHORT ? 1.0 / 6.0 : L.c_em1;
+  if (T == TIGHT && HALF) g.dlt_h = __builtin_fmaxf(g.dlt_h, __builtin_fabsf(hi_as_float(dlt)));
+  else g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
+  double e = L.c_em1;
   if (T == WIDE) {
     e = fm::hfma(e, dlt, 1.0 / 5040.0);
     e = fm::hfma(e, dlt, 1.0 / 720.0);
@@ -345,7 +340,7 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
     e = fm::hfma(e, dlt, 1.0 / 120.0);
     e = fm::hfma(e, dlt, 1.0 / 24.0);
   }
-  if (!SHORT) e = fm::hfma(e, dlt, 1.0 / 6.0);
+  e = fm::hfma(e, dlt, 1.0 / 6.0);
   e = __builtin_fma(e, dlt, 0.5);
   e = __builtin_fma(e, dlt, 1.0);
   w = __builtin_fma(w0 * dlt, e, w0);
@@ -355,19 +350,103 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
   if (T == WIDE) q = __builtin_fma(-rho, q, -rho);                 // WIDE: ... + rho^4
 }
 
-// TIGHT's full-step stage fed with c1 = rho / 2, the previous stage's d1' as it stands (the in-step mode): the doublings are
-// exact, so dlt and w are tight_incr<TIGHT, false>(c1 + c1, ...)'s to the bit; brx = bh (1 + q) comes out of one Horner
-// pass in c1 instead of q and a product (one rounding placed differently), and the sum c1 + c1 is never formed.
-template <bool GUARD = true>
-__device__ __forceinline__ void tight_incr_doubled(double c1, double dk, const Lane &L, double w0, double &w, double &brx, Guard &g) {
-  if constexpr (GUARD) g.rho_f = __builtin_fmaxf(g.rho_f, __builtin_fabsf(hi_as_float(c1)));
-  const double dlt = __builtin_fma(-c1, __builtin_fma(-c1, L.boa2, L.boa2), dk);
-  if constexpr (GUARD) g.dlt = __builtin_fmaxf(g.dlt, __builtin_fabsf(hi_as_float(dlt)));
-  double e = fm::hfma(L.c_em1, dlt, 1.0 / 6.0);
-  e = __builtin_fma(e, dlt, 0.5);
-  e = __builtin_fma(e, dlt, 1.0);
-  w = __builtin_fma(w0 * dlt, e, w0);
-  brx = __builtin_fma(c1, __builtin_fma(c1, L.bh4, L.bh2), L.bh);
+// The in-step mode's increments (TIGHT trips of the sampler: rk4_tight, INSTEP), with the stage stiffness folded into the series.
+// Write k for the factor that puts a stage's ms derivative d into increment units: khh at the half-step stages, kh at the
+// full-step stage, kh6 at the step's end.  dlt = k d - rho (b/a)(1 - rho/2) is never formed; the step works on del = dlt / k,
+//     del = d - rho (B + N rho),   B = (b/a)/k,  N = -(b/2a)/k        (two fmas on d as it stands: the product k d is gone),
+// and the series takes k into its coefficients: w' = w0 + (w0 del) Ek(del) with
+//     Ek(del) = k E(k del) = k + (k^2/2) del + (k^3/6) del^2 (+ (k^4/24) del^3)
+// — the Horner depth of E, its leading 1 now the k that the lane holds anyway: one operation fewer per increment, four per step.
+// k del is the same number as dlt, so every truncation bound above holds as it stands.  Of the roundings, the one of k d has
+// moved into the constants (each within 2 ulp, on terms below the leading one); d0 = V_l - v reaches del as it left the stage,
+// so nothing is rounded in front of that cancellation (pre-scaling d0 would do just that).
+//   half-step stages  r = rho, the previous stage's d1'; the series to del^2: their w is a stage value, not the carried state — at
+//                     the stage guard's edge, |dlt| = 2^-10, the dropped dlt^4/24 is 3.8e-14 of it, which reaches the step's sample
+//                     with weight 1/3 and the carried state through another factor |dlt|; at Dc ~ 1000 (|dlt| ~ 1e-4) it is 4e-18;
+//   full-step stage   r = c1 = rho / 2, the previous stage's d1' as it stands: (b/a) log1p(2 c1) / kh = c1 (B - B c1) with the
+//                     half-step stages' B = (b/a)/khh; brx = bh (1 + q) comes out of one Horner pass in c1 (Lane::bh2, bh4) in
+//                     place of q and a product, and the sum c1 + c1 is never formed;
+//   step's end        r = t1 = 3 rho, the weighted sum as it stands: (b/a) log1p(t1/3) / kh6 = t1 (B - (B/6) t1), the same B again.
+// The guard (GUARD; without it the same arithmetic, instruction for instruction, for a trip whose start state proves that no
+// increment can reach a threshold: tight_needs_guard) holds del to the regions of dlt: |del| < 2^-10 / |khh| at the half-step
+// stages — which is 2^-9 / |kh|, so the full-step stage shares the figure — and < 2^-9 / |kh6| at the step's end; rho and c1 as ever.
+// The thresholds are per lane and rounded DOWN: a trip earlier, never later.
+struct Series {
+  double B, N, N6;     // (b/a)/khh, -B/2, -B/6
+  double h1, h2;       // half-step stages: khh^2/2, khh^3/6
+  double f1, f2, f3;   // full-step stage: kh^2/2, kh^3/6, kh^4/24
+  double e1, e2, e3;   // step's end: kh6^2/2, kh6^3/6, kh6^4/24
+  float lim, lim_e;    // the guard's thresholds on |del|: high words, read as floats (struct Guard)
+};
+// Formed where a loop of in-step trips is entered (integrate_multi), from a value the compiler cannot trace back (local_value):
+// held from make_lane on, the constants were live through every other tier's loop as well and the sampler kernels spilled
+// (44 to 88 bytes of scratch per lane).  Thirty-odd operations per entry; at the headline shape a solve enters twice or so.
+template <bool GUARD>
+__device__ __forceinline__ Series make_series(const Lane &L) {
+  Series S;
+  const double khh = local_value(L.khh);
+  const double ik = fm::rcp(khh);
+  S.B = L.boa * ik;
+  S.N = -0.5 * S.B;
+  S.N6 = S.B * (-1.0 / 6.0);
+  const double kh = khh + khh, kh6 = khh * (1.0 / 3.0);  // (Lane::kh to the bit; Lane::kh6 to an ulp)
+  const double k2 = khh * khh, f2 = kh * kh, e2 = kh6 * kh6;
+  S.h1 = 0.5 * k2;
+  S.h2 = (k2 * khh) * (1.0 / 6.0);
+  S.f1 = 0.5 * f2;
+  S.f2 = (f2 * kh) * (1.0 / 6.0);
+  S.f3 = (f2 * f2) * (1.0 / 24.0);
+  S.e1 = 0.5 * e2;
+  S.e2 = (e2 * kh6) * (1.0 / 6.0);
+  S.e3 = (e2 * e2) * (1.0 / 24.0);
+  S.lim = S.lim_e = 0.0f;
+  if constexpr (GUARD) {
+    // 2^-10 / |khh| and 3 * 2^-9 / |khh|.  The factor 1 - 2^-30 covers the ulps of the reciprocal and of kh6 against khh / 3;
+    // keeping the high word alone rounds down once more (at most 2^-20 of the threshold in all).
+    const double aik = (1.0 - 0x1.0p-30) * __builtin_fabs(ik);
+    S.lim = hi_as_float(0x1.0p-10 * aik);
+    S.lim_e = hi_as_float(0x1.8p-8 * aik);
+  }
+  return S;
+}
+
+// a figure that comes once per step: held on even steps, folded with the next step's on odd ones (struct Guard)
+__device__ __forceinline__ void guard_note(float &acc, float &pend, double x, bool odd) {
+  const float ax = __builtin_fabsf(hi_as_float(x));
+  if (odd) acc = __builtin_fmaxf(__builtin_fmaxf(acc, pend), ax);
+  else pend = ax;
+}
+
+// STAGE 0: a half-step stage, q = -rho + rho^2;  1: the full-step stage, q = brx;  2: the step's end, q = -rho + rho^2 of rho = t1/3.
+// odd: the step's parity within its trip (guard_note).
+template <int STAGE, bool GUARD>
+__device__ __forceinline__ void tight_incr_scaled(double r, double d, const Lane &L, const Series &S, double w0, double &w, double &q, Guard &g,
+                                                  bool odd) {
+  const double pb = STAGE == 0 ? __builtin_fma(r, S.N, S.B) : (STAGE == 1 ? __builtin_fma(-r, S.B, S.B) : __builtin_fma(r, S.N6, S.B));
+  const double del = __builtin_fma(-r, pb, d);
+  double e;
+  if constexpr (STAGE == 0) e = __builtin_fma(__builtin_fma(S.h2, del, S.h1), del, L.khh);
+  else if constexpr (STAGE == 1) e = __builtin_fma(__builtin_fma(fm::hfma(S.f3, del, S.f2), del, S.f1), del, L.kh);
+  else e = __builtin_fma(__builtin_fma(fm::hfma(S.e3, del, S.e2), del, S.e1), del, L.kh6);
+  w = __builtin_fma(w0 * del, e, w0);
+  if constexpr (STAGE == 1) {
+    q = __builtin_fma(r, __builtin_fma(r, L.bh4, L.bh2), L.bh);
+    if constexpr (GUARD) {
+      guard_note(g.rho_f, g.p_rho_f, r, odd);
+      guard_note(g.del, g.p_del, del, odd);
+    }
+  } else {
+    const double rho = STAGE == 0 ? r : r * (1.0 / 3.0);  // the step's end: (h/6Dc)/x times the unscaled sum
+    q = __builtin_fma(rho, rho, -rho);
+    if constexpr (GUARD && STAGE == 0) {  // two of each per step: they fold within the step
+      g.rho = __builtin_fmaxf(g.rho, __builtin_fabsf(hi_as_float(rho)));
+      g.del = __builtin_fmaxf(g.del, __builtin_fabsf(hi_as_float(del)));
+    }
+    if constexpr (GUARD && STAGE == 2) {
+      guard_note(g.rho, g.p_rho, rho, odd);
+      guard_note(g.del_e, g.p_del_e, del, odd);
+    }
+  }
 }
 
 // d0 = V_l - V_ref w,  d1' = Rh - w xr  (xr = Rh x at the stage),  g = d0 - brx d1'  (brx = bh (1 + q)) and the damping pass.
@@ -392,10 +471,12 @@ __device__ __forceinline__ void rhs_tight(double w, double xr, double Rh, double
 // INSTEP (TIGHT trips of the sampler, one step per sample: integrate_multi): the step adds its sample's squared residual to
 // *ssq itself (`first`: starts that sum), r = cv sv + (2 cv sm - obs), and returns nothing of use — no per-step sample leaves the step, so a trip keeps
 // neither its samples nor, beyond each step, its observations in registers.  Its half-step stages take the expm1 series
-// one term shorter (tight_incr, SHORT) and its full-step stage the half increment (tight_incr_doubled).
+// one term shorter and its full-step stage the half increment, all four increments in units of their stage's stiffness (tight_incr_scaled;
+// S: the series constants, odd: the step's parity in its trip, for the guard).
 template <bool DAMP, int T, bool INSTEP = false, bool GUARD = true>
 __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, double vl1, const Lane &L, const Consts &K, Guard &g,
-                                            double obs = 0.0, double *ssq = nullptr, bool first = false) {
+                                            double obs = 0.0, double *ssq = nullptr, bool first = false, const Series *S = nullptr,
+                                            bool odd = false) {
   static_assert(!INSTEP || T == TIGHT, "the in-step sum of squares is the TIGHT step's");
   static_assert(GUARD || INSTEP, "the unguarded step is the in-step mode's");
   double a0, a1, a2, b0, b1, b2, c0, c1, c2, e0, e1, e2, w, q;
@@ -403,15 +484,17 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
   const double vr = L.vrw, xh = L.hhdw, xf = L.hdw;  // (V_ref, hhd, hd) / kvk with damping: s.w is W (Lane::vrw)
   rhs_tight<DAMP>(s.w, xh, Rh, vl0, L.bh, vr, a0, a1, a2);
   double sv = s.w * a2;  // k1 + k4 of dV/dt (in units of vk, vk/kvk with damping), and k2 + k3 below: 5 instructions for the weighted sum
-  tight_incr<T, true, INSTEP, GUARD>(a1, L.khh * a0, L, s.w, w, q, g);
+  if constexpr (INSTEP) tight_incr_scaled<0, GUARD>(a1, a0, L, *S, s.w, w, q, g, odd);
+  else tight_incr<T, true>(a1, L.khh * a0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, a1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, b0, b1, b2);
   double sm = w * b2;
-  tight_incr<T, true, INSTEP, GUARD>(b1, L.khh * b0, L, s.w, w, q, g);
+  if constexpr (INSTEP) tight_incr_scaled<0, GUARD>(b1, b0, L, *S, s.w, w, q, g, odd);
+  else tight_incr<T, true>(b1, L.khh * b0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, b1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, c0, c1, c2);
   sm = __builtin_fma(w, c2, sm);
   if constexpr (INSTEP) {
     double brx;
-    tight_incr_doubled<GUARD>(c1, L.kh * c0, L, s.w, w, brx, g);
+    tight_incr_scaled<1, GUARD>(c1, c0, L, *S, s.w, w, brx, g, odd);
     rhs_tight<DAMP>(w, __builtin_fma(xf, c1, xh), Rh, vl1, brx, vr, e0, e1, e2);
   } else {
     tight_incr<T, false>(c1 + c1, L.kh * c0, L, s.w, w, q, g);
@@ -420,8 +503,12 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
   sv = __builtin_fma(w, e2, sv);
   const double t0 = a0 + 2.0 * b0 + 2.0 * c0 + e0;
   const double t1 = a1 + 2.0 * b1 + 2.0 * c1 + e1;
-  const double rho = t1 * (1.0 / 3.0);  // (h/6Dc)/x times the unscaled sum
-  tight_incr<T, false, false, GUARD>(rho, L.kh6 * t0, L, s.w, w, q, g);
+  if constexpr (INSTEP) {
+    tight_incr_scaled<2, GUARD>(t1, t0, L, *S, s.w, w, q, g, odd);
+  } else {
+    const double rho = t1 * (1.0 / 3.0);  // (h/6Dc)/x times the unscaled sum
+    tight_incr<T, false>(rho, L.kh6 * t0, L, s.w, w, q, g);
+  }
   s.ms = __builtin_fma(K.h6, t0, s.ms);
   s.w = w;
   s.rx = __builtin_fma(Rh, q, Rh);  // x' = x (1 + rho), exact to rounding for |rho| < 2^-20; like w, resynced
@@ -664,14 +751,35 @@ __device__ __forceinline__ int wave_tier(const Wave &W) {
 // guard region (one add per trip, no copy kept for a restore).  Returns the wave's lanes that left it: the guard's compares
 // as ballots, OR-ed as scalars — the same set as ballot(!guard_ok), without forming the per-lane flag.
 // GUARD = false: the same steps with nothing measured (rk4_tight) — returns 0.
+// The observations: the caller reads the first kObsAhead before the arithmetic (integrate_multi); the trip reads the others, a pair
+// at every other step, kObsAhead steps before their own — far enough for the LDS latency, and the trip's top holds kObsAhead
+// observations in registers in place of NU (twelve doubles fewer at NU = 16: the room the Series constants live in).
+template <int NU>
+constexpr int kObsAhead = NU < 4 ? NU : 4;
 template <bool DAMP, int NU, bool GUARD = true>
-__device__ __forceinline__ unsigned long long trip_fast_ssq(const double *v, const double (&obs)[NU], const Lane &L, const Consts &K, State &s,
-                                                            double &tsum) {
-  Guard g = {0, 0, 0, 0};
+__device__ __forceinline__ unsigned long long trip_fast_ssq(const double *v, const double (&head)[kObsAhead<NU>], const double *ob, const Lane &L,
+                                                            const Series &S, const Consts &K, State &s, double &tsum) {
+  static_assert(NU % 2 == 0, "the guard folds the figures of two steps (guard_note); observations come in pairs");
+  constexpr int AH = kObsAhead<NU>;
+  Guard g = {};
+  double obs[NU];
 #pragma unroll
-  for (int j = 0; j < NU; ++j) rk4_tight<DAMP, TIGHT, true, GUARD>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K, g, obs[j], &tsum, j == 0);
+  for (int j = 0; j < AH; ++j) obs[j] = head[j];
+#pragma unroll
+  for (int j = 0; j < NU; ++j) {
+    if (j % 2 == 0 && j + AH < NU) {
+      obs[j + AH] = ob[j + AH];
+      obs[j + AH + 1] = ob[j + AH + 1];
+    }
+    rk4_tight<DAMP, TIGHT, true, GUARD>(s, v[2 * j], v[2 * j + 1], v[2 * j + 2], L, K, g, obs[j], &tsum, j == 0, &S, (j & 1) != 0);
+    // the guard's maxima are wanted only after the trip, and left alone the compiler gathers their instructions there, every
+    // figure of the trip kept (and spilled: 700 bytes per lane) until then: made opaque, each pair of steps folds its own
+    if constexpr (GUARD) {
+      if (j & 1) asm volatile("" : "+v"(g.rho), "+v"(g.rho_f), "+v"(g.del), "+v"(g.del_e));
+    }
+  }
   if constexpr (!GUARD) return 0ull;
-  return ballot(!(g.rho < hi_pow2(-20))) | ballot(!(g.rho_f < hi_pow2(-21))) | ballot(!(g.dlt < hi_pow2(-9))) | ballot(!(g.dlt_h < hi_pow2(-10)));
+  return ballot(!(g.rho < hi_pow2(-20))) | ballot(!(g.rho_f < hi_pow2(-21))) | ballot(!(g.del < S.lim)) | ballot(!(g.del_e < S.lim_e));
 }
 
 // Can a lane's increments reach TIGHT's guard anywhere in the NU steps that start at s?  An A-PRIORI bound from the trip's start
@@ -760,15 +868,18 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
   static_assert(!UNGUARD || (INSTEP && NU > 2), "whole trips of the in-step mode; the remainder's pairs keep the guard");
   constexpr bool HELD = INSTEP && NU > 2 && !UNGUARD;  // the guarded loop of whole in-step trips
   set_tier<T>(L);
+  Series S;
+  if constexpr (INSTEP) S = make_series<!UNGUARD>(L);
   const bool held = HELD && (W.never & W.alive) != 0;  // (loop-invariant: W.never is read again only where a lane dies)
   for (; r + NU <= nsteps; r += NU) {
     const unsigned long long deadmask = WANT_SSQ ? ballot(ssq > thr) : 0ull;  // NaN compares false: such a lane runs on
     const double *v = lds + 2 * r;
     // one step per sample: the observations this trip completes, read before the arithmetic (a lone wave has nothing
     // else to hide the LDS latency behind)
-    double obs[NU], dv[INSTEP ? 1 : NU];
+    constexpr int NOBS = INSTEP ? kObsAhead<NU> : NU;  // (the in-step trip reads the others itself: trip_fast_ssq)
+    double obs[NOBS], dv[INSTEP ? 1 : NU];
 #pragma unroll
-    for (int j = 0; j < NU; ++j) obs[j] = (WANT_SSQ && S1) ? ld[r + j] : 0.0;
+    for (int j = 0; j < NOBS; ++j) obs[j] = (WANT_SSQ && S1) ? ld[r + j] : 0.0;
     if (r >= W.next_resync) {
       resync_t<DAMP, T>(s, L, K);
       W.next_resync = (r & ~(kResync - 1)) + kResync;
@@ -781,7 +892,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
         return r;
       }
       double usum = 0.0;
-      trip_fast_ssq<DAMP, NU, false>(v, obs, L, K, s, usum);
+      trip_fast_ssq<DAMP, NU, false>(v, obs, ld + r, L, S, K, s, usum);
       W.steps[T] += NU;
       W.unguarded += NU;
       W.lane_steps += NU * (uint32_t)__builtin_popcountll(W.alive);
@@ -793,7 +904,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
     bool calm = false;
     double tsum = 0.0;
     unsigned long long tripped;
-    if constexpr (INSTEP) tripped = trip_fast_ssq<DAMP, NU>(v, obs, L, K, s, tsum);
+    if constexpr (INSTEP) tripped = trip_fast_ssq<DAMP, NU>(v, obs, ld + r, L, S, K, s, tsum);
     else tripped = ballot(trip_fast<DAMP, T, NU>(v, L, K, s, dv, &calm));
     const unsigned long long badmask = tripped & W.alive;  // wave-uniform, straight from the compares
     W.steps[T] += NU;
