@@ -82,7 +82,7 @@ struct Lane {
   // full-step stage fed with the half increment c1 (rho = 2 c1) through doubled constants (the step's other in-step constants
   // are formed where its loops are entered: struct Series)
   double cv2;           // 2 cv
-  double bh2, bh4;      // -2 bh, 4 bh: bh (1 - rho + rho^2) = bh + c1 (-2 bh + 4 bh c1)
+  double bh2;           // -2 bh: the full-step stage's bracket, bh (1 - rho) = bh + c1 (-2 bh) (tight_incr_scaled)
 };
 
 template <int T>
@@ -122,7 +122,6 @@ __device__ __forceinline__ Lane make_lane(double dc, double a, double b, const C
   L.bh = L.beta * fm::rcp(L.hhd);
   L.cv2 = 2.0 * L.cv;  // (exact doublings; formed only where an instantiation reads them)
   L.bh2 = -2.0 * L.bh;
-  L.bh4 = 4.0 * L.bh;
   set_tier<2>(L);
   return L;
 }
@@ -364,9 +363,18 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
 //                     the stage guard's edge, |dlt| = 2^-10, the dropped dlt^4/24 is 3.8e-14 of it, which reaches the step's sample
 //                     with weight 1/3 and the carried state through another factor |dlt|; at Dc ~ 1000 (|dlt| ~ 1e-4) it is 4e-18;
 //   full-step stage   r = c1 = rho / 2, the previous stage's d1' as it stands: (b/a) log1p(2 c1) / kh = c1 (B - B c1) with the
-//                     half-step stages' B = (b/a)/khh; brx = bh (1 + q) comes out of one Horner pass in c1 (Lane::bh2, bh4) in
-//                     place of q and a product, and the sum c1 + c1 is never formed;
+//                     half-step stages' B = (b/a)/khh, and the sum c1 + c1 is never formed;
 //   step's end        r = t1 = 3 rho, the weighted sum as it stands: (b/a) log1p(t1/3) / kh6 = t1 (B - (B/6) t1), the same B again.
+// The stage brackets take 1/(1 + rho) to FIRST order: brx = bh (1 - rho), one fma on the previous d1' at the half-step stages
+// (rk4_tight) and on c1 at the full-step stage (Lane::bh2) — no q there.  A stage's brx only forms g = d0 - brx d1', which
+// feeds the stage's dV/dt (the sample, cv sum wgt W g) and, with damping, d0 -= W g with W = k1 V_ref w / a ~ 1e-5; V never
+// feeds back.  So the dropped bh rho^2 d1' reaches the sample as it stands, the state scaled down by W, and is not carried
+// from step to step: |delta g| <= |bh| rho^2 |d1'| per stage, and the d1' of a half-step stage is the next stage's rho (or c1),
+// so <= |bh| lim^3 under a limit lim on |rho| (the full-step stage's own d1' is held through the step's end, t1 = 3 rho: it
+// stays within 7 lim whatever the others do, and is one of them to a part in 1e3 on any smooth trajectory).
+// The guard holds |bh| lim^3 to 2^-47 V_ref by a per-lane limit on |rho| (Series::lim_rho: it binds before 2^-20 where |bh| >
+// 8192 V_ref) — under the dlt^4/24 above; at Dc ~ 1000, h = 0.025 the term is 1e-18.  The step's end keeps its
+// q = -rho + rho^2: that one updates the carried Rh.
 // The guard (GUARD; without it the same arithmetic, instruction for instruction, for a trip whose start state proves that no
 // increment can reach a threshold: tight_needs_guard) holds del to the regions of dlt: |del| < 2^-10 / |khh| at the half-step
 // stages — which is 2^-9 / |kh|, so the full-step stage shares the figure — and < 2^-9 / |kh6| at the step's end; rho and c1 as ever.
@@ -377,12 +385,33 @@ struct Series {
   double f1, f2, f3;   // full-step stage: kh^2/2, kh^3/6, kh^4/24
   double e1, e2, e3;   // step's end: kh6^2/2, kh6^3/6, kh6^4/24
   float lim, lim_e;    // the guard's thresholds on |del|: high words, read as floats (struct Guard)
+  float lim_rho, lim_c1;  // the guard's thresholds on |rho| and on |c1|, half of it (tight_rho_limit), high words as well
+  float bmax;          // the unguarded loop's: what tight_needs_guard holds its bound on |d1'| to, 0.9 lim_rho / 2
 };
+
+// The lane's limit on |rho| in the in-step TIGHT step: min(2^-20, cbrt(2^-47 V_ref / |bh|)), rounded DOWN — the first from the
+// series in rho as ever, the second holds the rho^2 term that the stage brackets leave out to 2^-47 V_ref (tight_incr_scaled).
+// The cube root as y^(-1/3) of y = 2^47 |bh| / V_ref: a seed from the exponent (a third of the high word taken from a
+// constant: within 10.3 % in y r^3) and two Newton steps r <- r (4 - y r^3) / 3, each of which lands BELOW the root (by 2/9 of
+// the square of that figure: -2.5e-3, then -1.2e-5); the factor 1 - 2^-30 covers the roundings.  bh = 0 gives a huge r and
+// the first limit, a NaN anywhere the same (fmin keeps 2^-20: the path as it was), an infinite bh a limit of -inf, which every
+// compare fails.  A dozen and a half operations, where a Series is formed and once per solve (wave_begin): 0.0003 per step at
+// nsteps 2000.
+__device__ __forceinline__ double tight_rho_limit(double bh, const Consts &K) {
+  const double y = (0x1.0p47 * K.inv_vref) * __builtin_fabs(bh);
+  double r = __hiloint2double((int)(0x553ee800u - (unsigned)__double2hiint(y) / 3u), 0);
+#pragma unroll
+  for (int it = 0; it < 2; ++it) r = (r * (1.0 / 3.0)) * __builtin_fma(-(y * r), r * r, 4.0);
+  return __builtin_fmin(0x1.0p-20, (1.0 - 0x1.0p-30) * r);
+}
+// What the a-priori bound holds every |d1'| of a trip to, given the lane's limit on rho: 0.9 of the limit on c1 (tight_needs_guard
+// through Series::bmax, which keeps the high word — once more rounded down, by 2^-20 of the figure at most; W.never as it stands).
+__device__ __forceinline__ double tight_bmax(double lim_rho) { return 0.45 * lim_rho; }
 // Formed where a loop of in-step trips is entered (integrate_multi), from a value the compiler cannot trace back (local_value):
 // held from make_lane on, the constants were live through every other tier's loop as well and the sampler kernels spilled
-// (44 to 88 bytes of scratch per lane).  Thirty-odd operations per entry; at the headline shape a solve enters twice or so.
+// (44 to 88 bytes of scratch per lane).  Fifty-odd operations per entry; at the headline shape a solve enters twice or so.
 template <bool GUARD>
-__device__ __forceinline__ Series make_series(const Lane &L) {
+__device__ __forceinline__ Series make_series(const Lane &L, const Consts &K) {
   Series S;
   const double khh = local_value(L.khh);
   const double ik = fm::rcp(khh);
@@ -399,8 +428,12 @@ __device__ __forceinline__ Series make_series(const Lane &L) {
   S.e1 = 0.5 * e2;
   S.e2 = (e2 * kh6) * (1.0 / 6.0);
   S.e3 = (e2 * e2) * (1.0 / 24.0);
-  S.lim = S.lim_e = 0.0f;
+  S.lim = S.lim_e = S.lim_rho = S.lim_c1 = 0.0f;
+  const double lim_rho = tight_rho_limit(local_value(L.bh), K);  // (formed here, like the rest: see above)
+  S.bmax = hi_as_float(tight_bmax(lim_rho));  // (the high word of 0.9 * 2^-21 where the first limit holds)
   if constexpr (GUARD) {
+    S.lim_rho = hi_as_float(lim_rho);
+    S.lim_c1 = hi_as_float(0.5 * lim_rho);
     // 2^-10 / |khh| and 3 * 2^-9 / |khh|.  The factor 1 - 2^-30 covers the ulps of the reciprocal and of kh6 against khh / 3;
     // keeping the high word alone rounds down once more (at most 2^-20 of the threshold in all).
     const double aik = (1.0 - 0x1.0p-30) * __builtin_fabs(ik);
@@ -417,7 +450,8 @@ __device__ __forceinline__ void guard_note(float &acc, float &pend, double x, bo
   else pend = ax;
 }
 
-// STAGE 0: a half-step stage, q = -rho + rho^2;  1: the full-step stage, q = brx;  2: the step's end, q = -rho + rho^2 of rho = t1/3.
+// STAGE 0: a half-step stage, q left alone (the caller's bracket is bh - bh rho);  1: the full-step stage, q = brx = bh - 2 bh c1;
+// 2: the step's end, q = -rho + rho^2 of rho = t1/3.
 // odd: the step's parity within its trip (guard_note).
 template <int STAGE, bool GUARD>
 __device__ __forceinline__ void tight_incr_scaled(double r, double d, const Lane &L, const Series &S, double w0, double &w, double &q, Guard &g,
@@ -430,14 +464,14 @@ __device__ __forceinline__ void tight_incr_scaled(double r, double d, const Lane
   else e = __builtin_fma(__builtin_fma(fm::hfma(S.e3, del, S.e2), del, S.e1), del, L.kh6);
   w = __builtin_fma(w0 * del, e, w0);
   if constexpr (STAGE == 1) {
-    q = __builtin_fma(r, __builtin_fma(r, L.bh4, L.bh2), L.bh);
+    q = __builtin_fma(r, L.bh2, L.bh);
     if constexpr (GUARD) {
       guard_note(g.rho_f, g.p_rho_f, r, odd);
       guard_note(g.del, g.p_del, del, odd);
     }
   } else {
     const double rho = STAGE == 0 ? r : r * (1.0 / 3.0);  // the step's end: (h/6Dc)/x times the unscaled sum
-    q = __builtin_fma(rho, rho, -rho);
+    if constexpr (STAGE == 2) q = __builtin_fma(rho, rho, -rho);
     if constexpr (GUARD && STAGE == 0) {  // two of each per step: they fold within the step
       g.rho = __builtin_fmaxf(g.rho, __builtin_fabsf(hi_as_float(rho)));
       g.del = __builtin_fmaxf(g.del, __builtin_fabsf(hi_as_float(del)));
@@ -449,7 +483,8 @@ __device__ __forceinline__ void tight_incr_scaled(double r, double d, const Lane
   }
 }
 
-// d0 = V_l - V_ref w,  d1' = Rh - w xr  (xr = Rh x at the stage),  g = d0 - brx d1'  (brx = bh (1 + q)) and the damping pass.
+// d0 = V_l - V_ref w,  d1' = Rh - w xr  (xr = Rh x at the stage),  g = d0 - brx d1'  (brx = bh (1 + q); in the in-step mode
+// bh (1 - rho): tight_incr_scaled) and the damping pass.
 // g is the bracket of dV/dt = vk w g, one fma on the two derivatives the stage forms anyway.  With damping `w` is W = kvk w
 // (Lane::vrw; vr = V_ref/kvk, xr scaled by 1/kvk with it), so the pass d0 -= (kvk w) g, g -= (kvk w) g takes no product; the
 // caller forms W g (the stage's dV/dt in units of vk/kvk) inside its weighted sum.  (Rounds 1-2 wrote g linear in w so that all but one fma
@@ -479,18 +514,18 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
                                             bool odd = false) {
   static_assert(!INSTEP || T == TIGHT, "the in-step sum of squares is the TIGHT step's");
   static_assert(GUARD || INSTEP, "the unguarded step is the in-step mode's");
-  double a0, a1, a2, b0, b1, b2, c0, c1, c2, e0, e1, e2, w, q;
+  double a0, a1, a2, b0, b1, b2, c0, c1, c2, e0, e1, e2, w, q = 0.0;
   const double Rh = s.rx;
   const double vr = L.vrw, xh = L.hhdw, xf = L.hdw;  // (V_ref, hhd, hd) / kvk with damping: s.w is W (Lane::vrw)
   rhs_tight<DAMP>(s.w, xh, Rh, vl0, L.bh, vr, a0, a1, a2);
   double sv = s.w * a2;  // k1 + k4 of dV/dt (in units of vk, vk/kvk with damping), and k2 + k3 below: 5 instructions for the weighted sum
   if constexpr (INSTEP) tight_incr_scaled<0, GUARD>(a1, a0, L, *S, s.w, w, q, g, odd);
   else tight_incr<T, true>(a1, L.khh * a0, L, s.w, w, q, g);
-  rhs_tight<DAMP>(w, __builtin_fma(xh, a1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, b0, b1, b2);
+  rhs_tight<DAMP>(w, __builtin_fma(xh, a1, xh), Rh, vlm, INSTEP ? __builtin_fma(-L.bh, a1, L.bh) : __builtin_fma(L.bh, q, L.bh), vr, b0, b1, b2);
   double sm = w * b2;
   if constexpr (INSTEP) tight_incr_scaled<0, GUARD>(b1, b0, L, *S, s.w, w, q, g, odd);
   else tight_incr<T, true>(b1, L.khh * b0, L, s.w, w, q, g);
-  rhs_tight<DAMP>(w, __builtin_fma(xh, b1, xh), Rh, vlm, __builtin_fma(L.bh, q, L.bh), vr, c0, c1, c2);
+  rhs_tight<DAMP>(w, __builtin_fma(xh, b1, xh), Rh, vlm, INSTEP ? __builtin_fma(-L.bh, b1, L.bh) : __builtin_fma(L.bh, q, L.bh), vr, c0, c1, c2);
   sm = __builtin_fma(w, c2, sm);
   if constexpr (INSTEP) {
     double brx;
@@ -702,7 +737,7 @@ struct Wave {
 template <int NU>
 struct TightBound {
   static constexpr double R = 0x1.0p-20, B = 0x1.0p-21, Dmax = 0.9 * 0x1.0p-9, gm1 = 1.02 * NU * Dmax;
-  static constexpr double G = 1.02 * NU, kap = (NU + 1) * R, Bmax = 0.9 * B;
+  static constexpr double G = 1.02 * NU, kap = (NU + 1) * R;  // (the limit on rb is the lane's: Series::bmax)
   static_assert(NU * Dmax < 0.035, "exp(x) - 1 <= 1.02 x needs x < 0.035");
 };
 
@@ -724,11 +759,12 @@ __device__ __forceinline__ void wave_begin(Wave &W, bool active, const Lane &L, 
   const double dk = 1.2 * K.V_ref * K.h * L.kia;
   // W.never: what tight_needs_guard's two figures are AT LEAST, whatever the state — |V_l - v| ranges over half the table's range
   // or more, and Rh0 = hhd / x — taken at x = 1, the steady state at V_ref.  (A gate on speed alone: a lane it names keeps the
-  // guard, which is always right; a lane it misses fails the bound itself.)
+  // guard, which is always right; a lane it misses fails the bound itself.)  The limit on rmin is the lane's, as tight_needs_guard's
+  // (tight_bmax; not truncated to its high word here: rb >= rmin, so the stricter of the two figures is the one that decides).
   using TB = TightBound<NU>;
   const double dmin = __builtin_fma(__builtin_fabs(L.kh), 0.5 * (K.vl_hi - K.vl_lo), __builtin_fabs(L.boa) * TB::R);
   const double rmin = __builtin_fabs(L.hhd) * __builtin_fma(dmin, TB::G, TB::kap);
-  W.never = ballot(active && !(dmin < TB::Dmax && rmin < TB::Bmax));
+  W.never = ballot(active && !(dmin < TB::Dmax && rmin < tight_bmax(tight_rho_limit(L.bh, K))));
   W.guard_next = false;
   W.alive = ballot(active);
   W.need[0] = ballot(active && !(dk < 0x1.0p-9));
@@ -779,31 +815,34 @@ __device__ __forceinline__ unsigned long long trip_fast_ssq(const double *v, con
     }
   }
   if constexpr (!GUARD) return 0ull;
-  return ballot(!(g.rho < hi_pow2(-20))) | ballot(!(g.rho_f < hi_pow2(-21))) | ballot(!(g.del < S.lim)) | ballot(!(g.del_e < S.lim_e));
+  return ballot(!(g.rho < S.lim_rho)) | ballot(!(g.rho_f < S.lim_c1)) | ballot(!(g.del < S.lim)) | ballot(!(g.del_e < S.lim_e));
 }
 
 // Can a lane's increments reach TIGHT's guard anywhere in the NU steps that start at s?  An A-PRIORI bound from the trip's start
 // state (W0, Rh0) = (s.w, s.rx), the lane's constants and the range [vl_lo, vl_hi] of the loading table: where no lane of the wave
 // needs the guard, the trip runs without it (trip_fast_ssq, GUARD = false) and is the guarded trip's to the bit.  Returns the
-// lanes that DO need it.  Stated with R = 2^-20, B = 2^-21, Dmax = 0.9 * 2^-9 and, by induction over the trip's evaluations
-// in order, the hypotheses that every stage derivative so far has |d1'| <= 0.9 B and every increment |dlt| <= D <= Dmax:
+// lanes that DO need it.  Stated with the lane's limit on rho, Rl = min(2^-20, cbrt(2^-47 V_ref / |bh|)) (tight_rho_limit), Bl = Rl / 2,
+// the constants R = 2^-20 >= Rl, B = 2^-21 >= Bl, Dmax = 0.9 * 2^-9 and, by induction over the trip's evaluations
+// in order, the hypotheses that every stage derivative so far has |d1'| <= 0.9 Bl and every increment |dlt| <= D <= Dmax:
 //   W    every step's end and every stage multiply the carried W by exp(dlt) to 4e-14 (the short series' truncation), so at any
 //        stage of the trip W = W0 (1 + om) with |om| <= exp(NU D) - 1 + 1e-12 <= 1.02 NU D  (NU D <= NU Dmax < 0.035);
-//   rho  a half-step stage's rho is a d1', the full-step stage's 2 c1, the step's end t1/3 with |t1| <= 6 max|d1'|: all <= 0.9 R;
+//   rho  a half-step stage's rho is a d1', the full-step stage's 2 c1, the step's end t1/3 with |t1| <= 6 max|d1'|: all <= 0.9 Rl
+//        (<= 0.9 R, which is all the lines below use: where Rl is the smaller the hypotheses are tighter and nothing else changes);
 //   Rh   moves by (1 + q) per step, |q| <= |rho| (1 + |rho|): over NU - 1 steps Rh = Rh0 (1 + rr), |rr| < NU 0.9 R (1 + 1e-5);
 //   d0   = vl - vr W before the damping pass: |d0| <= max(|vl_hi - p|, |vl_lo - p|) + |p| gm1 =: D0,  p = vr W0, gm1 = 1.02 NU Dmax;
-//        the pass, d0 -= W (d0 - brx d1') with |brx| <= |bh| (1 + 2 R): |d0| <= D0 + Wm (D0 + |bh| B),  Wm = (1 + gm1) |W0|;
+//        the pass, d0 -= W (d0 - brx d1') with |brx| = |bh (1 - rho)| <= |bh| (1 + R): |d0| <= D0 + Wm (D0 + |bh| B),  Wm = (1 + gm1) |W0|;
 //   dlt  = dk - rho (b/a) (1 - rho/2) (the full-step stage: - 2 c1 (b/a)(1 - c1)) with |dk| <= |kh| max|d0| — the step's end takes
 //        kh/6 times a sum of weight 6 —: |dlt| <= |kh| D0 + |b/a| R =: D.  Half-step stages: |khh| = |kh|/2 and |rho| <= 0.9 B: <= D/2;
 //   d1'  = Rh - W xr, xr = xh (1 + dl) with dl in {0, a1, b1, 2 c1}, |dl| <= 0.9 R.  With c = Rh0 - W0 xh (the cancellation kept:
 //        |Rh0| + |W0 xh| is thirty times too crude):  d1' = c + Rh0 rr - W0 xh (om + dl + om dl), and |W0 xh| <= |Rh0| + |c|, so
 //        |d1'| <= |c| + (|Rh0| + |c|) (1.02 NU D + (NU + 1) R)    [0.9 (NU + 1.03 (1 + 1e-5)) <= NU + 1].
-// D < Dmax and that last bound < 0.9 B close the induction: |dlt| < 0.9 * 2^-9 (half-step stages 0.9 * 2^-10), |c1| < 0.9 * 2^-21,
-// every |rho| < 0.9 * 2^-20 in exact arithmetic; float64 rounding of the step and of these dozen operations is 1e-13 of that.
+// D < Dmax and that last bound < 0.9 Bl (bmax: Series::bmax, the one per-lane figure) close the induction: |dlt| < 0.9 * 2^-9
+// (half-step stages 0.9 * 2^-10), |c1| < 0.9 Bl, every |rho| < 0.9 Rl in exact arithmetic — the guard's own thresholds
+// (trip_fast_ssq) with a tenth to spare; float64 rounding of the step and of these dozen operations is 1e-13 of that.
 // Every quantity enters through its absolute value, so no sign of a constant is assumed, and a NaN anywhere makes a compare
 // false: that lane needs the guard — today's path, whose guard lets NaN pass.
 template <bool DAMP, int NU>
-__device__ __forceinline__ unsigned long long tight_needs_guard(const State &s, const Lane &L, const Wave &W) {
+__device__ __forceinline__ unsigned long long tight_needs_guard(const State &s, const Lane &L, const Wave &W, float bmax) {
   using TB = TightBound<NU>;
   constexpr double R = TB::R, B = TB::B, Dmax = TB::Dmax, gm1 = TB::gm1;
   const double p = L.vrw * s.w;
@@ -812,7 +851,7 @@ __device__ __forceinline__ unsigned long long tight_needs_guard(const State &s, 
   if (DAMP) D0 = __builtin_fma((1.0 + gm1) * __builtin_fabs(s.w), __builtin_fma(__builtin_fabs(L.bh), B, D0), D0);
   const double D = __builtin_fma(__builtin_fabs(L.kh), D0, __builtin_fabs(L.boa) * R);
   const double rb = __builtin_fma(__builtin_fabs(s.rx) + __builtin_fabs(c), __builtin_fma(D, TB::G, TB::kap), __builtin_fabs(c));
-  return ballot(!(D < Dmax)) | ballot(!(rb < TB::Bmax));
+  return ballot(!(D < Dmax)) | ballot(!(hi_as_float(rb) < bmax));
 }
 
 // samples completed by a trip of NU steps starting at chunk step r (dv[j]: the steps' V-derivative sums).  S1: every step
@@ -869,7 +908,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
   constexpr bool HELD = INSTEP && NU > 2 && !UNGUARD;  // the guarded loop of whole in-step trips
   set_tier<T>(L);
   Series S;
-  if constexpr (INSTEP) S = make_series<!UNGUARD>(L);
+  if constexpr (INSTEP) S = make_series<!UNGUARD>(L, K);
   const bool held = HELD && (W.never & W.alive) != 0;  // (loop-invariant: W.never is read again only where a lane dies)
   for (; r + NU <= nsteps; r += NU) {
     const unsigned long long deadmask = WANT_SSQ ? ballot(ssq > thr) : 0ull;  // NaN compares false: such a lane runs on
@@ -887,7 +926,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
     if constexpr (UNGUARD) {
       // no alive lane can reach the guard from here: the trip without it — no saved state, nothing to compare afterwards, and
       // the branch back waits for nothing the trip computed.  The sum joins ssq as the guarded trip's does.
-      if ((tight_needs_guard<DAMP, NU>(s, L, W) & W.alive) != 0) {
+      if ((tight_needs_guard<DAMP, NU>(s, L, W, S.bmax) & W.alive) != 0) {
         W.guard_next = true;
         return r;
       }
