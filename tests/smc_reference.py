@@ -15,7 +15,7 @@ Engine.draws the sampler's normals, uniform and gamma variate of a (seed, partic
     move       step k of stage s (`steps` per stage): iteration s steps + k + 1; the normals of slots 0 and 1 (Box-Muller: z0, z1
                = sqrt(-2 log u53(w0, w1)) (cos, sin)(2 pi u53(w2, w3))) and the uniform of slot 2: Engine.draws' z and u.
     resampling one uniform per stage: u53(w0, w1) of the counter (2^32 - 1, 2^32 - 1, stage, 4), the particle no run can hold.
-    sigma^2    Engine.draws' gamma variate of iteration `stages steps + 1` (the library's; not restated here).
+    sigma^2    Engine.draws' gamma variate of iteration `stages steps + 1` (specified in tests/variates_reference.py).
 
 One stage at the temperature beta (steps 2 to 4 of the algorithm):
     lmax = the largest finite l, w_j(delta) = exp(delta (l_j - lmax)), 0 for l_j = -inf.
