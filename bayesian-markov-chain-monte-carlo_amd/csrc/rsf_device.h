@@ -202,6 +202,18 @@ __device__ __forceinline__ void resync_t(State &s, const Lane &L, const Consts &
   eval_full_t<DAMP, T>(s, L, K);
 }
 
+// ms from the incremental tiers' (W, Rh): the inverse of eval_full on the scaled state,
+//     ms = (log w - tc + (b/a) log x) / kia,   x = hhd / Rh,  w = W / kvk with damping.
+// The in-step TIGHT trips do not carry ms (rk4_tight, INSTEP; Wave::ms_stale): whoever reads it after them forms it here first.
+// Every constant is formed where it is used (local_value), so nothing of this is live through a loop.  Measured against long
+// double on the lanes of tests/test_ms_free.py (the NumPy restatement): ms comes back within 1.04 ulp.
+template <bool DAMP>
+__device__ __forceinline__ void rebuild_ms(State &s, const Lane &L) {
+  const double lx = fm::log(local_value(L.hhd) * fm::rcp(s.rx));
+  const double lw = fm::log(DAMP ? s.w * fm::rcp(local_value(L.kvk)) : s.w);
+  s.ms = (__builtin_fma(local_value(L.boa), lx, lw) - local_value(L.tc)) * fm::rcp(local_value(L.kia));
+}
+
 // (w', 1/x') at (ms + dms, x1 = x + dx) from (w, rx) at (ms, x).  With rho = dx/x (= dtheta/theta) and
 // dlt = dk - (b/a) log1p(rho), dk = dmu/a = kia*dms:   w' = w exp(dlt),   1/x' = (1/x)/(1 + rho),
 // by short series — the same function of (ms', x') to rounding inside the tier's guard region:
@@ -277,6 +289,14 @@ __device__ __forceinline__ bool calm_enough(const Guard &g) {
 constexpr int kResync = 512;  // power of two; every trip length below divides it.  (128 until round 3: 0.7 instructions per step.
                               // Four roundings per step on w make 5e-15 relative over 512 steps.)  Not at a chunk's first step: the
                               // state arrives there from a full evaluation or from the previous chunk's steps, never stale.
+// The resync is the forward kernel's, the lockstep driver's and the NARROW / WIDE loops' of the sampler.  The sampler's in-step
+// TIGHT trips (rk4_tight, INSTEP) have none: there (W, Rh) is a plain two-variable float64 recurrence and ms is not carried at
+// all (rebuild_ms where somebody reads it).  The anchor injected more than it removed: only w was anchored (x is rebuilt from Rh),
+// and to an ms ~ 6 Dc that one fma per step had rounded 512 times — each rounding, scaled by kia, 4e-15 in log w, against the
+// 1e-16 of each of the four roundings the step puts on w itself.  Measured against the extended-precision RK4 (tests/test_ms_free.py:
+// 2000 steps at h = 0.025 and 4000 at h = 0.0125, Dc 300 .. 5000, one and three parameters, damping on and off), largest relative
+// error over the lanes, resynced form -> plain recurrence:  w 2.6e-13 .. 4.4e-13 -> 1.2e-14 .. 2.0e-14,  Rh 0.9e-14 .. 2.6e-14 ->
+// 0.5e-14 .. 1.0e-14,  the sum of squares 0.5e-13 .. 2.6e-13 -> 1.5e-14 .. 2.8e-14.
 
 // Both step functions return the weighted sum of the V derivatives, k1 + 2 k2 + 2 k3 + k4, IN UNITS OF vk (rhs_tail /
 // rhs_tight): the velocity increment of the step is (h/6) vk = L.h6v times it.  V itself never feeds back into the RHS, so the hot loop does not carry it: with one
@@ -544,7 +564,7 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
     const double rho = t1 * (1.0 / 3.0);  // (h/6Dc)/x times the unscaled sum
     tight_incr<T, false>(rho, L.kh6 * t0, L, s.w, w, q, g);
   }
-  s.ms = __builtin_fma(K.h6, t0, s.ms);
+  if constexpr (!INSTEP) s.ms = __builtin_fma(K.h6, t0, s.ms);  // (the in-step trips leave ms behind: rebuild_ms)
   s.w = w;
   s.rx = __builtin_fma(Rh, q, Rh);  // x' = x (1 + rho), exact to rounding for |rho| < 2^-20; like w, resynced
   if constexpr (INSTEP) {
@@ -731,6 +751,9 @@ struct Wave {
   unsigned long long never;
   bool guard_next;  // the bound just failed at this trip: one guarded trip before it is asked again (integrate_multi, UNGUARD)
   uint32_t unguarded;  // the wave-steps among steps[TIGHT] whose trip ran without the guard (tight_needs_guard)
+  // s.ms is stale: in-step TIGHT trips have run since it was last formed (they do not carry it: rk4_tight, INSTEP).  Set by the
+  // in-step loops of integrate_multi; whoever is about to read ms forms it from (W, Rh) first (rebuild_ms) and clears this.
+  bool ms_stale;
 };
 
 // the constants of tight_needs_guard, for trips of NU steps
@@ -766,6 +789,7 @@ __device__ __forceinline__ void wave_begin(Wave &W, bool active, const Lane &L, 
   const double rmin = __builtin_fabs(L.hhd) * __builtin_fma(dmin, TB::G, TB::kap);
   W.never = ballot(active && !(dmin < TB::Dmax && rmin < tight_bmax(tight_rho_limit(L.bh, K))));
   W.guard_next = false;
+  W.ms_stale = false;
   W.alive = ballot(active);
   W.need[0] = ballot(active && !(dk < 0x1.0p-9));
   W.need[1] = ballot(active && !(dk < 0x1.0p-7));
@@ -919,9 +943,11 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
     double obs[NOBS], dv[INSTEP ? 1 : NU];
 #pragma unroll
     for (int j = 0; j < NOBS; ++j) obs[j] = (WANT_SSQ && S1) ? ld[r + j] : 0.0;
-    if (r >= W.next_resync) {
-      resync_t<DAMP, T>(s, L, K);
-      W.next_resync = (r & ~(kResync - 1)) + kResync;
+    if constexpr (!INSTEP) {  // (the in-step trips carry (W, Rh) alone, with nothing to anchor them to: see kResync)
+      if (r >= W.next_resync) {
+        resync_t<DAMP, T>(s, L, K);
+        W.next_resync = (r & ~(kResync - 1)) + kResync;
+      }
     }
     if constexpr (UNGUARD) {
       // no alive lane can reach the guard from here: the trip without it — no saved state, nothing to compare afterwards, and
@@ -932,6 +958,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
       }
       double usum = 0.0;
       trip_fast_ssq<DAMP, NU, false>(v, obs, ld + r, L, S, K, s, usum);
+      W.ms_stale = true;
       W.steps[T] += NU;
       W.unguarded += NU;
       W.lane_steps += NU * (uint32_t)__builtin_popcountll(W.alive);
@@ -956,6 +983,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
         s = save;
         if constexpr (INSTEP) {
           tsum = 0.0;  // the cold trip's samples instead, straight onto the running sum
+          rebuild_ms<DAMP>(s, L);  // (the trips before this one left ms behind; the cold steps start from it)
           trip_cold_ssq<DAMP, T, NU>(v, ld + r, L, K, s, ssq);
         } else {
           trip_cold<DAMP, T, NU>(v, L, K, s, dv);
@@ -966,8 +994,10 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
       W.full_run = 0;
       W.calm = 0;
     }
-    if constexpr (INSTEP) ssq += tsum;
-    else emit_trip<WANT_SSQ, WANT_ACC, S1, NU>(dv, obs, ld, r, s, em, L, K, k0, ssq, active, acc_out, stride);
+    if constexpr (INSTEP) {
+      ssq += tsum;
+      W.ms_stale = true;  // (a lane that went through the cold trip holds its ms; the others do not)
+    } else emit_trip<WANT_SSQ, WANT_ACC, S1, NU>(dv, obs, ld, r, s, em, L, K, k0, ssq, active, acc_out, stride);
     const bool died = HELD && (deadmask & W.alive) != 0;
     W.alive &= ~deadmask;
     if constexpr (T != TIGHT) {
@@ -1118,6 +1148,16 @@ __device__ __forceinline__ void integrate_tiers(const double *lds, const double 
   bool scaled = false;      // s.rx holds Rh = hhd / x and s.w holds W (the incremental tiers' state) rather than 1 / x and w
   while (r < nsteps && W.alive != 0) {
     const int tier = wave_tier(W);
+    if constexpr (INSTEP) {
+      // in-step trips have run and something else comes next (another tier, the chunk's odd last step): ms from (W, Rh) before
+      // a cold step, a resync or the FULL tier reads it, and the resync interval counted from here, where ms and (W, Rh) agree.
+      // Out of line of the in-step loops: their register allocation does not see it.
+      if (W.ms_stale && (tier != TIGHT || nsteps - r == 1)) {
+        rebuild_ms<DAMP>(s, L);  // (scaled: only the incremental tiers set the flag)
+        W.ms_stale = false;
+        W.next_resync = (r & ~(kResync - 1)) + kResync;
+      }
+    }
     if (tier == FULL) {
       if (scaled) { tier_leave<DAMP, WIDE>(s, L); scaled = false; }
       r = integrate_full<DAMP, WANT_SSQ, WANT_ACC, S1>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
@@ -1130,6 +1170,12 @@ __device__ __forceinline__ void integrate_tiers(const double *lds, const double 
     else if (tier == TIGHT) r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, TIGHT, S1, NUT, INSTEP>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
     else if (tier == NARROW) r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, NARROW, S1, kNarrowUnroll>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
     else r = integrate_tier<DAMP, WANT_SSQ, WANT_ACC, WIDE, S1, kWiderUnroll>(lds, ld, K, L, k0, kn, r, nsteps, s, em, ssq, thr, active, acc_out, stride, W);
+  }
+  if constexpr (INSTEP) {
+    if (scaled && W.ms_stale && k0 + kn < K.nout) {  // the next chunk may start with anything; after the last one nobody reads ms
+      rebuild_ms<DAMP>(s, L);
+      W.ms_stale = false;
+    }
   }
   if (scaled) tier_leave<DAMP, WIDE>(s, L);
 }
