@@ -26,11 +26,11 @@ import numpy as np
 if __package__:
     from . import _figures
     from ._abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from .engine import Engine, _host, bayes_factor, law_name, state_law_of, whole_islands  # noqa: F401
+    from .engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, whole_islands  # noqa: F401
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     from _abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from engine import Engine, _host, bayes_factor, law_name, state_law_of, whole_islands  # noqa: F401
+    from engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, whole_islands  # noqa: F401
 
 
 @contextlib.contextmanager
@@ -220,11 +220,28 @@ class MCMC:
         """the model's state evolution law, "aging" or "slip" """
         return state_law_of(self.model)
 
+    def _observable(self):
+        """the series the model returns and `data` holds: "acc", "mu", "theta" or "velocity" """
+        return observable_of(self.model)
+
+    def _split(self):
+        """None, or what sends the model through the plain solve's sums of squares (Engine.law_ssq_fn) in place of the fused
+        kernels, which integrate the ageing law and fit the acceleration: the slip law, or another observable under either law"""
+        if self._law() == "slip":
+            return "state_law='slip'"
+        return None if self._observable() == "acc" else f"observable={self._observable()!r}"
+
+    def _ssq_fn(self, eng, data):
+        return eng.law_ssq_fn(self._law(), data, observable=self._observable())
+
     def _ageing_only(self, what):
         """`what` runs kernels that integrate the ageing law: refuse a model with another law instead of running the ageing law"""
         if self._law() != "aging":
             raise NotImplementedError(f"{what} integrates the ageing law only and the model's state_law is {self._law()!r}: under the slip "
                                       "law quadrature, compare_laws, sample_smc and sample_dr run")
+        if self._observable() != "acc":
+            raise NotImplementedError(f"{what} fits the acceleration only and the model's observable is {self._observable()!r}: on another "
+                                      "observable quadrature, compare_laws, sample_smc, sample_dr and SSqcalc run")
 
     def _init_chains(self, eng, q0, seed=0, chain_offset=0, adapt_mode=None):
         self._ageing_only("the fused sampler (sample, sample_batched and the reference's sub-methods)")
@@ -255,8 +272,8 @@ class MCMC:
             return np.sum((acc.reshape(1, -1) - np.asarray(self.data, dtype=np.float64).reshape(1, -1)) ** 2, axis=1, keepdims=True)
         eng = self._engine()
         dc = float(np.asarray(self.model.Dc, dtype=np.float64).reshape(-1)[0])
-        if self._law() == "slip":
-            return eng.law_ssq_fn("slip", np.asarray(self.data, dtype=np.float64).reshape(-1))([[dc]]).reshape(1, 1)
+        if self._split():
+            return self._ssq_fn(eng, np.asarray(self.data, dtype=np.float64).reshape(-1))([[dc]]).reshape(1, 1)
         ssq, _ = eng.forward([dc], data=np.asarray(self.data, dtype=np.float64).reshape(-1), want_ssq=True, want_acc=False)
         return ssq.reshape(1, 1)
 
@@ -556,11 +573,12 @@ class MCMC:
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         with Engine(mem=mem, device=device) as eng:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
-            if self._law() == "slip":  # the split path: the GPU's weights, resampling, proposals and accept tests on law_forward's SSq
+            if self._split():  # the split path: the GPU's weights, resampling, proposals and accept tests on the plain solve's SSq
                 if int(replicates) > 1:
                     raise NotImplementedError("sample_smc(replicates > 1) runs the batched kernels, which integrate the ageing law; the model's "
-                                              "state_law is 'slip'")
-                res = eng.smc_from_ssq(eng.law_ssq_fn("slip", data), lo, hi, int(n_particles), 0.5 * eng.nout, seed=seed, offset=offset,
+                                              "state_law is 'slip'" if self._law() == "slip" else
+                                              f"sample_smc(replicates > 1) runs the batched kernels, which fit the acceleration; the model's {self._split()}")
+                res = eng.smc_from_ssq(self._ssq_fn(eng, data), lo, hi, int(n_particles), 0.5 * eng.nout, seed=seed, offset=offset,
                                        ess_fraction=ess_fraction, steps=steps, max_stages=max_stages)
                 eng.sync()
                 return self._smc_pool(res)
@@ -723,8 +741,8 @@ class MCMC:
         frozen for the kept iterations: the nburn // iters_per_launch launches that lie wholly inside the burn-in adapt.  The target is the n0 = 0 posterior
         pi(q) ~ 1_box SSq^-N/2, sigma^2 drawn afterwards from its conditional at each kept state's own Philox iteration.  A model with
         state_law="slip" runs the split path (Engine.dr_from_ssq on Engine.law_forward's sums of squares): factor is then a (d, d)
-        array, start 'qstart' or an array, and nothing adapts: adapt=True raises there.  adapt=None (the default) is True under the
-        ageing law and False under the slip law; the pool's stats["adapt"] says which ran.  nburn:
+        array, start 'qstart' or an array, and nothing adapts: adapt=True raises there; a model whose observable is not 'acc' runs
+        that path under either law (Engine.law_observe's sums).  adapt=None (the default) is True on the fused path and False on the split one; the pool's stats["adapt"] says which ran.  nburn:
         iterations dropped, by default n_iter // 2; every thin-th of the others is kept.  Returns a PosteriorPool; its stats carry
         both stages' acceptance (accepted1, accepted2, accept_rate1, accept_rate2), both out-of-box counts (out_of_bounds,
         out_of_bounds2), stuck, n_solves — the forward solves spent — and the factor in use at the end (chol)."""
@@ -741,15 +759,15 @@ class MCMC:
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
         d, extra = self.n_params, {}
-        slip = self._law() == "slip"
+        slip = self._split()  # "state_law='slip'", "observable='...'" or None
         if slip and adapt:
-            raise NotImplementedError("sample_dr(adapt=True) under state_law='slip': the split path (Engine.dr_from_ssq) does not adapt the "
+            raise NotImplementedError(f"sample_dr(adapt=True) under {slip}: the split path (Engine.dr_from_ssq) does not adapt the "
                                       "factor; pass adapt=False or leave it out")
         adapt = (not slip) if adapt is None else bool(adapt)
         extra["adapt"] = adapt
         if slip and (isinstance(factor, str) or (isinstance(start, str) and start == "fit")):
-            raise NotImplementedError("sample_dr under state_law='slip' takes factor as a (d, d) array and start 'qstart' or an array: the init "
-                                      "kernel and the fit integrate the ageing law")
+            raise NotImplementedError(f"sample_dr under {slip} takes factor as a (d, d) array and start 'qstart' or an array: the init "
+                                      "kernel and the fit integrate the ageing law on acceleration data")
         fit = self.fit(seed=seed, device=device) if "fit" in (start if isinstance(start, str) else "", factor if isinstance(factor, str) else "") else None
         if fit is not None:
             extra["fit"] = fit
@@ -765,8 +783,8 @@ class MCMC:
                 L = self._dr_init_factor(eng, q0[0]) if factor == "init" else np.linalg.cholesky(fit.covariance())
             else:
                 L = np.asarray(factor, dtype=np.float64).reshape(d, d)
-            if slip:  # the split path on law_forward's SSq; the factor stays as given (no adaptation)
-                res = eng.dr_from_ssq(eng.law_ssq_fn("slip", data), q0, lo, hi, L, n_iter, 0.5 * eng.nout, gamma=gamma, stages=stages, seed=seed,
+            if slip:  # the split path on the plain solve's SSq; the factor stays as given (no adaptation)
+                res = eng.dr_from_ssq(self._ssq_fn(eng, data), q0, lo, hi, L, n_iter, 0.5 * eng.nout, gamma=gamma, stages=stages, seed=seed,
                                       offset=chain_offset, keep=n_iter - nburn, thin=thin)
                 std2 = res.std2(engine=eng, kept=True)
                 eng.sync()
@@ -792,10 +810,10 @@ class MCMC:
         eng = Engine(mem=mem, device=device)
         try:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
-            if self._law() == "slip":  # the same two stages, the nodes solved by law_forward
+            if self._split():  # the same two stages, the nodes solved by law_forward or law_observe
                 if self.n_params != 1:
-                    raise NotImplementedError("quadrature under state_law='slip' is one-parameter (Dc)")
-                res = eng.grid_posterior(data, lo, hi, n=n, coords=coords, window_sd=window_sd, ssq_fn=eng.law_ssq_fn("slip", data))
+                    raise NotImplementedError(f"quadrature under {self._split()} is one-parameter (Dc)")
+                res = eng.grid_posterior(data, lo, hi, n=n, coords=coords, window_sd=window_sd, ssq_fn=self._ssq_fn(eng, data))
             else:
                 res = eng.grid_posterior(data, lo, hi, n=n, coords=coords, window_sd=window_sd)
             res.q, res.std2 = res.draw(int(n_draws), seed) if int(n_draws) > 0 else (None, None)

@@ -6,16 +6,17 @@ solve runs on the GPU through the C ABI (rsf_forward_batch) as a fixed-step RK4 
 (`substeps` steps per output interval) instead of the reference's SciPy dop853 call.  DESIGN.md
 states the resulting tolerance ladder against the reference trajectory.
 
-Additive surface: `substeps`, `precision`, `integrator`, `loading`, `state_law`, `evaluate_batch(dc, a=None, b=None)`.
+Additive surface: `substeps`, `precision`, `integrator`, `loading`, `state_law`, `observable`, `noise_sd`,
+`evaluate_batch(dc, a=None, b=None)`, `trajectory(dc=None, a=None, b=None)`.
 """
 import zlib
 
 import numpy as np
 
 if __package__:
-    from .engine import Engine, check_law_options
+    from .engine import Engine, check_law_options, observable_of
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
-    from engine import Engine, check_law_options
+    from engine import Engine, check_law_options, observable_of
 
 # RateStateModel.py:5-11
 A = 0.011
@@ -54,6 +55,12 @@ class RateStateModel:
         # state evolution law, "aging" (the reference's; "ageing" is accepted) or "slip".  float64 RK4 only
         self.loading = None
         self.state_law = "aging"
+        # additive: the series evaluate() returns and the samplers fit — "acc" (the reference's acceleration), "mu" (or "friction":
+        # what a laboratory records), "theta" (or "state") or "velocity" (or "V") — and, for the observables other than "acc", the
+        # standard deviation of evaluate()'s additive noise (the reference's |acc| N(0, 1) would bury a friction of 0.6 under 0.6).
+        # Another observable than "acc" runs the plain float64 RK4 (Engine.law_observe) under either law
+        self.observable = "acc"
+        self.noise_sd = 0.0
         self._engine = None
         self._engine_key = None
 
@@ -68,7 +75,7 @@ class RateStateModel:
     def _model_key(self):
         return (self.a, self.b, self.mu_ref, self.V_ref, self.k1, self.t_start, self.t_final, self.num_tsteps, self.delta_t,
                 self.mu_t_zero, bool(self.RadiationDamping), int(self.substeps), self.precision, self.integrator, self._loading_key(),
-                self.state_law)
+                self.state_law, self.observable)
 
     def engine(self):
         """Host-memory Engine bound to the HIP library, re-armed when an attribute changed."""
@@ -95,23 +102,47 @@ class RateStateModel:
     # ---- reference surface --------------------------------------------------------------
     def evaluate(self):
         """→ (t, acc, acc_noise); acc_noise = acc + |acc|·N(0,1) from the global NumPy RNG
-        (RateStateModel.py:392), so a seeded caller sees the reference's draw order."""
+        (RateStateModel.py:392), so a seeded caller sees the reference's draw order.  With another `observable` than "acc":
+        (t, series, series + noise_sd·N(0,1)) from the same RNG."""
         if self.Dc is None:
             raise ValueError("RateStateModel.Dc must be set before evaluate()")
         _, acc = self._forward([_scalar(self.Dc)])
         acc = np.ascontiguousarray(acc[:, 0])
+        if observable_of(self) != "acc":  # the chosen series + noise_sd N(0, 1); no variate is drawn at noise_sd = 0
+            sd = float(self.noise_sd)
+            noisy = acc + sd * np.random.randn(acc.shape[0]) if sd != 0.0 else acc.copy()
+            return self.time_axis(), acc, noisy
         acc_noise = acc + 1.0 * np.abs(acc) * np.random.randn(acc.shape[0])
         return self.time_axis(), acc, acc_noise
 
     # ---- batched surface (additive) -----------------------------------------------------
     def evaluate_batch(self, dc, a=None, b=None):
-        """Clean acceleration for C parameter sets in one launch → ndarray (C, nout)."""
+        """The clean series (the acceleration, or the model's observable) for C parameter sets in one launch → ndarray (C, nout)."""
         _, acc = self._forward(np.asarray(dc, dtype=np.float64).reshape(-1), a=a, b=b)
         return np.ascontiguousarray(acc.T)
 
     def _forward(self, dc, a=None, b=None):
         """the clean series under the model's loading history and state law: the tier kernels (rsf_forward_batch) for the ageing
-        law, the plain float64 RK4 of rsf_law_forward for the slip law"""
-        if check_law_options(self) == "slip":
+        law, the plain float64 RK4 of rsf_law_forward for the slip law; the model's observable, if it is not the acceleration, by
+        rsf_law_observe under either law"""
+        law = check_law_options(self)
+        if observable_of(self) != "acc":
+            return self.engine().law_observe(law, self.observable, dc, a=a, b=b, want_series=True)
+        if law == "slip":
             return self.engine().law_forward("slip", dc, a=a, b=b, want_acc=True)
         return self.engine().forward(dc, a=a, b=b, want_acc=True)
+
+    def trajectory(self, dc=None, a=None, b=None):
+        """The four clean series of the state-law solve under the model's loading history and state law → dict(acc, mu, theta,
+        velocity), each (nout,) for a scalar dc (None: the model's Dc) or (C, nout) for C parameter sets: one Engine.law_observe
+        call each, whatever the model's own observable."""
+        law = check_law_options(self)
+        if dc is None and self.Dc is None:
+            raise ValueError("RateStateModel.Dc must be set before trajectory()")
+        one = dc is None or np.ndim(dc) == 0
+        q = np.asarray([_scalar(self.Dc if dc is None else dc)] if one else dc, dtype=np.float64).reshape(-1)
+        eng, out = self.engine(), {}
+        for name in ("acc", "mu", "theta", "velocity"):
+            series = np.asarray(eng.law_observe(law, name, q, a=a, b=b, want_series=True)[1])
+            out[name] = np.ascontiguousarray(series[:, 0] if one else series.T)
+        return out

@@ -322,6 +322,12 @@ LAW_PROTOTYPES = {
 }
 LAW_AGEING, LAW_SLIP = 0, 1  # RSF_LAW_AGEING, RSF_LAW_SLIP
 LAWS = {"aging": LAW_AGEING, "ageing": LAW_AGEING, "slip": LAW_SLIP}
+# include/rsf_observe.h: the observable of the state-law solve; exported by librsf_hip.so only, bound by load()
+OBSERVE_PROTOTYPES = {
+    "rsf_law_observe": (c_int, [c_void_p, c_int32, c_int32, c_int64, _P, _P, _P, _P, _P, _P]),
+}
+OBS_ACC, OBS_MU, OBS_THETA, OBS_VELOCITY = 0, 1, 2, 3  # RSF_OBS_ACC, RSF_OBS_MU, RSF_OBS_THETA, RSF_OBS_VELOCITY
+OBSERVABLES = {"acc": OBS_ACC, "mu": OBS_MU, "friction": OBS_MU, "theta": OBS_THETA, "state": OBS_THETA, "velocity": OBS_VELOCITY, "V": OBS_VELOCITY}
 MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
 
 
@@ -370,7 +376,7 @@ def load():
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
                       SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
-                      DR_PROTOTYPES, LAW_PROTOTYPES):
+                      DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

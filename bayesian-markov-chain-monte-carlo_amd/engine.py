@@ -140,15 +140,35 @@ def state_law_of(model):
     return law_name(getattr(model, "state_law", "aging"))
 
 
+_OBSERVABLE_NAMES = {_abi.OBS_ACC: "acc", _abi.OBS_MU: "mu", _abi.OBS_THETA: "theta", _abi.OBS_VELOCITY: "velocity"}
+
+
+def observable_name(observable):
+    """'acc', 'mu', 'theta' or 'velocity' of an observable's name ('friction', 'state' and 'V' are accepted)"""
+    if not isinstance(observable, str) or observable not in _abi.OBSERVABLES:
+        raise ValueError(f"observable is 'acc', 'mu' (or 'friction'), 'theta' (or 'state') or 'velocity' (or 'V'), not {observable!r}")
+    return _OBSERVABLE_NAMES[_abi.OBSERVABLES[observable]]
+
+
+def observable_of(model):
+    """The series the model returns and is fitted to: "acc" (the default, the reference's), "mu", "theta" or "velocity"."""
+    return observable_name(getattr(model, "observable", "acc"))
+
+
 def check_law_options(model):
-    """The slip law and a caller's loading history run the float64 RK4 only → the model's law."""
-    law = state_law_of(model)
+    """The slip law, a caller's loading history and an observable other than the acceleration run the float64 RK4 only → the
+    model's law."""
+    law, obs = state_law_of(model), observable_of(model)
     integrator, precision = getattr(model, "integrator", "rk4"), getattr(model, "precision", "float64")
     for what, on in ((f"state_law={law!r}", law == "slip"), ("a custom loading history", getattr(model, "loading", None) is not None)):
         if on and integrator == "dop853":
             raise NotImplementedError(f"{what} with integrator='dop853': the adaptive steps evaluate the built-in history and the ageing law")
         if on and precision == "float32":
             raise NotImplementedError(f"{what} with precision='float32': the float32 solve runs the built-in history and the ageing law")
+    if obs != "acc" and integrator == "dop853":
+        raise NotImplementedError(f"observable={obs!r} with integrator='dop853': the observables are samples of the float64 RK4 solve (law_observe)")
+    if obs != "acc" and precision == "float32":
+        raise NotImplementedError(f"observable={obs!r} with precision='float32': the observables are samples of the float64 RK4 solve (law_observe)")
     return law
 
 
@@ -621,6 +641,7 @@ class Engine:
         _abi.check(lib, lib.rsf_create(ctypes.byref(cfg), ctypes.byref(self._ctx)))
         self.nout = None
         self.state_law = "aging"  # the model's (set_model)
+        self.observable = "acc"   # the model's (set_model)
         self.n_chains = self.n_params = None
         self.world = self.rank = 0  # set by comm_init
 
@@ -671,8 +692,10 @@ class Engine:
     def set_model(self, model, substeps=1):
         """rsf_set_model, then the model's own loading history (model.loading, if it has one: set_loading).  model.state_law
         is kept as self.state_law: the kernels of every family integrate the ageing law, so with 'slip' only law_forward and
-        the calls built on it run (_need_model)."""
+        the calls built on it run (_need_model).  model.observable is kept as self.observable in the same way: the kernels of
+        every family fit the acceleration, so with another observable only law_observe and the calls that take an ssq_fn run."""
         law = check_law_options(model)
+        observable = observable_of(model)
         m = _model_struct(model, substeps)
         _abi.check(self.lib, self.lib.rsf_set_model(self._ctx, ctypes.byref(m)))
         n = ctypes.c_int32()
@@ -680,6 +703,7 @@ class Engine:
         self.nout = n.value
         self.model_args = (model, substeps)
         self.state_law = law
+        self.observable = observable
         self.n_chains = self.n_params = None  # a new model invalidates the chains (rsf_abi.h: rsf_set_model)
         if getattr(model, "loading", None) is not None:
             try:
@@ -695,6 +719,9 @@ class Engine:
         if not law_aware and getattr(self, "state_law", "aging") != "aging":
             raise NotImplementedError(f"this call integrates the ageing law only, and the model's state_law is {self.state_law!r}: "
                                       "the slip law runs through law_forward and the calls that take an ssq_fn")
+        if not law_aware and getattr(self, "observable", "acc") != "acc":
+            raise NotImplementedError(f"this call fits the acceleration only, and the model's observable is {self.observable!r}: "
+                                      "another observable runs through law_observe and the calls that take an ssq_fn")
 
     # -- the loading history and the state law (include/rsf_law.h) ---------------------------------------
     def _law_fn(self, name):
@@ -763,16 +790,54 @@ class Engine:
         _abi.check(self.lib, self._law_fn("rsf_law_forward")(self._ctx, int(law), C, self._ptr(dc), self._ptr(a), self._ptr(b), self._ptr(data), self._ptr(ssq), self._ptr(acc)))
         return ssq, acc
 
-    def law_ssq_fn(self, law, data):
+    # -- the observable of the state-law solve (include/rsf_observe.h) -----------------------------------
+    def _observe_fn(self, name):
+        """a function of include/rsf_observe.h, which librsf_hip.so alone exports"""
+        try:
+            return getattr(self.lib, name)
+        except AttributeError:
+            raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
+                                    "symbol (include/rsf_observe.h)") from None
+
+    def law_observe(self, law, observable, dc, a=None, b=None, data=None, want_ssq=False, want_series=True):
+        """rsf_law_observe: law_forward's solve, arguments and checks, → (ssq[C] | None, series[nout, C] | None) of `observable`:
+        'acc' (law_forward's results, bit for bit), 'mu' (or 'friction'), 'theta' (or 'state'), 'velocity' (or 'V'); an integer
+        goes to the library as it is.  data is a series of the same observable."""
+        self._need_model(law_aware=True)
+        if isinstance(law, str):
+            if law not in _abi.LAWS:
+                raise ValueError(f"law is 'aging' (or 'ageing') or 'slip', not {law!r}")
+            law = _abi.LAWS[law]
+        if isinstance(observable, str):
+            observable = _abi.OBSERVABLES[observable_name(observable)]
+        dc = self._in(np.atleast_1d(dc) if not hasattr(dc, "data_ptr") else dc)
+        C = int(dc.shape[0])
+        a, b, data = self._in(a), self._in(b), self._in(data)
+        if want_ssq and data is None:
+            raise ValueError("want_ssq needs data")
+        if data is not None and int(data.shape[0]) != self.nout:
+            raise ValueError(f"data has {int(data.shape[0])} entries, the model produces {self.nout}")
+        ssq = self._empty((C,)) if want_ssq else None
+        series = self._empty((self.nout, C)) if want_series else None
+        _abi.check(self.lib, self._observe_fn("rsf_law_observe")(self._ctx, int(law), int(observable), C, self._ptr(dc), self._ptr(a), self._ptr(b),
+                                                                 self._ptr(data), self._ptr(ssq), self._ptr(series)))
+        return ssq, series
+
+    def law_ssq_fn(self, law, data, observable="acc"):
         """The ssq_fn of smc_from_ssq, dr_from_ssq, grid_from_ssq and grid_posterior for the device model under `law`: points
-        (m, 1) of Dc or (m, 3) of (Dc, a, b) on the host → SSq (m,) on the host, solved by law_forward."""
+        (m, 1) of Dc or (m, 3) of (Dc, a, b) on the host → SSq (m,) on the host, solved by law_forward — or, with `data` a series
+        of another observable than 'acc', by law_observe."""
         obs = self._in(data)
+        if observable_name(observable) == "acc":
+            solve = lambda dc, a, b: self.law_forward(law, dc, a, b, data=obs, want_ssq=True, want_acc=False)[0]
+        else:
+            solve = lambda dc, a, b: self.law_observe(law, observable, dc, a, b, data=obs, want_ssq=True, want_series=False)[0]
 
         def ssq_fn(pts):
             pts = np.asarray(pts, dtype=np.float64)
             pts = pts.reshape(-1, 1) if pts.ndim < 2 else pts
             ab = [np.ascontiguousarray(pts[:, p]) for p in (1, 2)] if pts.shape[1] == 3 else [None, None]
-            return _host(self.law_forward(law, np.ascontiguousarray(pts[:, 0]), ab[0], ab[1], data=obs, want_ssq=True, want_acc=False)[0])
+            return _host(solve(np.ascontiguousarray(pts[:, 0]), ab[0], ab[1]))
 
         return ssq_fn
 
