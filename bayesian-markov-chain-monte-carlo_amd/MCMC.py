@@ -742,7 +742,7 @@ class MCMC:
         pi(q) ~ 1_box SSq^-N/2, sigma^2 drawn afterwards from its conditional at each kept state's own Philox iteration.  A model with
         state_law="slip" runs the split path (Engine.dr_from_ssq on Engine.law_forward's sums of squares): factor is then a (d, d)
         array, start 'qstart' or an array, and nothing adapts: adapt=True raises there; a model whose observable is not 'acc' runs
-        that path under either law (Engine.law_observe's sums).  adapt=None (the default) is True on the fused path and False on the split one; the pool's stats["adapt"] says which ran.  nburn:
+        that path under either law (Engine.law_observe's sums); sample_law runs such models on the fused kernel, adapting.  adapt=None (the default) is True on the fused path and False on the split one; the pool's stats["adapt"] says which ran.  nburn:
         iterations dropped, by default n_iter // 2; every thin-th of the others is kept.  Returns a PosteriorPool; its stats carry
         both stages' acceptance (accepted1, accepted2, accept_rate1, accept_rate2), both out-of-box counts (out_of_bounds,
         out_of_bounds2), stuck, n_solves — the forward solves spent — and the factor in use at the end (chol)."""
@@ -794,6 +794,44 @@ class MCMC:
             std2 = res.std2(engine=eng, kept=True)
             eng.sync()
         return self._dr_pool(res, std2, nburn, extra)
+
+    def sample_law(self, n_chains, n_iter, nburn=None, start="qstart", factor="gn", gamma=0.2, stages=2, adapt=True, seed=0, mem="device", device=-1,
+                   chain_offset=0, thin=1, iters_per_launch=16):
+        """sample_dr's sampler on the fused kernel of the state-law solve (additive; Engine.law_dr, include/rsf_law_dr.h): for ANY
+        device model — state_law "aging" or "slip", observable "acc", "mu", "theta" or "velocity", the built-in or a custom loading
+        history, d = 1 or 3 — every iteration runs inside the launch, and the factor adapts.  start="qstart": every chain at
+        qstart; an array (n_chains, d): there.  factor="gn": Engine.law_gn_factor at the start point (chain 0's for an array), the
+        Gauss-Newton proposal from one solve of 1 + d lanes, which needs no init kernel and no fit; an array (d, d): that lower
+        triangular factor.  adapt=True: the nburn // iters_per_launch launches that lie wholly inside the burn-in adapt the factor
+        (Engine.dr's adapt_launches), then it is frozen.  Everything else — the target, sigma^2, nburn, thin, the returned
+        PosteriorPool and its stats — is sample_dr's; stats["adapt"] says whether the factor adapted and stats["path"] is "law_dr"."""
+        n_chains, n_iter, ipl = int(n_chains), int(n_iter), int(iters_per_launch)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_chains < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1 or ipl < 1:
+            raise ValueError("n_chains >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1, iters_per_launch >= 1")
+        if isinstance(start, str) and start != "qstart":
+            raise ValueError(f"start is 'qstart' or an array of chains, not {start!r}")
+        if isinstance(factor, str) and factor != "gn":
+            raise ValueError(f"factor is 'gn' or a (d, d) array, not {factor!r}")
+        if not self._device_model():
+            raise TypeError("sample_law integrates the model on the device: `model` must be this package's RateStateModel")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
+        d, law, observable = self.n_params, self._law(), self._observable()
+        if isinstance(start, str):
+            q0 = np.tile(np.asarray(self.qstart, dtype=np.float64).reshape(1, d), (n_chains, 1))
+        else:
+            q0 = _host(start).reshape(-1, d)
+            if q0.shape[0] != n_chains:
+                raise ValueError(f"start holds {q0.shape[0]} chains, not {n_chains}")
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            L = eng.law_gn_factor(law, observable, q0[0], data)[0] if isinstance(factor, str) else np.asarray(factor, dtype=np.float64).reshape(d, d)
+            res = eng.law_dr(law, observable, q0, data, lo, hi, L, n_iter, gamma=gamma, stages=stages, seed=seed, offset=chain_offset,
+                             iters_per_launch=ipl, keep=n_iter - nburn, thin=thin, adapt_launches=nburn // ipl if adapt else 0)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        return self._dr_pool(res, std2, nburn, {"adapt": bool(adapt), "path": "law_dr"})
 
     def quadrature(self, n=None, n_draws=0, seed=0, coords=None, window_sd=12.0, mem="device", device=-1):
         """The exact posterior by quadrature on the GPU (additive; Engine.grid_posterior): the n0 = 0 target

@@ -328,6 +328,12 @@ OBSERVE_PROTOTYPES = {
 }
 OBS_ACC, OBS_MU, OBS_THETA, OBS_VELOCITY = 0, 1, 2, 3  # RSF_OBS_ACC, RSF_OBS_MU, RSF_OBS_THETA, RSF_OBS_VELOCITY
 OBSERVABLES = {"acc": OBS_ACC, "mu": OBS_MU, "friction": OBS_MU, "theta": OBS_THETA, "state": OBS_THETA, "velocity": OBS_VELOCITY, "V": OBS_VELOCITY}
+# include/rsf_law_dr.h: the delayed-rejection sampler under either state law and any observable; exported by librsf_hip.so only, bound
+# by load().  rsf_dr_run's and rsf_dr_ssq's arguments behind (ctx, law, observable)
+LAW_DR_PROTOTYPES = {
+    "rsf_law_dr_run": (c_int, [c_void_p, c_int32, c_int32] + DR_PROTOTYPES["rsf_dr_run"][1][1:]),
+    "rsf_law_dr_ssq": (c_int, [c_void_p, c_int32, c_int32] + DR_PROTOTYPES["rsf_dr_ssq"][1][1:]),
+}
 MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
 
 
@@ -376,7 +382,7 @@ def load():
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
                       SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
-                      DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES):
+                      DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES, LAW_DR_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -1,7 +1,7 @@
 // rsf_kernels_dr.h — two-stage delayed-rejection Metropolis over the strict box (include/rsf_dr.h; tests/dr_reference.py is the
 // specification): dr_stage1 / dr_stage2 / dr_decide2, the iteration's pieces as device functions defined ONCE, the split kernels
 // dr_propose_kernel / dr_accept_kernel around them, dr_ssq_kernel (one stage's solve alone) and dr_kernel, the fused hot path in
-// smc_move_kernel's arrangement.  Included by rsf_dr.hip only.
+// smc_move_kernel's arrangement.  Included by rsf_dr.hip and, for the chain logic around the state-law solve, by rsf_kernels_law_dr.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // rsf_kernels_observe.h — the observables of the state-law solve (include/rsf_observe.h): law_observe_kernel, law_forward_kernel's
 // plain float64 RK4 under either law with the output sample chosen by the caller: the acceleration, the friction coefficient, the
-// state variable or the slip velocity.  Included by rsf_observe.hip only.  The arithmetic of the solve is rsf_kernels_law.h's
-// law_rhs / law_step, called from here, not restated.
+// state variable or the slip velocity.  Included by rsf_observe.hip and, for the sample rule, by rsf_kernels_law_dr.h.  The
+// arithmetic of the solve is rsf_kernels_law.h's law_rhs / law_step, called from here, not restated.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,6 +17,26 @@ namespace rsfk {
 __device__ __forceinline__ double observe_residual(double s, double obs) {
 #pragma clang fp contract(off)
   return s - obs;
+}
+
+// The sample rule of an observable, defined ONCE for law_observe_kernel and the fused sampler's solve (rsf_kernels_law_dr.h):
+// sample k >= 1 from the state after the sample's last step, and its residual against obs; vprev: the V of the sample before
+__device__ __forceinline__ void observe_sample(int32_t observable, double V, double &vprev, double ms, double x, double scale, double obs,
+                                               const Consts &K, double &s, double &res) {
+  switch (observable) {
+    case RSF_OBS_ACC: {
+      // rsf::emit_at's sample and residual AS law_forward_kernel COMPILES THEM: the stored sample is the rounded product,
+      // the residual ak - obs one fma of the velocity difference (the compiler contracts emit_at's product into it).  Written
+      // out, because beside the other cases the compiler shares the rounded product instead, an ulp of SSq away.
+      const double dv = V - vprev;
+      s = dv * K.inv_dt;
+      res = __builtin_fma(dv, K.inv_dt, -obs);
+      vprev = V;
+    } break;
+    case RSF_OBS_VELOCITY: s = V; res = observe_residual(s, obs); break;
+    case RSF_OBS_MU: s = scale * ms; res = observe_residual(s, obs); break;
+    default: s = x * scale; res = observe_residual(s, obs); break;  // RSF_OBS_THETA (the host admits no other)
+  }
 }
 
 // law_forward_kernel's solve — one lane per (dc, a, b), the loading table and the observation through LDS chunk by chunk, a wave
@@ -72,20 +92,7 @@ law_observe_kernel(Consts K, int32_t observable, int64_t n, const double *__rest
         phase = 0;
         const double obs = want_ssq ? ld[ko] : 0.0;
         double s, res;                                   // the sample and its residual
-        switch (observable) {
-          case RSF_OBS_ACC: {
-            // rsf::emit_at's sample and residual AS law_forward_kernel COMPILES THEM: the stored sample is the rounded product,
-            // the residual ak - obs one fma of the velocity difference (the compiler contracts emit_at's product into it).  Written
-            // out, because beside the other cases the compiler shares the rounded product instead, an ulp of SSq away.
-            const double dv = V - vprev;
-            s = dv * K.inv_dt;
-            res = __builtin_fma(dv, K.inv_dt, -obs);
-            vprev = V;
-          } break;
-          case RSF_OBS_VELOCITY: s = V; res = observe_residual(s, obs); break;
-          case RSF_OBS_MU: s = scale * ms; res = observe_residual(s, obs); break;
-          default: s = x * scale; res = observe_residual(s, obs); break;  // RSF_OBS_THETA (the host admits no other)
-        }
+        observe_sample(observable, V, vprev, ms, x, scale, obs, K, s, res);
         if (store) series_i[(int64_t)(k0 + ko) * n] = s;
         if (want_ssq) ssq = __builtin_fma(res, res, ssq);
         ++ko;

@@ -2512,6 +2512,16 @@ class Engine:
         bit for bit (DrResult.q, .l and .chol, iter0 = the next Philox iteration); by default evidence_logtarget's.  keep: the
         trailing iterations whose states are kept (None: all), every thin-th of them → DrResult."""
         self._need_model()
+        start_l = lambda q, obs, lo, hi, shape: _host(self.evidence_logtarget(q, obs, lo, hi, np.zeros(int(q.shape[0])), shape))
+        return self._dr_drive(self.dr_run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin,
+                              adapt_launches, iter0, l0)
+
+    def _dr_drive(self, run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches,
+                  iter0, l0, ready=None):
+        """What Engine.dr and Engine.law_dr share, everything but the solve: the checks, the groups, the launches of `run`
+        (dr_run's signature) with the burn-in adaptation between them, the kept traces.  start_l(q (per, d) in this engine's
+        memory space, obs (nout,) on the host, lo, hi, shape) → the start's l of one group on the host; ready(): called after the
+        argument checks and before the first library call."""
         q0, lo, hi, d, L, n_iter, gamma, stages, shape, seed, offset, ipl, keep, thin, adapt, iter0 = self._dr_args(
             q0, lo, hi, chol, (1, 3), n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches, iter0)
         shape = 0.5 * self.nout if shape is None else shape
@@ -2524,9 +2534,11 @@ class Engine:
             raise ValueError(f"{n} chains cannot be split over {G} observation series in whole workgroups of {self.block_threads}")
         L = self._dr_factors(L, d, G).copy()
         per = n // G
+        if ready is not None:
+            ready()
         q = self._in(q0)
         if l0 is None:
-            l0 = np.concatenate([_host(self.evidence_logtarget(q[g * per:(g + 1) * per], obs[g], lo, hi, np.zeros(per), shape)) for g in range(G)])
+            l0 = np.concatenate([start_l(q[g * per:(g + 1) * per], obs[g], lo, hi, shape) for g in range(G)])
         else:
             l0 = _host(l0).reshape(-1).copy()
             if l0.shape != (n,):
@@ -2538,8 +2550,8 @@ class Engine:
         while done < n_iter:
             k = min(ipl, n_iter - done)
             adapting = launch < adapt
-            tr = self.dr_run(q, l, obs, lo, hi, L, k, counters, gamma=gamma, stages=stages, shape=shape, seed=seed, offset=offset, iter0=iter0 + done,
-                             trace=adapting or done + k > n_iter - keep)
+            tr = run(q, l, obs, lo, hi, L, k, counters, gamma=gamma, stages=stages, shape=shape, seed=seed, offset=offset, iter0=iter0 + done,
+                     trace=adapting or done + k > n_iter - keep)
             if adapting:
                 seen.append(tr[0])
                 for g in range(G):
@@ -2603,6 +2615,116 @@ class Engine:
             if k >= n_iter - keep:
                 kept.append((_host(q).copy()[None], _host(l).copy()[None]))
         return self._dr_result(q, l, counters, n_iter, kept, keep, thin, L, gamma, stages, shape, seed, offset, iter0)
+
+    # -- delayed rejection under either state law and any observable (include/rsf_law_dr.h) ------------------------------
+    def _law_dr_fn(self, name):
+        """a function of include/rsf_law_dr.h, which librsf_hip.so alone exports"""
+        try:
+            return getattr(self.lib, name)
+        except AttributeError:
+            raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
+                                    "symbol (include/rsf_law_dr.h)") from None
+
+    @staticmethod
+    def _law_codes(law, observable):
+        """names or aliases of _abi.LAWS / _abi.OBSERVABLES → their codes, law_observe's checks; integers pass through"""
+        if isinstance(law, str):
+            if law not in _abi.LAWS:
+                raise ValueError(f"law is 'aging' (or 'ageing') or 'slip', not {law!r}")
+            law = _abi.LAWS[law]
+        if isinstance(observable, str):
+            observable = _abi.OBSERVABLES[observable_name(observable)]
+        return int(law), int(observable)
+
+    def law_dr_run(self, law, observable, q, l, data, lo, hi, chol, n_iter, counters, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iter0=1,
+                   trace=False):
+        """rsf_law_dr_run: dr_run — its arguments, checks and results — with the solve under the state law `law` against `data`,
+        series of `observable` (law_observe's names, aliases or integers), under the loading table in use."""
+        self._need_model(law_aware=True)
+        law, observable = self._law_codes(law, observable)
+        n, d = self._dr_state(q, l, counters)
+        data = self._in(data)
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        tri = self._dr_pack(self._dr_factors(chol, d, G))
+        fn = self._law_dr_fn("rsf_law_dr_run")
+        tq, tl = (self._empty((int(n_iter), n, d)), self._empty((int(n_iter), n))) if trace else (None, None)
+        _abi.check(self.lib, fn(self._ctx, law, observable, n, d, self._ptr(q), self._ptr(l), self._ptr(data), G, _dp(_vec(lo, d, "lo")),
+                                _dp(_vec(hi, d, "hi")), _dp(tri), float(gamma), int(stages), float(0.5 * self.nout if shape is None else shape),
+                                int(seed), int(offset), int(iter0), int(n_iter), *(self._ptr(c) for c in counters), self._ptr(tq), self._ptr(tl)))
+        return (tq, tl) if trace else None
+
+    def law_dr_ssq(self, law, observable, y, mask, data, ssq=None):
+        """rsf_law_dr_ssq: dr_ssq under `law` against `data` of `observable` → ssq (n,), law_observe's SSq bit for bit at dr_propose's
+        y (n, d) for the chains whose mask is 1, solved in law_dr_run's arrangement.  The other entries are ssq's (by default 1)."""
+        self._need_model(law_aware=True)
+        law, observable = self._law_codes(law, observable)
+        y, mask, data = self._in(y), self._bytes(mask), self._in(data)
+        if y.ndim != 2 or tuple(mask.shape) != (int(y.shape[0]),):
+            raise ValueError("y is (n, d), mask (n,)")
+        n, d = int(y.shape[0]), int(y.shape[1])
+        G = int(data.shape[0]) if data.ndim == 2 else 1
+        fn = self._law_dr_fn("rsf_law_dr_ssq")
+        out = self._in(np.ones(n) if ssq is None else ssq)
+        out = out.clone() if hasattr(out, "clone") else out.copy()
+        _abi.check(self.lib, fn(self._ctx, law, observable, n, d, self._ptr(y), self._ptr(mask), self._ptr(data), G, self._ptr(out)))
+        return out
+
+    def law_gn_factor(self, law, observable, q, data, rel_step=1e-4):
+        """The Gauss-Newton proposal at the point q (d,), d = 1 (Dc) or 3 (Dc, a, b) → (L, cov, ssq): from ONE law_observe call of
+        1 + d lanes, q and q + rel_step q_p e_p, the Jacobian J of the series by forward differences; cov = (SSq / nout) (J^T J)^-1,
+        the Laplace covariance of the posterior at q, and L = chol((2.38^2 / d) cov), the random walk's factor.  What factor="init"
+        is for the tier kernels, without an init kernel and without a fit.  ValueError where a series is not finite or the matrix
+        has no Cholesky factor."""
+        self._need_model(law_aware=True)
+        law, observable = self._law_codes(law, observable)
+        q = np.asarray(_host(q), dtype=np.float64).reshape(-1)
+        d = q.size
+        if d not in (1, 3) or not np.isfinite(q).all() or not (q != 0.0).all() or not (math.isfinite(float(rel_step)) and float(rel_step) > 0.0):
+            raise ValueError(f"q has shape {q.shape}: a finite point (Dc,) or (Dc, a, b) without a zero, and rel_step is finite and > 0")
+        obs = _host(data).reshape(-1)
+        if obs.size != self.nout:
+            raise ValueError(f"data has {obs.size} entries, the model produces {self.nout}")
+        self._law_dr_fn("rsf_law_dr_run")  # the factor of this family's sampler: a library without it is refused here
+        h = float(rel_step) * q
+        pts = np.tile(q, (1 + d, 1))
+        pts[1:] += np.diag(h)
+        ab = [np.ascontiguousarray(pts[:, p]) for p in (1, 2)] if d == 3 else [None, None]
+        series = _host(self.law_observe(law, observable, np.ascontiguousarray(pts[:, 0]), ab[0], ab[1], want_series=True)[1])
+        if not np.isfinite(series).all():
+            raise ValueError(f"law_gn_factor: the series at q = {q.tolist()} or beside it is not finite")
+        r = series[:, 0] - obs
+        ssq = float(r @ r)
+        J = (series[:, 1:] - series[:, :1]) / h
+        try:
+            cov = (ssq / self.nout) * np.linalg.inv(J.T @ J)
+            if not np.isfinite(cov).all():
+                raise np.linalg.LinAlgError
+            L = np.linalg.cholesky((2.38 ** 2 / d) * cov)
+        except np.linalg.LinAlgError:
+            raise ValueError(f"law_gn_factor: (SSq / nout) (J^T J)^-1 at q = {q.tolist()} has no Cholesky factor (a parameter the series "
+                             "does not depend on, or a step too small for it)") from None
+        return L, cov, ssq
+
+    def law_dr(self, law, observable, q0, data, lo, hi, chol, n_iter, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iters_per_launch=16, keep=None,
+               thin=1, adapt_launches=0, iter0=1, l0=None):
+        """Engine.dr — its arguments, groups, adaptation, continuation and result, through the same driver — for the device model
+        under the state law `law` against `data`, series of `observable`: the launch is law_dr_run, and the start's l is what
+        dr_from_ssq forms, -shape log SSq in NumPy on the host from law_ssq_fn(law, data_g, observable) (-inf where SSq is not
+        finite and > 0; such a start is refused).  With adapt_launches = 0 the run is dr_from_ssq(law_ssq_fn(...), ...)'s bit for
+        bit, from the first state on."""
+        self._need_model(law_aware=True)
+        codes = self._law_codes(law, observable)
+        if codes[1] not in _OBSERVABLE_NAMES:
+            raise ValueError(f"observable is one of {sorted(_OBSERVABLE_NAMES)} (RSF_OBS_*), not {codes[1]}")
+
+        def start_l(q, obs, lo, hi, shape):
+            s = np.asarray(self.law_ssq_fn(codes[0], obs, _OBSERVABLE_NAMES[codes[1]])(_host(q)), dtype=np.float64).reshape(-1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return np.where(np.isfinite(s) & (s > 0), -shape * np.log(s), -np.inf)
+
+        run = lambda q, l, obs, lo, hi, L, k, counters, **kw: self.law_dr_run(codes[0], codes[1], q, l, obs, lo, hi, L, k, counters, **kw)
+        return self._dr_drive(run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin,
+                              adapt_launches, iter0, l0, ready=lambda: self._law_dr_fn("rsf_law_dr_run"))
 
     # -- the exact posterior on a tensor quadrature grid (include/rsf_grid.h) ------------------------------
     @staticmethod
