@@ -86,6 +86,15 @@ class PosteriorPool:
         `quantiles` is the credible band of the clean model series; it does not contain the noise, and most observations lie
         outside it when the posterior is tight.  noise_probs (each strictly inside (0, 1)) adds `noise_quantiles`, the posterior
         predictive band of an observation — the quantiles of mean_i N(y_ik, std2_i) — which is the band to overlay on the data."""
+        q, s2 = self._draws(max_draws)
+        extra = dict(loo=True, r_eff=r_eff) if loo else {}  # without loo or noise_probs the engine is called as it always was
+        if np.size(noise_probs):
+            extra["noise_probs"] = noise_probs
+        with _engine_for(engine, model, substeps) as eng:
+            return eng.predictive(q, s2, data, probs=probs, **extra)
+
+    def _draws(self, max_draws):
+        """(q (m, d), std2 (m,)) on the host: every kept draw, or the evenly strided subset of at most max_draws of them"""
         n, C, d = self.samples.shape
         q, s2 = _host(self.samples).reshape(n * C, d), _host(self.std2).reshape(n * C)
         if max_draws is not None:
@@ -94,11 +103,27 @@ class PosteriorPool:
             if int(max_draws) < n * C:
                 idx = (np.arange(int(max_draws), dtype=np.int64) * (n * C)) // int(max_draws)  # evenly strided, no RNG
                 q, s2 = q[idx], s2[idx]
-        extra = dict(loo=True, r_eff=r_eff) if loo else {}  # without loo or noise_probs the engine is called as it always was
+        return q, s2
+
+    def law_predictive(self, model, data, probs=(0.05, 0.5, 0.95), max_draws=None, engine=None, substeps=None, loo=False, r_eff=1.0,
+                       noise_probs=()):
+        """predictive — its arguments and its result — for ANY device model (Engine.law_predictive): the state law
+        (model.state_law: "aging" or "slip"), the observable `data` is a series of (model.observable: "acc", "mu", "theta" or
+        "velocity") and the loading history (model.loading) are the model's, d = 1 or 3: the checks of a pool that sample_law
+        returned.  The result also carries `law` and `observable`, the names the solve ran under."""
+        q, s2 = self._draws(max_draws)
+        law, observable = state_law_of(model), observable_of(model)
+        extra = dict(loo=True, r_eff=r_eff) if loo else {}
         if np.size(noise_probs):
             extra["noise_probs"] = noise_probs
         with _engine_for(engine, model, substeps) as eng:
-            return eng.predictive(q, s2, data, probs=probs, **extra)
+            res = eng.law_predictive(law, observable, q, s2, data, probs=probs, **extra)
+        res.update(law=law, observable=observable)
+        return res
+
+    def law_loo(self, model, data, max_draws=None, engine=None, substeps=None, r_eff=1.0):
+        """loo for any device model: law_predictive without a band and with the PSIS-LOO entries."""
+        return self.law_predictive(model, data, probs=(), max_draws=max_draws, engine=engine, substeps=substeps, loo=True, r_eff=r_eff)
 
     def joint(self, engine=None):
         """Mean, covariance (ddof = 1) and correlation matrix of the kept draws over all parameters, computed on the GPU

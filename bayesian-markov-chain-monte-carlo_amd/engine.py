@@ -718,10 +718,12 @@ class Engine:
             raise _abi.RsfError(-3, "call set_model first")
         if not law_aware and getattr(self, "state_law", "aging") != "aging":
             raise NotImplementedError(f"this call integrates the ageing law only, and the model's state_law is {self.state_law!r}: "
-                                      "the slip law runs through law_forward and the calls that take an ssq_fn")
+                                      "the slip law runs through law_forward and the calls that take an ssq_fn; the predictive checks under a law are "
+                                      "law_predictive's")
         if not law_aware and getattr(self, "observable", "acc") != "acc":
             raise NotImplementedError(f"this call fits the acceleration only, and the model's observable is {self.observable!r}: "
-                                      "another observable runs through law_observe and the calls that take an ssq_fn")
+                                      "another observable runs through law_observe and the calls that take an ssq_fn; the predictive checks of an "
+                                      "observable are law_predictive's")
 
     # -- the loading history and the state law (include/rsf_law.h) ---------------------------------------
     def _law_fn(self, name):
@@ -3076,8 +3078,8 @@ class Engine:
         return res
 
     # -- posterior predictive checks of pooled draws (include/rsf_predict.h) ---------------------
-    def _predict_args(self, q, std2, data):
-        self._need_model()
+    def _predict_args(self, q, std2, data, law_aware=False):
+        self._need_model(law_aware)
         q, std2, data = self._in(q), self._in(std2), self._in(data)
         if q.ndim == 1:
             q = q.reshape(-1, 1)
@@ -3092,12 +3094,14 @@ class Engine:
             raise ValueError(f"data has shape {tuple(data.shape)}, the model produces {self.nout} samples")
         return q, std2, data, n, int(q.shape[1])
 
-    def _predict_centers(self, center_y, center_l):
+    def _predict_centers(self, center_y, center_l, rows=None):
         c = []
         for v in (center_y, center_l):
             v = _host(v)
-            if v.shape != (self.nout,):
+            if rows is None and v.shape != (self.nout,):
                 raise ValueError(f"a centre has shape {v.shape}, the model produces {self.nout} samples")
+            if rows is not None and v.shape != (rows,):
+                raise ValueError(f"a centre has shape {v.shape}, the series has {rows} rows")
             c.append(v)
         return c
 
@@ -3106,7 +3110,11 @@ class Engine:
         predictive statistics about the centres center_y, center_l (nout,) → (PREDICT_HEAD + nout * len(PREDICT_FIELDS),)
         float64 on the host; with return_series also the series (nout, n) in this engine's memory space.  Partials of disjoint
         shards of a pool taken about the same centres add (dist.allreduce_predictive_partials)."""
-        q, std2, data, n, d = self._predict_args(q, std2, data)
+        return self._partials(lambda *a: self.lib.rsf_predict_partials(self._ctx, *a), False, q, std2, data, center_y, center_l, return_series)
+
+    def _partials(self, call, law_aware, q, std2, data, center_y, center_l, return_series):
+        """predictive_partials' and law_predictive_partials' body; call: the entry point behind its leading arguments"""
+        q, std2, data, n, d = self._predict_args(q, std2, data, law_aware)
         cy, cl = self._predict_centers(center_y, center_l)
         series = None
         if return_series:
@@ -3117,9 +3125,7 @@ class Engine:
                                   "pass fewer draws (max_draws)") from e
         out = np.empty(_abi.PREDICT_HEAD + self.nout * len(_abi.PREDICT_FIELDS))
         try:
-            _abi.check(self.lib, self.lib.rsf_predict_partials(self._ctx, n, d, self._ptr(q), self._ptr(std2), self._ptr(data),
-                                                               _dp(cy), _dp(cl), _dp(out),
-                                                               self._ptr(series)))
+            _abi.check(self.lib, call(n, d, self._ptr(q), self._ptr(std2), self._ptr(data), _dp(cy), _dp(cl), _dp(out), self._ptr(series)))
         except _abi.RsfError as e:
             if e.code == -4:  # RSF_ERR_NOMEM
                 raise _abi.RsfError(e.code, f"{e}; pass fewer draws (max_draws)") from e
@@ -3217,13 +3223,18 @@ class Engine:
         `noise_quantiles` (from noise_probs, each strictly inside (0, 1); see predictive_noise_quantiles) is the POSTERIOR
         PREDICTIVE band — where an observation lies, the inferred noise included: the one to overlay on the data.  A non-empty
         noise_probs materialises the series and adds the keys noise_probs and noise_quantiles; the default adds nothing."""
-        q, std2, data, n, d = self._predict_args(q, std2, data)
+        return self._predictive(self.predictive_partials, lambda dc, a, b: self.forward(dc, a=a, b=b)[1], False, q, std2, data, probs, center,
+                                return_series, loo, r_eff, noise_probs)
+
+    def _predictive(self, partials, solve, law_aware, q, std2, data, probs, center, return_series, loo, r_eff, noise_probs):
+        """predictive's and law_predictive's body; partials: predictive_partials or law_predictive_partials behind its law,
+        solve(dc, a, b): the series (nout, 1) at one point, for the default centre"""
+        q, std2, data, n, d = self._predict_args(q, std2, data, law_aware)
         probs, noise_probs = _probs(probs, False, True, "probs"), _probs(noise_probs, True, True, "noise_probs")
 
         if center is None:
             qm = _host(q.mean(0)).reshape(d)
-            _, acc = self.forward(qm[:1], a=qm[1:2] if d == 3 else None, b=qm[2:3] if d == 3 else None)
-            cy = _host(acc).reshape(self.nout)
+            cy = _host(solve(qm[:1], qm[1:2] if d == 3 else None, qm[2:3] if d == 3 else None)).reshape(self.nout)
             ms = float(_host(std2).mean())
             cl = -0.5 * np.log(2.0 * np.pi * ms) - (_host(data) - cy) ** 2 / (2.0 * ms)
             if not (np.isfinite(cy).all() and np.isfinite(cl).all()):
@@ -3232,7 +3243,7 @@ class Engine:
             cy, cl = center
         cy, cl = self._predict_centers(cy, cl)
         want_series = bool(return_series) or probs.size > 0 or bool(loo) or noise_probs.size > 0
-        part = self.predictive_partials(q, std2, data, cy, cl, return_series=want_series)
+        part = partials(q, std2, data, cy, cl, return_series=want_series)
         series = None
         if want_series:
             part, series = part
@@ -3247,6 +3258,52 @@ class Engine:
         if return_series:
             res["series"] = series
         return res
+
+    # -- the same checks under either state law and any observable (include/rsf_law_predict.h) -----------
+    def _law_predict_fn(self, name):
+        """a function of include/rsf_law_predict.h, which librsf_hip.so alone exports"""
+        try:
+            return getattr(self.lib, name)
+        except AttributeError:
+            raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
+                                    "symbol (include/rsf_law_predict.h)") from None
+
+    def law_predictive_partials(self, law, observable, q, std2, data, center_y, center_l, return_series=False):
+        """rsf_law_predict_partials: predictive_partials — its arguments, checks and results — with the solve under the state law
+        `law` and y the series of `observable` (law_observe's names, aliases or integers; its series bit for bit), under the loading
+        table in use.  data is a series of the same observable."""
+        self._need_model(law_aware=True)
+        law, observable = self._law_codes(law, observable)
+        return self._partials(lambda *a: self._law_predict_fn("rsf_law_predict_partials")(self._ctx, law, observable, *a), True, q, std2, data,
+                              center_y, center_l, return_series)
+
+    def series_partials(self, series, std2, data, center_y, center_l):
+        """rsf_predict_series_partials: predictive_partials' partials of a series (nout, n) that exists (law_observe's, or any), in
+        this engine's memory space with std2 (n,) and data (nout,), about the centres center_y, center_l (nout,) → (PREDICT_HEAD +
+        nout * len(PREDICT_FIELDS),) float64 on the host, bit for bit what law_predictive_partials returns for the draws that gave
+        the series.  Needs no model."""
+        x, s2, obs = self._in(series), self._in(std2), self._in(data)
+        rows, n = _series_args(x, s2, obs)
+        cy, cl = self._predict_centers(center_y, center_l, rows)
+        out = np.empty(_abi.PREDICT_HEAD + rows * len(_abi.PREDICT_FIELDS))
+        _abi.check(self.lib, self._law_predict_fn("rsf_predict_series_partials")(self._ctx, n, rows, self._ptr(x), self._ptr(s2), self._ptr(obs),
+                                                                                 _dp(cy), _dp(cl), _dp(out)))
+        return out
+
+    def law_predictive(self, law, observable, q, std2, data, probs=(), center=None, return_series=False, loo=False, r_eff=1.0, noise_probs=()):
+        """predictive — its arguments, checks and result, key for key — for a model under the state law `law` whose data is a series
+        of `observable` (law_observe's names, aliases or integers), under the loading table in use: the fused solve and reduction is
+        rsf_law_predict_partials, the default centre the series of one law_observe call at the draws' mean point, and the
+        quantiles, the PSIS-LOO entries and noise_quantiles come from the series entry points predictive uses."""
+        self._need_model(law_aware=True)
+        law, observable = self._law_codes(law, observable)
+
+        def centre(dc, a, b):
+            self._law_predict_fn("rsf_law_predict_partials")  # a library without this family is refused under its name, before any solve
+            return self.law_observe(law, observable, dc, a, b)[1]
+
+        return self._predictive(lambda *a, **kw: self.law_predictive_partials(law, observable, *a, **kw), centre, True, q, std2, data, probs, center,
+                                return_series, loo, r_eff, noise_probs)
 
     # -- multi-GPU posterior pool through the C ABI (RCCL bound inside the library; SURVEY §8e) -----
     def comm_unique_id(self):
