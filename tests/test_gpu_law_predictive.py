@@ -124,12 +124,19 @@ def _series_is_observe(eng, law, obs, d, n, tag):
     return q, std2, data, cy, cl, part
 
 
+def _non_default():
+    """tests/golden/forward_nondefault.json's V_ref, mu_ref, mu_t_zero and k1, the step history as a table in the model's units"""
+    attrs = dict(V_ref=1.7, mu_ref=0.55, mu_t_zero=0.58, k1=3e-7)
+    return dict(attrs, loading=R.table(C.spec(**attrs), "step"))
+
+
 @pytest.mark.parametrize("obs", O.OBSERVABLES)
 @pytest.mark.parametrize("law", R.LAWS)
 def test_series_is_law_observe_bit_for_bit(pkg, law, obs):
     kept = {}
     with pkg.Engine(mem="host") as eng:
-        for tag, attrs in (("damped", {}), ("k1 = 0", dict(k1=0.0)), ("undamped", dict(RadiationDamping=False)), ("built-in loading", dict(history=None))):
+        for tag, attrs in (("damped", {}), ("k1 = 0", dict(k1=0.0)), ("undamped", dict(RadiationDamping=False)), ("built-in loading", dict(history=None)),
+                           ("non-default", _non_default())):
             eng.set_model(_model(pkg, **attrs), 1)
             for d in (1, 3):
                 for n in (1, 63, 65):
