@@ -935,6 +935,22 @@ class MCMC:
             eng.sync()
             return res
 
+    def fit_law(self, n_starts=64, seed=0, mem="host", device=-1, **kw):
+        """fit on the kernels of the state-law solve (additive; Engine.law_fit, include/rsf_law_fit.h): for ANY device model —
+        state_law "aging" or "slip", observable "acc", "mu", "theta" or "velocity", the built-in or a custom loading history,
+        d = 1 or 3 — the Levenberg-Marquardt fit from fit's start points (qstart, then uniform in the prior box), every iteration
+        inside the launch.  Returns fit's FitResult; best()'s point is a start for sample_law (start=np.tile(point, (n_chains, 1)))
+        from which its factor="gn" has a Cholesky factor.  kw: Engine.law_fit's fd_rel_step, ftol, max_iter, iters_per_launch."""
+        if not self._device_model():
+            raise TypeError("fit_law integrates the model on the device: `model` must be this package's RateStateModel")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            q0, lo, hi = self._fit_starts(eng, n_starts, seed)
+            res = eng.law_fit(self._law(), self._observable(), q0, data, lo, hi, **kw)
+            eng.sync()
+            return res
+
     # ---- visualisation (off the hot path; degrades gracefully) --------------------------
     def _animate(self, qparams):
         _figures.chain_movie(qparams[0], f"MCMC Sampling Evolution for dc = {self.dc_true:.2f} as True value",

@@ -316,6 +316,37 @@ class RSF:
             out[float(dc)] = MCMC._dr_pool(part, std2[:, s], nburn)
         return out
 
+    def inference_law(self, n_chains=256, n_iter=200, nburn=None, n_starts=64, gamma=0.2, stages=2, adapt=True, seed=0, mem="device", device=-1, thin=1,
+                      iters_per_launch=16, **fit_kw):
+        """Additive: the laboratory workflow for every series of dc_list under the model's state law, observable and loading
+        history — the least-squares fit of all groups in ONE call (Engine.law_fit; each group n_starts start points, MCMC.fit_law's),
+        then MCMC.sample_law per group from its best point (start: that point for every chain; factor="gn" there).  Returns
+        ({dc: dict(q, ssq, cov, stderr, status, iters, index)} in inference_fit's shape, {dc: PosteriorPool}); the FitResult of all
+        starts is kept in self.fit_result.  The fit runs in host memory as inference_fit does by default, the sampler in `mem`.  fit_kw: Engine.law_fit's fd_rel_step, ftol, max_iter.  The `inference` path is not touched."""
+        n_chains, n_iter = int(n_chains), int(n_iter)
+        if n_chains < 1 or n_iter < 1:
+            raise ValueError("n_chains >= 1, n_iter >= 1")
+        n, G = self.model.num_tsteps, len(self.dc_list)
+        data = np.ascontiguousarray(np.asarray(self.data, dtype=np.float64).reshape(G, n))
+        probes = [MCMC(self.model, data[g], self.dc_list[g], self.qpriors, self.qstart, nsamples=10, verbose=False) for g in range(G)]
+        with Engine(mem="host", device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            q0, lo, hi = probes[0]._fit_starts(eng, n_starts, seed)
+            res = eng.law_fit(probes[0]._law(), probes[0]._observable(), np.tile(q0, (G, 1)), data, lo, hi, **fit_kw)
+            eng.sync()
+        self.fit_result, fits, pools = res, {}, {}
+        for g, dc in enumerate(self.dc_list):
+            i = res.best(g)
+            cov = res.covariance(i)
+            fits[float(dc)] = {"q": res.q[i].copy(), "ssq": float(res.ssq[i]), "cov": cov, "stderr": np.sqrt(np.diag(cov)),
+                               "status": int(res.status[i]), "iters": int(res.iters[i]), "index": i}
+        for g, dc in enumerate(self.dc_list):
+            pools[float(dc)] = probes[g].sample_law(n_chains, n_iter, nburn=nburn, start=np.tile(fits[float(dc)]["q"], (n_chains, 1)), factor="gn",
+                                                    gamma=gamma, stages=stages, adapt=adapt, seed=seed, mem=mem, device=device, thin=thin,
+                                                    iters_per_launch=iters_per_launch)
+        self.posteriors = {dc: pool.pooled() for dc, pool in pools.items()}
+        return fits, pools
+
     @measure_execution_time
     def inference(self, nsamples):
         data = self.prepare_data(self.data)

@@ -334,6 +334,12 @@ LAW_DR_PROTOTYPES = {
     "rsf_law_dr_run": (c_int, [c_void_p, c_int32, c_int32] + DR_PROTOTYPES["rsf_dr_run"][1][1:]),
     "rsf_law_dr_ssq": (c_int, [c_void_p, c_int32, c_int32] + DR_PROTOTYPES["rsf_dr_ssq"][1][1:]),
 }
+# include/rsf_law_fit.h: the Levenberg-Marquardt fit under either state law and any observable; exported by librsf_hip.so only, bound by
+# load().  rsf_fit_normal's and rsf_fit_run's arguments behind (ctx, law, observable)
+LAW_FIT_PROTOTYPES = {
+    "rsf_law_fit_normal": (c_int, [c_void_p, c_int32, c_int32] + FIT_PROTOTYPES["rsf_fit_normal"][1][1:]),
+    "rsf_law_fit_run": (c_int, [c_void_p, c_int32, c_int32] + FIT_PROTOTYPES["rsf_fit_run"][1][1:]),
+}
 # include/rsf_law_predict.h: the posterior predictive checks under either state law and any observable, and the partials of a series
 # that exists; exported by librsf_hip.so only, bound by load().  rsf_predict_partials' arguments behind (ctx, law, observable)
 LAW_PREDICT_PROTOTYPES = {
@@ -388,7 +394,7 @@ def load():
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
                       SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
-                      DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES, LAW_DR_PROTOTYPES, LAW_PREDICT_PROTOTYPES):
+                      DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES, LAW_DR_PROTOTYPES, LAW_PREDICT_PROTOTYPES, LAW_FIT_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

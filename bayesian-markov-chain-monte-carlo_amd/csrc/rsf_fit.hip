@@ -1,36 +1,13 @@
 // rsf_fit.hip — multi-start Levenberg-Marquardt least squares (include/rsf_fit.h): rsf_fit_normal / _run / _trial / _decide
-// (kernels: rsf_kernels_fit.h).  rsf_fit_laplace, the host arithmetic, is in rsf_finish.cpp.
+// (kernels: rsf_kernels_fit.h; the argument checks shared with rsf_law_fit.hip: rsf_fit_host.h).  rsf_fit_laplace, the host arithmetic, is in rsf_finish.cpp.
 #include <cmath>
 
-#include "rsf_host.h"
-#include "rsf_kernels_fit.h"
+#include "rsf_fit_host.h"
 
 using namespace rsfk;
 using namespace rsfh;
 
 namespace {
-
-int set_box(const char *fn, int d, const double *lo, const double *hi, FitArgs &A) {
-  for (int p = 0; p < d; ++p) {
-    if (!std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !(lo[p] < hi[p])) return fail(RSF_ERR_INVALID, "%s: need finite lo[%d] < hi[%d]", fn, p, p);
-    A.lo[p] = lo[p]; A.hi[p] = hi[p];
-  }
-  return RSF_OK;
-}
-
-// what the calls with a solve share: the shape, the model's integrator, the split of the starts over the observation series
-int set_solve(const char *fn, const rsf_ctx *c, int64_t n, int32_t d, int32_t n_groups, double fd, FitArgs &A) {
-  if (n < 1 || (d != 1 && d != 3)) return fail(RSF_ERR_INVALID, "%s: need n >= 1 and d = 1 or 3", fn);
-  if (!std::isfinite(fd) || !(fd > 0.0)) return fail(RSF_ERR_INVALID, "%s: fd must be finite and > 0", fn);
-  if (c->m.flags & RSF_FLAG_DOP853)
-    return fail(RSF_ERR_UNSUPPORTED, "%s: a model flagged RSF_FLAG_DOP853 is not supported (the solve is the float64 RK4)", fn);
-  // a workgroup's starts share one observation series: rsf_mcmc_init's rule for chain groups
-  if (n_groups < 1 || n % n_groups || (n_groups > 1 && (n / n_groups) % c->block))
-    return fail(RSF_ERR_INVALID, "%s: need n_groups >= 1 and, with more than one, n/n_groups a whole multiple of a workgroup's threads (%d)", fn, c->block);
-  A.n = n; A.fd = fd;
-  A.group_starts = n_groups > 1 ? n / n_groups : 0;
-  return RSF_OK;
-}
 
 auto normal_fn(const rsf_ctx *c, int d) {
   return with<1, 3>(d, [&](auto D) { return with<true, false>(damped(c, RK4_F64), [&](auto DAMP) { return fit_normal_kernel<D, DAMP>; }); });
@@ -70,10 +47,8 @@ int rsf_fit_run(rsf_ctx *c, int64_t n, int32_t d, double *q, const double *data,
   int rc;
   FitArgs A{};
   if ((rc = set_solve(__func__, c, n, d, n_groups, fd, A))) return rc;
-  if (n_iter < 1 || n_iter > RSF_FIT_MAX_ITER) return fail(RSF_ERR_INVALID, "rsf_fit_run: need 1 <= n_iter <= %d", RSF_FIT_MAX_ITER);
-  if (!std::isfinite(ftol) || ftol < 0.0) return fail(RSF_ERR_INVALID, "rsf_fit_run: ftol must be finite and >= 0");
+  if ((rc = set_run(__func__, n_iter, ftol, A))) return rc;
   if ((rc = set_box(__func__, d, lo, hi, A))) return rc;
-  A.ftol = ftol; A.n_iter = n_iter;
   const size_t nb = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int32_t);
   Staged s(c);
   const int iq = s.add(q, nb * d, true, true), idata = s.add(data, (size_t)n_groups * c->nout * sizeof(double), true, false);

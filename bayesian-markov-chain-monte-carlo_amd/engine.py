@@ -1867,6 +1867,11 @@ class Engine:
         at d = 1 and 1e-4 at d = 3 (sample_batched's).  → FitResult.  With G > 1 each series' starts are padded to whole
         workgroups with copies of its first start; the result holds the caller's starts only."""
         self._need_model()
+        return self._fit_drive(self.fit_normal, self.fit_run, q0, data, lo, hi, fd_rel_step, ftol, max_iter, iters_per_launch)
+
+    def _fit_drive(self, normal, run, q0, data, lo, hi, fd_rel_step, ftol, max_iter, iters_per_launch, ready=None):
+        """Engine.fit's driver, shared with law_fit: normal(q, obs, fd) and run(q, obs, lo, hi, ssq, grad, jtj, lam, status, iters, k,
+        fd, ftol) are fit_normal's and fit_run's signatures; ready() is called after the argument checks and before the first launch"""
         q0, lo, hi, d, fd, ftol, max_iter, ipl = self._fit_args(q0, lo, hi, (1, 3), fd_rel_step, ftol, max_iter, iters_per_launch)
         obs = _host(data)
         obs = obs.reshape(1, -1) if obs.ndim == 1 else obs
@@ -1880,8 +1885,10 @@ class Engine:
         keep = (np.arange(n) // per) * (per + pad) + np.arange(n) % per
         if pad:
             q0 = np.concatenate([np.concatenate([q0[g * per:(g + 1) * per], np.repeat(q0[g * per:g * per + 1], pad, axis=0)]) for g in range(G)])
+        if ready is not None:
+            ready()
         q, obs = self._in(q0), self._in(obs)
-        ssq, grad, jtj = self.fit_normal(q, obs, fd)
+        ssq, grad, jtj = normal(q, obs, fd)
         running = np.isfinite(_host(ssq))
         lam = self._in(np.full(q0.shape[0], _abi.FIT_LAM0))
         status = self._ints(np.where(running, _abi.FIT_RUNNING, _abi.FIT_FAILED))
@@ -1889,7 +1896,7 @@ class Engine:
         done = 0
         while done < max_iter and running.any():
             k = min(ipl, max_iter - done)
-            self.fit_run(q, obs, lo, hi, ssq, grad, jtj, lam, status, iters, k, fd, ftol)
+            run(q, obs, lo, hi, ssq, grad, jtj, lam, status, iters, k, fd, ftol)
             running = self._ints_host(status) == _abi.FIT_RUNNING
             done += k
         return self._fit_result(keep, q, ssq, grad, jtj, lam, status, iters, G, self.nout)
@@ -2727,6 +2734,70 @@ class Engine:
         run = lambda q, l, obs, lo, hi, L, k, counters, **kw: self.law_dr_run(codes[0], codes[1], q, l, obs, lo, hi, L, k, counters, **kw)
         return self._dr_drive(run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin,
                               adapt_launches, iter0, l0, ready=lambda: self._law_dr_fn("rsf_law_dr_run"))
+
+    # -- Levenberg-Marquardt under either state law and any observable (include/rsf_law_fit.h) ---------------------------
+    def _law_fit_fn(self, name):
+        """a function of include/rsf_law_fit.h, which librsf_hip.so alone exports"""
+        try:
+            return getattr(self.lib, name)
+        except AttributeError:
+            raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
+                                    "symbol (include/rsf_law_fit.h)") from None
+
+    def _law_fit_data(self, data):
+        """data (nout,) or (G, nout) in this engine's memory space → (data, G)"""
+        data = self._in(data)
+        if data.ndim not in (1, 2) or int(data.shape[-1]) != self.nout:
+            raise ValueError(f"data has shape {tuple(data.shape)}: (nout,) or (G, nout), the model produces nout = {self.nout} samples")
+        return data, int(data.shape[0]) if data.ndim == 2 else 1
+
+    def law_fit_normal(self, law, observable, q, data, fd_rel_step=None):
+        """rsf_law_fit_normal: fit_normal — its arguments and results — with the solve under the state law `law` against `data`,
+        series of `observable` (law_observe's names, aliases or integers), under the loading table in use.  ssq is law_observe's SSq
+        at q bit for bit."""
+        self._need_model(law_aware=True)
+        law, observable = self._law_codes(law, observable)
+        q = self._in(q)
+        if q.ndim == 1:
+            q = q.reshape(-1, 1)
+        if q.ndim != 2 or int(q.shape[0]) < 1:
+            raise ValueError(f"q has shape {tuple(q.shape)}: (n,) or (n, d) points")
+        n, d = int(q.shape[0]), int(q.shape[1])
+        obs, G = self._law_fit_data(data)
+        fd = (1e-6 if d == 1 else 1e-4) if fd_rel_step is None else float(fd_rel_step)
+        fn = self._law_fit_fn("rsf_law_fit_normal")
+        ssq, grad, jtj = self._empty((n,)), self._empty((n, d)), self._empty((n, d, d))
+        _abi.check(self.lib, fn(self._ctx, law, observable, n, d, self._ptr(q), self._ptr(obs), G, fd, self._ptr(ssq), self._ptr(grad), self._ptr(jtj)))
+        return ssq, grad, jtj
+
+    def law_fit_run(self, law, observable, q, data, lo, hi, ssq, grad, jtj, lam, status, iters, n_iter, fd_rel_step=None, ftol=1e-9):
+        """rsf_law_fit_run, the fused hot path: fit_run — its arguments, IN PLACE in the same seven arrays — with the solve under
+        `law` against `data` of `observable`."""
+        self._need_model(law_aware=True)
+        law, observable = self._law_codes(law, observable)
+        n, d = self._fit_state(q, grad, jtj, lam, status, ssq, iters)
+        data, G = self._law_fit_data(data)
+        fd = (1e-6 if d == 1 else 1e-4) if fd_rel_step is None else float(fd_rel_step)
+        lo, hi = _vec(lo, d, "lo"), _vec(hi, d, "hi")
+        fn = self._law_fit_fn("rsf_law_fit_run")
+        _abi.check(self.lib, fn(self._ctx, law, observable, n, d, self._ptr(q), self._ptr(data), G, _dp(lo), _dp(hi), fd, float(ftol), int(n_iter),
+                                self._ptr(ssq), self._ptr(grad), self._ptr(jtj), self._ptr(lam), self._ptr(status), self._ptr(iters)))
+
+    def law_fit(self, law, observable, q0, data, lo, hi, fd_rel_step=None, ftol=1e-9, max_iter=100, iters_per_launch=8):
+        """Engine.fit — its arguments, groups, padding, statuses and FitResult, through the same driver — for the device model under
+        the state law `law` against `data`, series of `observable`, under the loading table in use: the launches are law_fit_normal
+        and law_fit_run, every iteration of every start inside the kernel, only the statuses read between launches.  Any device
+        model runs, the default one included (ageing law, acceleration, built-in loading: the plain solve in place of fit's tiers)."""
+        self._need_model(law_aware=True)
+        codes = self._law_codes(law, observable)
+        if codes[0] not in (_abi.LAW_AGEING, _abi.LAW_SLIP):
+            raise ValueError(f"law is {_abi.LAW_AGEING} or {_abi.LAW_SLIP} (RSF_LAW_*), not {codes[0]}")
+        if codes[1] not in _OBSERVABLE_NAMES:
+            raise ValueError(f"observable is one of {sorted(_OBSERVABLE_NAMES)} (RSF_OBS_*), not {codes[1]}")
+        normal = lambda q, obs, fd: self.law_fit_normal(codes[0], codes[1], q, obs, fd)
+        run = lambda q, obs, *rest: self.law_fit_run(codes[0], codes[1], q, obs, *rest)
+        return self._fit_drive(normal, run, q0, data, lo, hi, fd_rel_step, ftol, max_iter, iters_per_launch,
+                               ready=lambda: (self._law_fit_fn("rsf_law_fit_normal"), self._law_fit_fn("rsf_law_fit_run")))
 
     # -- the exact posterior on a tensor quadrature grid (include/rsf_grid.h) ------------------------------
     @staticmethod
