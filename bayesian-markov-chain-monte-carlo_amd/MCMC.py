@@ -171,6 +171,16 @@ class PosteriorPool:
         with _engine_for(engine, model, substeps) as eng:
             return eng.evidence(self.samples, data, lo, hi, transform=transform, **kw)
 
+    def law_evidence(self, model, data, lo, hi, transform=None, engine=None, substeps=None, **kw):
+        """evidence — its arguments and its result — for ANY device model (Engine.law_evidence): the state law, the observable
+        `data` is a series of and the loading history are the model's, d = 1 or 3: the marginal likelihood of a pool that
+        sample_law or LawGridPosterior.pool returned.  The result also carries `law` and `observable`."""
+        law, observable = state_law_of(model), observable_of(model)
+        with _engine_for(engine, model, substeps) as eng:
+            res = eng.law_evidence(law, observable, self.samples, data, lo, hi, transform=transform, **kw)
+        res.update(law=law, observable=observable)
+        return res
+
     def pooled(self):
         """(d, n_keep*C): every kept draw of every chain, the reference's (d, n) layout."""
         n, C, d = self.samples.shape
@@ -902,6 +912,77 @@ class MCMC:
                 self.model.state_law = law
                 out[law] = self.quadrature(**quadrature_kw)
                 ev[self._law()] = out[law].log_evidence
+        finally:
+            self.model.state_law = before
+        out["log_bayes_factor"] = ev["slip"] - ev["aging"]
+        return out
+
+    def quadrature_law(self, n=None, n_starts=64, window_sd=8.0, log_coords=None, marginals=("Dc",), n_draws=0, seed=0, mem="device", device=-1):
+        """The exact posterior by quadrature for ANY device model at d = 1 or 3 (additive; Engine.law_grid_posterior,
+        include/rsf_law_grid.h): state_law "aging" or "slip", observable "acc", "mu", "theta" or "velocity", the built-in or a custom
+        loading history.  fit_law from n_starts starts gives the point (FitResult.best()) and its covariance; the tensor grid is laid
+        in the whitened coordinates of that fit, n (default 65 per axis) Simpson nodes on +- window_sd per axis, log_coords naming
+        the parameters whose logarithm is the working coordinate (on acceleration data ("Dc", "a") straightens the ridge).  One grid
+        per name in `marginals`, with that parameter on axis 0: each extra name costs one more grid.  → the first grid's
+        LawGridPosterior (log_evidence, mean, cov, std2_mean, marginal(), quantiles(probs), cdf(xs), draw(n), pool(n), edge_mass,
+        n_neginf, n_solves) with .grids {name: LawGridPosterior}, .evidence_spread (the largest minus the smallest log_evidence over
+        the grids: what the order of the axes changes), .fit (the FitResult) and, with n_draws > 0, .q and .std2.  The result holds
+        its engine (result.engine.close() releases it)."""
+        if not self._device_model():
+            raise TypeError("quadrature_law integrates the model on the device: `model` must be this package's RateStateModel")
+        names = ("Dc", "a", "b")[:self.n_params]
+        marginals = (marginals,) if isinstance(marginals, str) else tuple(marginals)
+        if not marginals or any(k not in names for k in marginals) or len(set(marginals)) != len(marginals):
+            raise ValueError(f"marginals names parameters of {names}, each once, at least one")
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        lo, hi = self.qstart_limits[:, 0], self.qstart_limits[:, 1]
+        d, law, observable = self.n_params, self._law(), self._observable()
+        eng = Engine(mem=mem, device=device)
+        try:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            q0, _, _ = self._fit_starts(eng, n_starts, seed)
+            fit = eng.law_fit(law, observable, q0, data, lo, hi)
+            i = fit.best()
+            point, cov = fit.q[i].copy(), fit.covariance(i)
+            logged = [names.index(k) if isinstance(k, str) and k in names else int(k) for k in (log_coords or ())]
+            J = np.ones(d)
+            J[logged] = 1.0 / point[logged]
+            try:
+                F = np.linalg.cholesky(cov * J[:, None] * J[None, :])
+            except np.linalg.LinAlgError:
+                raise RsfError(ERR_NOT_POSDEF, "quadrature_law: the fit's covariance is not positive definite (a fit on a face of the box?)") from None
+            grids = {k: eng.law_grid_posterior(law, observable, data, lo, hi, point, F, log_coords=logged, first=k, n=n, window_sd=window_sd)
+                     for k in marginals}
+            res = grids[marginals[0]]
+            ev = [g.log_evidence for g in grids.values()]
+            res.grids, res.evidence_spread, res.fit = grids, float(max(ev) - min(ev)), fit
+            res.q, res.std2 = res.draw(int(n_draws), seed) if int(n_draws) > 0 else (None, None)
+            eng.sync()
+        except BaseException:
+            eng.close()
+            raise
+        return res
+
+    def bayes_factor_laws(self, laws=("aging", "slip"), **quadrature_kw):
+        """compare_laws at d = 1 or 3 on quadrature_law: the exact posterior under each state law and the log Bayes factor between
+        them → dict with a LawGridPosterior per entry of `laws` (keyed as given) and log_bayes_factor, the slip law's log evidence
+        minus the ageing law's.  quadrature_kw: quadrature_law's arguments.  The model's state_law is restored afterwards.  Each
+        result holds its engine (out[law].engine.close() releases it); if a law's quadrature raises, the engines of the laws
+        already done are closed here.  A law
+        that the data contradict is often fitted onto a face of the box: its grid then has n_neginf > 0 and its evidence is
+        approximate — by far less than such a Bayes factor is large."""
+        if sorted(law_name(law) for law in laws) != ["aging", "slip"]:
+            raise ValueError(f"laws names the ageing and the slip law once each, not {laws!r}")
+        before, out, ev = getattr(self.model, "state_law", "aging"), {}, {}
+        try:
+            for law in laws:
+                self.model.state_law = law
+                out[law] = self.quadrature_law(**quadrature_kw)
+                ev[self._law()] = out[law].log_evidence
+        except BaseException:
+            for res in out.values():  # the engines of the laws already done: nobody else holds them
+                res.engine.close()
+            raise
         finally:
             self.model.state_law = before
         out["log_bayes_factor"] = ev["slip"] - ev["aging"]

@@ -8,9 +8,9 @@ on sys.path and use the reference's flat module names (`from MCMC import MCMC`).
 """
 from . import _abi  # noqa: F401
 from ._abi import RsfError  # noqa: F401
-from .engine import DrResult, Engine, EnsembleResult, FitResult, GridPosterior, MalaResult, bayes_factor, smc_batch_populations, smc_batch_summary  # noqa: F401
+from .engine import DrResult, Engine, EnsembleResult, FitResult, GridPosterior, LawGridPosterior, MalaResult, bayes_factor, smc_batch_populations, smc_batch_summary  # noqa: F401
 from .RateStateModel import RateStateModel  # noqa: F401
 from .MCMC import MCMC, PosteriorPool  # noqa: F401
 from .RSF import RSF, measure_execution_time  # noqa: F401
 
-__all__ = ["DrResult", "Engine", "EnsembleResult", "FitResult", "GridPosterior", "MalaResult", "bayes_factor", "smc_batch_populations", "smc_batch_summary", "RsfError", "RateStateModel", "MCMC", "PosteriorPool", "RSF", "measure_execution_time"]
+__all__ = ["DrResult", "Engine", "EnsembleResult", "FitResult", "GridPosterior", "LawGridPosterior", "MalaResult", "bayes_factor", "smc_batch_populations", "smc_batch_summary", "RsfError", "RateStateModel", "MCMC", "PosteriorPool", "RSF", "measure_execution_time"]

@@ -346,6 +346,16 @@ LAW_PREDICT_PROTOTYPES = {
     "rsf_law_predict_partials": (c_int, [c_void_p, c_int32, c_int32] + PREDICT_PROTOTYPES["rsf_predict_partials"][1][1:]),
     "rsf_predict_series_partials": (c_int, [c_void_p, c_int64, c_int64, _P, _P, _P, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
 }
+# include/rsf_law_grid.h: the exact posterior of a state-law model on a tensor grid in the coordinates of a fit; exported by
+# librsf_hip.so only, bound by load()
+LAW_GRID_PROTOTYPES = {
+    "rsf_law_logtarget": (c_int, [c_void_p, c_int32, c_int32, c_int32, _I32P, _DP, _DP, _DP, _I32P, _I32P, c_int64, _P, _P, _P, c_double, _DP, _DP,
+                                  _P, _P, _P]),
+    "rsf_law_grid_moments": (c_int, [c_void_p, c_int32, _I32P, _DP, _DP, _DP, _DP, _I32P, _I32P, _P, _P, c_double, _DP, _P, _DP]),
+}
+LAW_GRID_MAX_PARAMS = 3  # RSF_LAW_GRID_MAX_PARAMS
+# the totals of rsf_law_grid_moments (RSF_LAW_GRID_FIELDS), in index order; d0..d2: q - center of (Dc, a, b)
+LAW_GRID_FIELDS = ("s0", "d0", "d1", "d2", "d0d0", "d0d1", "d0d2", "d1d1", "d1d2", "d2d2", "ssq", "ssq2")
 MAX_BLOCK = 256     # kMaxBlock: a workgroup's threads unless Engine(block_threads=...) says otherwise
 
 
@@ -394,7 +404,8 @@ def load():
         lib = bind(ctypes.CDLL(LIB_PATH))
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
                       SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
-                      DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES, LAW_DR_PROTOTYPES, LAW_PREDICT_PROTOTYPES, LAW_FIT_PROTOTYPES):
+                      DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES, LAW_DR_PROTOTYPES, LAW_PREDICT_PROTOTYPES, LAW_FIT_PROTOTYPES,
+                      LAW_GRID_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes
