@@ -395,6 +395,21 @@ __device__ __forceinline__ void tight_incr(double rho, double dk, const Lane &L,
 // The guard holds |bh| lim^3 to 2^-47 V_ref by a per-lane limit on |rho| (Series::lim_rho: it binds before 2^-20 where |bh| >
 // 8192 V_ref) — under the dlt^4/24 above; at Dc ~ 1000, h = 0.025 the term is 1e-18.  The step's end keeps its
 // q = -rho + rho^2: that one updates the carried Rh.
+// The log1p bracket pb = B + N rho is formed ONCE for the two half-step stages, at the first one's rho_a = a1; the second takes it
+// with its own r = rho_b = b1, del = d - rho_b (B + N rho_a): one fma fewer per step, 67 operations.  What that leaves out of the
+// second stage's dlt is k rho_b N (rho_b - rho_a) = (b/2a) |rho_b| |rho_b - rho_a|, and from rhs_tight
+//     rho_b - rho_a = (Rh - w_b xh (1 + a1)) - (Rh - W xh) = -W xh (expm1(dlt_a) + (1 + expm1(dlt_a)) a1),   |W xh| = |Rh - rho_a| <= |Rh| + |rho|,
+// so |rho_b - rho_a| <= (|Rh| + |rho|)(|dlt| + |rho|) to first order: second order in a second-order term.  Under the guard |dlt| < 2^-10
+// at that stage and |rho| < 2^-20.  Rh drifts by a factor 1 + q per step, |q| < 2^-19: under 1 % in the few thousand steps of a chunk,
+// so with Rh0 the state's where a Series was formed |Rh| + |rho| <= 1.01 |Rh0| + 2^-20 <= 2 |Rh0| wherever |Rh0| >= 1.02 * 2^-20; below
+// that the term is under (b/a) 2^-49 whatever the limit.  The limit
+//     |rho| < lim_pb = 2^-43 / ((b/2a) (2^-10 + 2^-20) 2 |Rh0|)                                       (tight_pb_limit, rounded down)
+// holds the term to 2^-43 = 1.1e-13 in dlt — a stage value's, like the dlt^4/24 = 3.8e-14 the half-step stages drop at the same
+// edge; it joins Series::lim_rho, lim_c1 and bmax through a min with tight_rho_limit's and costs a trip nothing.  It binds before
+// 2^-20 where (b/a) |Rh| > 1.22e-4: with the default (a, b) below TIGHT's a-priori edge; at Dc ~ 1000, h = 0.025 it is 8 * 2^-20.
+// The FULL-step stage does not take the shared bracket: its rho is 2 c1, TWICE a half-step stage's, so rho_s - rho_a ~ rho_a there and
+// B + N a1 in place of B - B c1 would leave out (b/a) |c1| |2 c1 - a1| ~ (b/a) c1^2 — half of the second-order term outright, 2.3e-13
+// in dlt at 0.9 of the guard's edge, which no limit on |Rh| mends (the limit on |rho| it would take is near 0.3 * 2^-20).
 // The guard (GUARD; without it the same arithmetic, instruction for instruction, for a trip whose start state proves that no
 // increment can reach a threshold: tight_needs_guard) holds del to the regions of dlt: |del| < 2^-10 / |khh| at the half-step
 // stages — which is 2^-9 / |kh|, so the full-step stage shares the figure — and < 2^-9 / |kh6| at the step's end; rho and c1 as ever.
@@ -427,11 +442,23 @@ __device__ __forceinline__ double tight_rho_limit(double bh, const Consts &K) {
 // What the a-priori bound holds every |d1'| of a trip to, given the lane's limit on rho: 0.9 of the limit on c1 (tight_needs_guard
 // through Series::bmax, which keeps the high word — once more rounded down, by 2^-20 of the figure at most; W.never as it stands).
 __device__ __forceinline__ double tight_bmax(double lim_rho) { return 0.45 * lim_rho; }
+// The lane's limit on |rho| that holds what the shared half-step bracket leaves out to 2^-43 (tight_incr_scaled):
+//     lim_pb = 2^-43 / ((b/2a) (2^-10 + 2^-20) 2 |Rh|) = (2^-33 / (1 + 2^-10)) / |(b/a) Rh|,   rounded DOWN:
+// the constant is the double below the quotient, the factor 1 - 2^-30 covers the product's rounding and the reciprocal's ulp, and
+// the high word that the guard keeps rounds down once more.  Rh is the state's where a Series is formed (make_series).  (b/a) Rh = 0
+// gives a NaN (fm::rcp), and so does a NaN in either factor: the fmin at the caller keeps its other operand, the limit as it was
+// (as tight_rho_limit treats them); an infinite product the same (fm::rcp's Newton step on the seed 0 forms inf * 0): such a state is
+// already lost, and its rho trips the limit as it was.  Eight operations per Series.
+__device__ __forceinline__ double tight_pb_limit(double boa, double Rh) {
+  constexpr double C = 0x1.ff801ff801ff8p-34;  // 2^-33 / (1 + 2^-10) = 2^-34 * 1.99805..., truncated
+  return ((1.0 - 0x1.0p-30) * C) * fm::rcp(__builtin_fabs(boa * Rh));
+}
 // Formed where a loop of in-step trips is entered (integrate_multi), from a value the compiler cannot trace back (local_value):
 // held from make_lane on, the constants were live through every other tier's loop as well and the sampler kernels spilled
 // (44 to 88 bytes of scratch per lane).  Fifty-odd operations per entry; at the headline shape a solve enters twice or so.
+// Rh: the state's at the entry, for the limit that goes with the shared half-step bracket (tight_pb_limit).
 template <bool GUARD>
-__device__ __forceinline__ Series make_series(const Lane &L, const Consts &K) {
+__device__ __forceinline__ Series make_series(const Lane &L, const Consts &K, double Rh) {
   Series S;
   const double khh = local_value(L.khh);
   const double ik = fm::rcp(khh);
@@ -449,7 +476,8 @@ __device__ __forceinline__ Series make_series(const Lane &L, const Consts &K) {
   S.e2 = (e2 * kh6) * (1.0 / 6.0);
   S.e3 = (e2 * e2) * (1.0 / 24.0);
   S.lim = S.lim_e = S.lim_rho = S.lim_c1 = 0.0f;
-  const double lim_rho = tight_rho_limit(local_value(L.bh), K);  // (formed here, like the rest: see above)
+  // (formed here, like the rest: see above; fmin keeps the first limit where the second is a NaN)
+  const double lim_rho = __builtin_fmin(tight_rho_limit(local_value(L.bh), K), tight_pb_limit(L.boa, Rh));
   S.bmax = hi_as_float(tight_bmax(lim_rho));  // (the high word of 0.9 * 2^-21 where the first limit holds)
   if constexpr (GUARD) {
     S.lim_rho = hi_as_float(lim_rho);
@@ -463,6 +491,12 @@ __device__ __forceinline__ Series make_series(const Lane &L, const Consts &K) {
   return S;
 }
 
+// The bracket of a stage's own r: B + N rho with rho = r at a half-step stage, 2 r at the full-step stage, r / 3 at the step's end.
+template <int STAGE>
+__device__ __forceinline__ double tight_bracket(double r, const Series &S) {
+  return STAGE == 0 ? __builtin_fma(r, S.N, S.B) : (STAGE == 1 ? __builtin_fma(-r, S.B, S.B) : __builtin_fma(r, S.N6, S.B));
+}
+
 // a figure that comes once per step: held on even steps, folded with the next step's on odd ones (struct Guard)
 __device__ __forceinline__ void guard_note(float &acc, float &pend, double x, bool odd) {
   const float ax = __builtin_fabsf(hi_as_float(x));
@@ -473,10 +507,10 @@ __device__ __forceinline__ void guard_note(float &acc, float &pend, double x, bo
 // STAGE 0: a half-step stage, q left alone (the caller's bracket is bh - bh rho);  1: the full-step stage, q = brx = bh - 2 bh c1;
 // 2: the step's end, q = -rho + rho^2 of rho = t1/3.
 // odd: the step's parity within its trip (guard_note).
+// pb: the bracket B + N rho of the stage — its own (tight_bracket) or, at the second half-step stage, the first one's (rk4_tight).
 template <int STAGE, bool GUARD>
-__device__ __forceinline__ void tight_incr_scaled(double r, double d, const Lane &L, const Series &S, double w0, double &w, double &q, Guard &g,
-                                                  bool odd) {
-  const double pb = STAGE == 0 ? __builtin_fma(r, S.N, S.B) : (STAGE == 1 ? __builtin_fma(-r, S.B, S.B) : __builtin_fma(r, S.N6, S.B));
+__device__ __forceinline__ void tight_incr_scaled(double r, double pb, double d, const Lane &L, const Series &S, double w0, double &w, double &q,
+                                                  Guard &g, bool odd) {
   const double del = __builtin_fma(-r, pb, d);
   double e;
   if constexpr (STAGE == 0) e = __builtin_fma(__builtin_fma(S.h2, del, S.h1), del, L.khh);
@@ -539,17 +573,20 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
   const double vr = L.vrw, xh = L.hhdw, xf = L.hdw;  // (V_ref, hhd, hd) / kvk with damping: s.w is W (Lane::vrw)
   rhs_tight<DAMP>(s.w, xh, Rh, vl0, L.bh, vr, a0, a1, a2);
   double sv = s.w * a2;  // k1 + k4 of dV/dt (in units of vk, vk/kvk with damping), and k2 + k3 below: 5 instructions for the weighted sum
-  if constexpr (INSTEP) tight_incr_scaled<0, GUARD>(a1, a0, L, *S, s.w, w, q, g, odd);
-  else tight_incr<T, true>(a1, L.khh * a0, L, s.w, w, q, g);
+  double pb = 0.0;  // INSTEP: the first half-step stage's bracket, which the second one takes as well (tight_incr_scaled)
+  if constexpr (INSTEP) {
+    pb = tight_bracket<0>(a1, *S);
+    tight_incr_scaled<0, GUARD>(a1, pb, a0, L, *S, s.w, w, q, g, odd);
+  } else tight_incr<T, true>(a1, L.khh * a0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, a1, xh), Rh, vlm, INSTEP ? __builtin_fma(-L.bh, a1, L.bh) : __builtin_fma(L.bh, q, L.bh), vr, b0, b1, b2);
   double sm = w * b2;
-  if constexpr (INSTEP) tight_incr_scaled<0, GUARD>(b1, b0, L, *S, s.w, w, q, g, odd);
+  if constexpr (INSTEP) tight_incr_scaled<0, GUARD>(b1, pb, b0, L, *S, s.w, w, q, g, odd);
   else tight_incr<T, true>(b1, L.khh * b0, L, s.w, w, q, g);
   rhs_tight<DAMP>(w, __builtin_fma(xh, b1, xh), Rh, vlm, INSTEP ? __builtin_fma(-L.bh, b1, L.bh) : __builtin_fma(L.bh, q, L.bh), vr, c0, c1, c2);
   sm = __builtin_fma(w, c2, sm);
   if constexpr (INSTEP) {
     double brx;
-    tight_incr_scaled<1, GUARD>(c1, c0, L, *S, s.w, w, brx, g, odd);
+    tight_incr_scaled<1, GUARD>(c1, tight_bracket<1>(c1, *S), c0, L, *S, s.w, w, brx, g, odd);
     rhs_tight<DAMP>(w, __builtin_fma(xf, c1, xh), Rh, vl1, brx, vr, e0, e1, e2);
   } else {
     tight_incr<T, false>(c1 + c1, L.kh * c0, L, s.w, w, q, g);
@@ -559,7 +596,7 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
   const double t0 = a0 + 2.0 * b0 + 2.0 * c0 + e0;
   const double t1 = a1 + 2.0 * b1 + 2.0 * c1 + e1;
   if constexpr (INSTEP) {
-    tight_incr_scaled<2, GUARD>(t1, t0, L, *S, s.w, w, q, g, odd);
+    tight_incr_scaled<2, GUARD>(t1, tight_bracket<2>(t1, *S), t0, L, *S, s.w, w, q, g, odd);
   } else {
     const double rho = t1 * (1.0 / 3.0);  // (h/6Dc)/x times the unscaled sum
     tight_incr<T, false>(rho, L.kh6 * t0, L, s.w, w, q, g);
@@ -932,7 +969,7 @@ __device__ __forceinline__ int integrate_multi(const double *lds, const double *
   constexpr bool HELD = INSTEP && NU > 2 && !UNGUARD;  // the guarded loop of whole in-step trips
   set_tier<T>(L);
   Series S;
-  if constexpr (INSTEP) S = make_series<!UNGUARD>(L, K);
+  if constexpr (INSTEP) S = make_series<!UNGUARD>(L, K, s.rx);
   const bool held = HELD && (W.never & W.alive) != 0;  // (loop-invariant: W.never is read again only where a lane dies)
   for (; r + NU <= nsteps; r += NU) {
     const unsigned long long deadmask = WANT_SSQ ? ballot(ssq > thr) : 0ull;  // NaN compares false: such a lane runs on
