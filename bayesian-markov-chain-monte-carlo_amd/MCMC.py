@@ -26,11 +26,11 @@ import numpy as np
 if __package__:
     from . import _figures
     from ._abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from .engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, whole_islands  # noqa: F401
+    from .engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, stiffness_of, whole_islands  # noqa: F401
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     from _abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, whole_islands  # noqa: F401
+    from engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, stiffness_of, whole_islands  # noqa: F401
 
 
 @contextlib.contextmanager
@@ -110,7 +110,8 @@ class PosteriorPool:
         """predictive — its arguments and its result — for ANY device model (Engine.law_predictive): the state law
         (model.state_law: "aging" or "slip"), the observable `data` is a series of (model.observable: "acc", "mu", "theta" or
         "velocity") and the loading history (model.loading) are the model's, d = 1 or 3: the checks of a pool that sample_law
-        returned.  The result also carries `law` and `observable`, the names the solve ran under."""
+        returned.  The result also carries `law` and `observable`, the names the solve ran under.  A model with a stiffness
+        (model.stiffness) runs Engine.law_predictive's split route: law_observe's series, then series_partials."""
         q, s2 = self._draws(max_draws)
         law, observable = state_law_of(model), observable_of(model)
         extra = dict(loo=True, r_eff=r_eff) if loo else {}
@@ -176,6 +177,9 @@ class PosteriorPool:
         `data` is a series of and the loading history are the model's, d = 1 or 3: the marginal likelihood of a pool that
         sample_law or LawGridPosterior.pool returned.  The result also carries `law` and `observable`."""
         law, observable = state_law_of(model), observable_of(model)
+        if stiffness_of(model) is not None:
+            raise NotImplementedError(f"PosteriorPool.law_evidence cannot run a model with stiffness={stiffness_of(model)!r}: the kernel "
+                                      "integrates k' = 0.1 / Dc (Engine.law_logtarget); sample_smc and quadrature (d = 1) give its evidence")
         with _engine_for(engine, model, substeps) as eng:
             res = eng.law_evidence(law, observable, self.samples, data, lo, hi, transform=transform, **kw)
         res.update(law=law, observable=observable)
@@ -264,13 +268,27 @@ class MCMC:
         kernels, which integrate the ageing law and fit the acceleration: the slip law, or another observable under either law"""
         if self._law() == "slip":
             return "state_law='slip'"
-        return None if self._observable() == "acc" else f"observable={self._observable()!r}"
+        if self._observable() != "acc":
+            return f"observable={self._observable()!r}"
+        return None if self._stiffness() is None else f"stiffness={self._stiffness()!r}"
+
+    def _stiffness(self):
+        """the model's stiffness independent of Dc, or None for the reference's coupling k' = 0.1 / Dc"""
+        return stiffness_of(self.model)
 
     def _ssq_fn(self, eng, data):
-        return eng.law_ssq_fn(self._law(), data, observable=self._observable())
+        return eng.law_ssq_fn(self._law(), data, observable=self._observable())  # the engine's model's stiffness, if it has one
+
+    def _coupled_only(self, what):
+        """`what` runs kernels that integrate the reference's spring: refuse a model with a stiffness of its own"""
+        if self._stiffness() is not None:
+            raise NotImplementedError(f"{what} cannot run a model with stiffness={self._stiffness()!r}: the kernel integrates k' = 0.1 / Dc; "
+                                      "with a stiffness quadrature (d = 1), compare_laws, sample_smc, sample_dr, sample_law, fit_law and "
+                                      "SSqcalc run")
 
     def _ageing_only(self, what):
         """`what` runs kernels that integrate the ageing law: refuse a model with another law instead of running the ageing law"""
+        self._coupled_only(what)
         if self._law() != "aging":
             raise NotImplementedError(f"{what} integrates the ageing law only and the model's state_law is {self._law()!r}: under the slip "
                                       "law quadrature, compare_laws, sample_smc and sample_dr run")
@@ -610,6 +628,7 @@ class MCMC:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
             if self._split():  # the split path: the GPU's weights, resampling, proposals and accept tests on the plain solve's SSq
                 if int(replicates) > 1:
+                    self._coupled_only("sample_smc(replicates > 1)")
                     raise NotImplementedError("sample_smc(replicates > 1) runs the batched kernels, which integrate the ageing law; the model's "
                                               "state_law is 'slip'" if self._law() == "slip" else
                                               f"sample_smc(replicates > 1) runs the batched kernels, which fit the acceleration; the model's {self._split()}")
@@ -930,6 +949,7 @@ class MCMC:
         its engine (result.engine.close() releases it)."""
         if not self._device_model():
             raise TypeError("quadrature_law integrates the model on the device: `model` must be this package's RateStateModel")
+        self._coupled_only("quadrature_law (and bayes_factor_laws)")
         names = ("Dc", "a", "b")[:self.n_params]
         marginals = (marginals,) if isinstance(marginals, str) else tuple(marginals)
         if not marginals or any(k not in names for k in marginals) or len(set(marginals)) != len(marginals):
@@ -1021,13 +1041,27 @@ class MCMC:
         state_law "aging" or "slip", observable "acc", "mu", "theta" or "velocity", the built-in or a custom loading history,
         d = 1 or 3 — the Levenberg-Marquardt fit from fit's start points (qstart, then uniform in the prior box), every iteration
         inside the launch.  Returns fit's FitResult; best()'s point is a start for sample_law (start=np.tile(point, (n_chains, 1)))
-        from which its factor="gn" has a Cholesky factor.  kw: Engine.law_fit's fd_rel_step, ftol, max_iter, iters_per_launch."""
+        from which its factor="gn" has a Cholesky factor.  kw: Engine.law_fit's fd_rel_step, ftol, max_iter, iters_per_launch.
+        A model with a stiffness (model.stiffness) runs Engine.fit_from_residuals around Engine.law_observe instead: the fused
+        kernel integrates k' = 0.1 / Dc."""
         if not self._device_model():
             raise TypeError("fit_law integrates the model on the device: `model` must be this package's RateStateModel")
         data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
         with Engine(mem=mem, device=device) as eng:
             eng.set_model(self.model, getattr(self.model, "substeps", 1))
             q0, lo, hi = self._fit_starts(eng, n_starts, seed)
+            if self._stiffness() is not None:  # the split route: the GPU's trial points and decisions around law_observe's series
+                kw.pop("iters_per_launch", None)
+                law, observable = self._law(), self._observable()
+
+                def residuals(pts):
+                    ab = [np.ascontiguousarray(pts[:, p]) for p in (1, 2)] if pts.shape[1] == 3 else [None, None]
+                    series = _host(eng.law_observe(law, observable, np.ascontiguousarray(pts[:, 0]), ab[0], ab[1])[1])
+                    return series.T - data[None, :]
+
+                res = eng.fit_from_residuals(residuals, q0, lo, hi, **kw)
+                eng.sync()
+                return res
             res = eng.law_fit(self._law(), self._observable(), q0, data, lo, hi, **kw)
             eng.sync()
             return res

@@ -6,7 +6,7 @@ solve runs on the GPU through the C ABI (rsf_forward_batch) as a fixed-step RK4 
 (`substeps` steps per output interval) instead of the reference's SciPy dop853 call.  DESIGN.md
 states the resulting tolerance ladder against the reference trajectory.
 
-Additive surface: `substeps`, `precision`, `integrator`, `loading`, `state_law`, `observable`, `noise_sd`,
+Additive surface: `substeps`, `precision`, `integrator`, `loading`, `state_law`, `observable`, `noise_sd`, `stiffness`,
 `evaluate_batch(dc, a=None, b=None)`, `trajectory(dc=None, a=None, b=None)`.
 """
 import zlib
@@ -61,6 +61,10 @@ class RateStateModel:
         # Another observable than "acc" runs the plain float64 RK4 (Engine.law_observe) under either law
         self.observable = "acc"
         self.noise_sd = 0.0
+        # additive: the stiffness of the spring — None (the reference's coupling to the parameter being inferred,
+        # k' = 1e-2 * 10 / Dc, RateStateModel.py:324) or a positive float, a constant of the apparatus that does not move with Dc.
+        # With one, every solve is Engine.law_observe's (rsf_stiff_observe) under either law, for every observable; float64 RK4 only
+        self.stiffness = None
         self._engine = None
         self._engine_key = None
 
@@ -75,7 +79,7 @@ class RateStateModel:
     def _model_key(self):
         return (self.a, self.b, self.mu_ref, self.V_ref, self.k1, self.t_start, self.t_final, self.num_tsteps, self.delta_t,
                 self.mu_t_zero, bool(self.RadiationDamping), int(self.substeps), self.precision, self.integrator, self._loading_key(),
-                self.state_law, self.observable)
+                self.state_law, self.observable, self.stiffness)
 
     def engine(self):
         """Host-memory Engine bound to the HIP library, re-armed when an attribute changed."""
@@ -124,9 +128,9 @@ class RateStateModel:
     def _forward(self, dc, a=None, b=None):
         """the clean series under the model's loading history and state law: the tier kernels (rsf_forward_batch) for the ageing
         law, the plain float64 RK4 of rsf_law_forward for the slip law; the model's observable, if it is not the acceleration, by
-        rsf_law_observe under either law"""
+        rsf_law_observe under either law; with a stiffness every observable by rsf_stiff_observe (law_observe routes there)"""
         law = check_law_options(self)
-        if observable_of(self) != "acc":
+        if observable_of(self) != "acc" or self.stiffness is not None:
             return self.engine().law_observe(law, self.observable, dc, a=a, b=b, want_series=True)
         if law == "slip":
             return self.engine().law_forward("slip", dc, a=a, b=b, want_acc=True)

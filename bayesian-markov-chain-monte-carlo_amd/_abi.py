@@ -334,6 +334,14 @@ LAW_DR_PROTOTYPES = {
     "rsf_law_dr_run": (c_int, [c_void_p, c_int32, c_int32] + DR_PROTOTYPES["rsf_dr_run"][1][1:]),
     "rsf_law_dr_ssq": (c_int, [c_void_p, c_int32, c_int32] + DR_PROTOTYPES["rsf_dr_ssq"][1][1:]),
 }
+# include/rsf_stiff.h: the state-law solve and its delayed-rejection sampler with the spring's stiffness independent of Dc; exported
+# by librsf_hip.so only, bound by load().  rsf_law_observe's, rsf_law_dr_run's and rsf_law_dr_ssq's arguments with the stiffness
+# behind (ctx, law, observable)
+STIFF_PROTOTYPES = {
+    "rsf_stiff_observe": (c_int, [c_void_p, c_int32, c_int32, c_double] + OBSERVE_PROTOTYPES["rsf_law_observe"][1][3:]),
+    "rsf_stiff_dr_run": (c_int, [c_void_p, c_int32, c_int32, c_double] + DR_PROTOTYPES["rsf_dr_run"][1][1:]),
+    "rsf_stiff_dr_ssq": (c_int, [c_void_p, c_int32, c_int32, c_double] + DR_PROTOTYPES["rsf_dr_ssq"][1][1:]),
+}
 # include/rsf_law_fit.h: the Levenberg-Marquardt fit under either state law and any observable; exported by librsf_hip.so only, bound by
 # load().  rsf_fit_normal's and rsf_fit_run's arguments behind (ctx, law, observable)
 LAW_FIT_PROTOTYPES = {
@@ -405,7 +413,7 @@ def load():
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
                       SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
                       DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES, LAW_DR_PROTOTYPES, LAW_PREDICT_PROTOTYPES, LAW_FIT_PROTOTYPES,
-                      LAW_GRID_PROTOTYPES):
+                      LAW_GRID_PROTOTYPES, STIFF_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -90,13 +90,17 @@ __device__ __forceinline__ void set_tier(Lane &L);
 
 // DAMP: radiation damping, k1 != 0 (with k1 = 0 the host launches the DAMP = false kernels: the damping pass is then an exact
 // identity, and W = kvk w would be 0)
-template <bool DAMP>
-__device__ __forceinline__ Lane make_lane(double dc, double a, double b, const Consts &K) {
+// STIFF (rsf_kernels_stiff.h, include/rsf_stiff.h): the spring's stiffness k is the caller's, independent of Dc — kappa = k Dc
+// stands where the reference's coupling has the literal 1e-2 * 10, ikappa = 1 / kappa (one IEEE division per lane per solve, the
+// caller's) where it has that literal's reciprocal; every other constant is formed as it is.  Without STIFF the two are not read.
+template <bool DAMP, bool STIFF = false>
+__device__ __forceinline__ Lane make_lane(double dc, double a, double b, const Consts &K, double kappa = 0.0, double ikappa = 0.0) {
   Lane L;
   // reciprocals by rsf_math.h (<= 1 ulp from the IEEE quotient at a fifth of its instruction count)
   const double inv_a = fm::rcp(a);
   L.inv_dc = fm::rcp(dc);
-  L.kprime = (1e-2 * 10) * L.inv_dc;
+  if constexpr (STIFF) L.kprime = kappa * L.inv_dc;
+  else L.kprime = (1e-2 * 10) * L.inv_dc;
   L.kia = L.kprime * inv_a;
   L.khh = L.kia * K.hh;
   L.kh = L.kia * K.h;
@@ -104,7 +108,8 @@ __device__ __forceinline__ Lane make_lane(double dc, double a, double b, const C
   const double via = K.V_ref * inv_a;
   L.vdc = K.V_ref * L.inv_dc;
   L.vk = via * L.kprime;
-  L.beta = (b * K.V_ref) * (1.0 / (1e-2 * 10));
+  if constexpr (STIFF) L.beta = (b * K.V_ref) * ikappa;
+  else L.beta = (b * K.V_ref) * (1.0 / (1e-2 * 10));
   L.kvk = K.k1 * via;
   const double ikw = DAMP ? fm::rcp(L.kvk) : 1.0;
   const double vkw = DAMP ? L.vk * ikw : L.vk;
@@ -612,9 +617,12 @@ __device__ __forceinline__ double rk4_tight(State &s, double vl0, double vlm, do
   return __builtin_fma(2.0, sm, sv);
 }
 
-__device__ __forceinline__ State initial_state(double dc, const Lane &L, const Consts &K) {
+// STIFF: make_lane's; ikappa = 1 / (k Dc) stands for the reciprocal of the coupling's literal
+template <bool STIFF = false>
+__device__ __forceinline__ State initial_state(double dc, const Lane &L, const Consts &K, double ikappa = 0.0) {
   State s;
-  s.ms = (K.mu0 * dc) * (1.0 / (1e-2 * 10));  // mu(0)/k' = mu_t_zero/k', RateStateModel.py:367-377
+  if constexpr (STIFF) s.ms = (K.mu0 * dc) * ikappa;
+  else s.ms = (K.mu0 * dc) * (1.0 / (1e-2 * 10));  // mu(0)/k' = mu_t_zero/k', RateStateModel.py:367-377
   s.x = K.V_ref * ((dc * K.inv_vref) * L.inv_dc);  // V_ref theta(0)/Dc with theta(0) = Dc/V_ref: 1 to rounding
   s.V = K.V_ref;
   eval_full(s.ms, s.x, L, K, s.w, s.rx);

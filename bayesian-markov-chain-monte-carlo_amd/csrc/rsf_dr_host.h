@@ -1,8 +1,9 @@
 // rsf_dr_host.h — the host-side argument checks the delayed-rejection entry points share (internal: not installed): rsf_dr.hip's
-// rsf_dr_* and rsf_law_dr.hip's rsf_law_dr_*.  Host code only; the argument block DrArgs is rsf_kernels_dr.h's.
+// rsf_dr_*, rsf_law_dr.hip's rsf_law_dr_* and rsf_stiff.hip's rsf_stiff_*.  Host code only; the argument block DrArgs is rsf_kernels_dr.h's.
 #pragma once
 #include <cmath>
 
+#include "../../include/rsf_observe.h"
 #include "rsf_host.h"
 #include "rsf_kernels_dr.h"
 
@@ -48,6 +49,14 @@ inline int set_factors(const char *fn, rsf_ctx *c, int32_t d, int32_t n_groups, 
   HIP_TRY(hipMemcpyAsync(c->poolws.p, chol, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   A.chol = (const double *)c->poolws.p;
+  return RSF_OK;
+}
+
+// the law and the observable of a call (rsf_law_dr.hip, rsf_stiff.hip): rsf_law_observe's checks and messages under the caller's name
+inline int check_law(const char *fn, int32_t law, int32_t observable) {
+  if (law != RSF_LAW_AGEING && law != RSF_LAW_SLIP) return fail(RSF_ERR_INVALID, "%s: law is RSF_LAW_AGEING (0) or RSF_LAW_SLIP (1), not %d", fn, law);
+  if (observable != RSF_OBS_ACC && observable != RSF_OBS_MU && observable != RSF_OBS_THETA && observable != RSF_OBS_VELOCITY)
+    return fail(RSF_ERR_INVALID, "%s: observable is RSF_OBS_ACC (0), RSF_OBS_MU (1), RSF_OBS_THETA (2) or RSF_OBS_VELOCITY (3), not %d", fn, observable);
   return RSF_OK;
 }
 

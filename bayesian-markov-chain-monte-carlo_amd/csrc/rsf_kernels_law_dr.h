@@ -19,8 +19,11 @@ namespace rsfk {
 // taken by every wave of the workgroup whatever its lanes need.  A table that is RESIDENT (K.nchunks == 1) is staged once per
 // launch (`staged` remembers).  The arithmetic is law_observe_kernel's, call for call: the SSq is rsf_law_observe's bit for bit,
 // whatever the lane's neighbours are.  No tier, no guard: a NaN trajectory runs to its end and gives a non-finite SSq.
-template <int D, int LAW, bool DAMP>
-__device__ __forceinline__ double law_dr_solve(double *lds, const Consts &K, int32_t observable, bool inb, const double (&y)[D], bool &staged) {
+// STIFF (rsf_kernels_stiff.h): the spring's stiffness is `stiffness` (a kernel argument: wave-uniform), independent of Dc; the lane
+// forms kappa = stiffness Dc and its IEEE reciprocal once per solve for make_lane and initial_state, and nothing else differs.
+template <int D, int LAW, bool DAMP, bool STIFF = false>
+__device__ __forceinline__ double law_dr_solve(double *lds, const Consts &K, int32_t observable, bool inb, const double (&y)[D], bool &staged,
+                                               double stiffness = 0.0) {
   const double *ld = lds + rsf::lds_data_offset(K);
   double pq[3] = {1000.0, K.a_def, K.b_def};
   if (inb) {
@@ -32,8 +35,13 @@ __device__ __forceinline__ double law_dr_solve(double *lds, const Consts &K, int
   // the fused kernel's stage loop and hold them in vector registers across the whole iteration: 174 to 180 registers, past the
   // three-wave bracket of 168.  Opaque here, they are formed per stage as at D = 3: the same operations on the same values.
   if constexpr (D == 1) asm volatile("" : "+v"(pq[1]), "+v"(pq[2]));
-  const rsf::Lane L = rsf::make_lane<DAMP>(pq[0], pq[1], pq[2], K);
-  const rsf::State s0 = rsf::initial_state(pq[0], L, K);
+  double kappa = 0.0, ikappa = 0.0;
+  if constexpr (STIFF) {
+    kappa = stiffness * pq[0];
+    ikappa = 1.0 / kappa;
+  }
+  const rsf::Lane L = rsf::make_lane<DAMP, STIFF>(pq[0], pq[1], pq[2], K, kappa, ikappa);
+  const rsf::State s0 = rsf::initial_state<STIFF>(pq[0], L, K, ikappa);
   double ms = s0.ms, x = s0.x, V = s0.V, vprev = s0.V, ssq = 0.0;
   // law_observe_kernel's per-lane factor and sample 0, RESTATED: as functions shared with that kernel they change its instructions
   // (the operands of one product swap), and the parent build's kernels stay as they are

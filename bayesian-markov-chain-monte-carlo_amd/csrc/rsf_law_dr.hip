@@ -22,14 +22,6 @@ auto ssq_fn(const rsf_ctx *c, int d, int law) {
   return law_dr_fn(c, d, law, [](auto D, auto LAW, auto DAMP) { return law_dr_ssq_kernel<D, LAW, DAMP>; });
 }
 
-// the law and the observable of a call: rsf_law_observe's checks and messages under the caller's name
-int check_law(const char *fn, int32_t law, int32_t observable) {
-  if (law != RSF_LAW_AGEING && law != RSF_LAW_SLIP) return fail(RSF_ERR_INVALID, "%s: law is RSF_LAW_AGEING (0) or RSF_LAW_SLIP (1), not %d", fn, law);
-  if (observable != RSF_OBS_ACC && observable != RSF_OBS_MU && observable != RSF_OBS_THETA && observable != RSF_OBS_VELOCITY)
-    return fail(RSF_ERR_INVALID, "%s: observable is RSF_OBS_ACC (0), RSF_OBS_MU (1), RSF_OBS_THETA (2) or RSF_OBS_VELOCITY (3), not %d", fn, observable);
-  return RSF_OK;
-}
-
 }  // namespace
 
 extern "C" {

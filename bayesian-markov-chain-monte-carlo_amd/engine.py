@@ -155,12 +155,26 @@ def observable_of(model):
     return observable_name(getattr(model, "observable", "acc"))
 
 
+def stiffness_of(model):
+    """The stiffness of the apparatus, independent of Dc: None (the reference's coupling k' = 0.1 / Dc) or a finite float > 0."""
+    k = getattr(model, "stiffness", None)
+    if k is None:
+        return None
+    if isinstance(k, (bool, str)) or not np.isscalar(k) or not (math.isfinite(float(k)) and float(k) > 0.0):
+        raise ValueError(f"stiffness is None (the reference's coupling k' = 0.1 / Dc) or a finite float > 0, not {k!r}")
+    return float(k)
+
+
+_COUPLED = "the kernel integrates k' = 0.1 / Dc"
+
+
 def check_law_options(model):
-    """The slip law, a caller's loading history and an observable other than the acceleration run the float64 RK4 only → the
-    model's law."""
-    law, obs = state_law_of(model), observable_of(model)
+    """The slip law, a caller's loading history, an observable other than the acceleration and a stiffness independent of Dc run
+    the float64 RK4 only → the model's law."""
+    law, obs, k = state_law_of(model), observable_of(model), stiffness_of(model)
     integrator, precision = getattr(model, "integrator", "rk4"), getattr(model, "precision", "float64")
-    for what, on in ((f"state_law={law!r}", law == "slip"), ("a custom loading history", getattr(model, "loading", None) is not None)):
+    for what, on in ((f"state_law={law!r}", law == "slip"), ("a custom loading history", getattr(model, "loading", None) is not None),
+                     (f"stiffness={k!r}", k is not None)):
         if on and integrator == "dop853":
             raise NotImplementedError(f"{what} with integrator='dop853': the adaptive steps evaluate the built-in history and the ageing law")
         if on and precision == "float32":
@@ -741,6 +755,7 @@ class Engine:
         self.nout = None
         self.state_law = "aging"  # the model's (set_model)
         self.observable = "acc"   # the model's (set_model)
+        self.stiffness = None     # the model's (set_model): None, the reference's coupling k' = 0.1 / Dc, or the apparatus's
         self.n_chains = self.n_params = None
         self.world = self.rank = 0  # set by comm_init
 
@@ -792,9 +807,12 @@ class Engine:
         """rsf_set_model, then the model's own loading history (model.loading, if it has one: set_loading).  model.state_law
         is kept as self.state_law: the kernels of every family integrate the ageing law, so with 'slip' only law_forward and
         the calls built on it run (_need_model).  model.observable is kept as self.observable in the same way: the kernels of
-        every family fit the acceleration, so with another observable only law_observe and the calls that take an ssq_fn run."""
+        every family fit the acceleration, so with another observable only law_observe and the calls that take an ssq_fn run.
+        model.stiffness is kept as self.stiffness: only the kernels of include/rsf_stiff.h carry a stiffness independent of Dc, so
+        with one only law_observe, the law_dr calls and the calls that take an ssq_fn or residuals run (they route to stiff_*)."""
         law = check_law_options(model)
         observable = observable_of(model)
+        stiffness = stiffness_of(model)
         m = _model_struct(model, substeps)
         _abi.check(self.lib, self.lib.rsf_set_model(self._ctx, ctypes.byref(m)))
         n = ctypes.c_int32()
@@ -803,6 +821,7 @@ class Engine:
         self.model_args = (model, substeps)
         self.state_law = law
         self.observable = observable
+        self.stiffness = stiffness
         self.n_chains = self.n_params = None  # a new model invalidates the chains (rsf_abi.h: rsf_set_model)
         if getattr(model, "loading", None) is not None:
             try:
@@ -812,9 +831,13 @@ class Engine:
                 raise
         return self.nout
 
-    def _need_model(self, law_aware=False):
+    def _need_model(self, law_aware=False, stiff_aware=False):
         if self.nout is None:
             raise _abi.RsfError(-3, "call set_model first")
+        if not stiff_aware and getattr(self, "stiffness", None) is not None:
+            raise NotImplementedError(f"this call cannot run a model with stiffness={self.stiffness!r}: {_COUPLED}, the reference's spring; a "
+                                      "stiffness independent of Dc runs through law_observe, law_dr and the calls that take an ssq_fn or "
+                                      "residuals")
         if not law_aware and getattr(self, "state_law", "aging") != "aging":
             raise NotImplementedError(f"this call integrates the ageing law only, and the model's state_law is {self.state_law!r}: "
                                       "the slip law runs through law_forward and the calls that take an ssq_fn; the predictive checks under a law are "
@@ -835,14 +858,14 @@ class Engine:
 
     def loading_size(self):
         """the loading table's length, 2 substeps (nout - 1) + 1"""
-        self._need_model(law_aware=True)
+        self._need_model(law_aware=True, stiff_aware=True)
         n = ctypes.c_int64()
         _abi.check(self.lib, self._law_fn("rsf_loading_size")(self._ctx, ctypes.byref(n)))
         return n.value
 
     def loading_times(self):
         """the RK4 stage times t_start + j (delta_t / substeps) / 2 of the loading table, as rsf_set_model forms them"""
-        self._need_model(law_aware=True)
+        self._need_model(law_aware=True, stiff_aware=True)
         model, substeps = self.model_args
         hh = 0.5 * (((float(model.t_final) - float(model.t_start)) / int(model.num_tsteps)) / int(substeps))
         return float(model.t_start) + np.arange(2 * int(substeps) * (self.nout - 1) + 1, dtype=np.float64) * hh
@@ -851,7 +874,7 @@ class Engine:
         """rsf_set_loading: the loading history V_l of every float64 RK4 solve from here on, until the next set_model.  values: an
         array of loading_size() values at loading_times(), a callable t -> V_l (called once with loading_times()), or None for the
         built-in history.  The chains of an earlier mcmc_init are discarded."""
-        self._need_model(law_aware=True)
+        self._need_model(law_aware=True, stiff_aware=True)
         v = None
         if values is not None:
             t = self.loading_times()
@@ -900,11 +923,31 @@ class Engine:
             raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
                                     "symbol (include/rsf_observe.h)") from None
 
-    def law_observe(self, law, observable, dc, a=None, b=None, data=None, want_ssq=False, want_series=True):
+    def _stiff_fn(self, name):
+        """a function of include/rsf_stiff.h, which librsf_hip.so alone exports"""
+        try:
+            return getattr(self.lib, name)
+        except AttributeError:
+            raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
+                                    "symbol (include/rsf_stiff.h)") from None
+
+    def _stiffness(self, stiffness):
+        """the stiffness in force for a call: the keyword's, or (None) the engine's model's → a float, or None for the coupling"""
+        k = getattr(self, "stiffness", None) if stiffness is None else stiffness
+        return None if k is None else float(k)
+
+    def stiff_observe(self, law, observable, stiffness, dc, a=None, b=None, data=None, want_ssq=False, want_series=True):
+        """rsf_stiff_observe: law_observe — its arguments, checks and results — with the spring's stiffness `stiffness`, a constant
+        independent of Dc (include/rsf_stiff.h), in place of the reference's coupling k' = 0.1 / Dc."""
+        return self.law_observe(law, observable, dc, a=a, b=b, data=data, want_ssq=want_ssq, want_series=want_series, stiffness=float(stiffness))
+
+    def law_observe(self, law, observable, dc, a=None, b=None, data=None, want_ssq=False, want_series=True, stiffness=None):
         """rsf_law_observe: law_forward's solve, arguments and checks, → (ssq[C] | None, series[nout, C] | None) of `observable`:
         'acc' (law_forward's results, bit for bit), 'mu' (or 'friction'), 'theta' (or 'state'), 'velocity' (or 'V'); an integer
-        goes to the library as it is.  data is a series of the same observable."""
-        self._need_model(law_aware=True)
+        goes to the library as it is.  data is a series of the same observable.  stiffness: None, the engine's model's; with one
+        in force the call is rsf_stiff_observe."""
+        self._need_model(law_aware=True, stiff_aware=True)
+        k = self._stiffness(stiffness)
         if isinstance(law, str):
             if law not in _abi.LAWS:
                 raise ValueError(f"law is 'aging' (or 'ageing') or 'slip', not {law!r}")
@@ -920,19 +963,24 @@ class Engine:
             raise ValueError(f"data has {int(data.shape[0])} entries, the model produces {self.nout}")
         ssq = self._empty((C,)) if want_ssq else None
         series = self._empty((self.nout, C)) if want_series else None
+        if k is not None:
+            _abi.check(self.lib, self._stiff_fn("rsf_stiff_observe")(self._ctx, int(law), int(observable), k, C, self._ptr(dc), self._ptr(a),
+                                                                     self._ptr(b), self._ptr(data), self._ptr(ssq), self._ptr(series)))
+            return ssq, series
         _abi.check(self.lib, self._observe_fn("rsf_law_observe")(self._ctx, int(law), int(observable), C, self._ptr(dc), self._ptr(a), self._ptr(b),
                                                                  self._ptr(data), self._ptr(ssq), self._ptr(series)))
         return ssq, series
 
-    def law_ssq_fn(self, law, data, observable="acc"):
+    def law_ssq_fn(self, law, data, observable="acc", stiffness=None):
         """The ssq_fn of smc_from_ssq, dr_from_ssq, grid_from_ssq and grid_posterior for the device model under `law`: points
         (m, 1) of Dc or (m, 3) of (Dc, a, b) on the host → SSq (m,) on the host, solved by law_forward — or, with `data` a series
-        of another observable than 'acc', by law_observe."""
+        of another observable than 'acc' or with a stiffness in force (stiffness: None, the engine's model's), by law_observe."""
         obs = self._in(data)
-        if observable_name(observable) == "acc":
+        k = self._stiffness(stiffness)
+        if observable_name(observable) == "acc" and k is None:
             solve = lambda dc, a, b: self.law_forward(law, dc, a, b, data=obs, want_ssq=True, want_acc=False)[0]
         else:
-            solve = lambda dc, a, b: self.law_observe(law, observable, dc, a, b, data=obs, want_ssq=True, want_series=False)[0]
+            solve = lambda dc, a, b: self.law_observe(law, observable, dc, a, b, data=obs, want_ssq=True, want_series=False, stiffness=k)[0]
 
         def ssq_fn(pts):
             pts = np.asarray(pts, dtype=np.float64)
@@ -2744,46 +2792,65 @@ class Engine:
             observable = _abi.OBSERVABLES[observable_name(observable)]
         return int(law), int(observable)
 
+    def stiff_dr_run(self, law, observable, stiffness, q, l, data, lo, hi, chol, n_iter, counters, **kw):
+        """rsf_stiff_dr_run, the fused hot path of include/rsf_stiff.h: law_dr_run — its arguments, checks and results — with the
+        spring's stiffness `stiffness`, a constant independent of Dc."""
+        return self.law_dr_run(law, observable, q, l, data, lo, hi, chol, n_iter, counters, stiffness=float(stiffness), **kw)
+
+    def stiff_dr_ssq(self, law, observable, stiffness, y, mask, data, ssq=None):
+        """rsf_stiff_dr_ssq: law_dr_ssq with the spring's stiffness `stiffness` → stiff_observe's SSq bit for bit."""
+        return self.law_dr_ssq(law, observable, y, mask, data, ssq=ssq, stiffness=float(stiffness))
+
+    def _stiff_args(self, name, stiffness):
+        """(the entry point, the arguments between `observable` and the chains) of a law_dr call: rsf_law_dr_* without a stiffness
+        in force, rsf_stiff_dr_* and the stiffness with one"""
+        k = self._stiffness(stiffness)
+        if k is None:
+            return self._law_dr_fn("rsf_law_" + name), ()
+        return self._stiff_fn("rsf_stiff_" + name), (k,)
+
     def law_dr_run(self, law, observable, q, l, data, lo, hi, chol, n_iter, counters, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iter0=1,
-                   trace=False):
+                   trace=False, stiffness=None):
         """rsf_law_dr_run: dr_run — its arguments, checks and results — with the solve under the state law `law` against `data`,
-        series of `observable` (law_observe's names, aliases or integers), under the loading table in use."""
-        self._need_model(law_aware=True)
+        series of `observable` (law_observe's names, aliases or integers), under the loading table in use.  stiffness: None, the
+        engine's model's; with one in force the launch is rsf_stiff_dr_run."""
+        self._need_model(law_aware=True, stiff_aware=True)
         law, observable = self._law_codes(law, observable)
         n, d = self._dr_state(q, l, counters)
         data = self._in(data)
         G = int(data.shape[0]) if data.ndim == 2 else 1
         tri = self._dr_pack(self._dr_factors(chol, d, G))
-        fn = self._law_dr_fn("rsf_law_dr_run")
+        fn, k = self._stiff_args("dr_run", stiffness)
         tq, tl = (self._empty((int(n_iter), n, d)), self._empty((int(n_iter), n))) if trace else (None, None)
-        _abi.check(self.lib, fn(self._ctx, law, observable, n, d, self._ptr(q), self._ptr(l), self._ptr(data), G, _dp(_vec(lo, d, "lo")),
+        _abi.check(self.lib, fn(self._ctx, law, observable, *k, n, d, self._ptr(q), self._ptr(l), self._ptr(data), G, _dp(_vec(lo, d, "lo")),
                                 _dp(_vec(hi, d, "hi")), _dp(tri), float(gamma), int(stages), float(0.5 * self.nout if shape is None else shape),
                                 int(seed), int(offset), int(iter0), int(n_iter), *(self._ptr(c) for c in counters), self._ptr(tq), self._ptr(tl)))
         return (tq, tl) if trace else None
 
-    def law_dr_ssq(self, law, observable, y, mask, data, ssq=None):
+    def law_dr_ssq(self, law, observable, y, mask, data, ssq=None, stiffness=None):
         """rsf_law_dr_ssq: dr_ssq under `law` against `data` of `observable` → ssq (n,), law_observe's SSq bit for bit at dr_propose's
-        y (n, d) for the chains whose mask is 1, solved in law_dr_run's arrangement.  The other entries are ssq's (by default 1)."""
-        self._need_model(law_aware=True)
+        y (n, d) for the chains whose mask is 1, solved in law_dr_run's arrangement.  The other entries are ssq's (by default 1).
+        stiffness: None, the engine's model's; with one in force the launch is rsf_stiff_dr_ssq."""
+        self._need_model(law_aware=True, stiff_aware=True)
         law, observable = self._law_codes(law, observable)
         y, mask, data = self._in(y), self._bytes(mask), self._in(data)
         if y.ndim != 2 or tuple(mask.shape) != (int(y.shape[0]),):
             raise ValueError("y is (n, d), mask (n,)")
         n, d = int(y.shape[0]), int(y.shape[1])
         G = int(data.shape[0]) if data.ndim == 2 else 1
-        fn = self._law_dr_fn("rsf_law_dr_ssq")
+        fn, k = self._stiff_args("dr_ssq", stiffness)
         out = self._in(np.ones(n) if ssq is None else ssq)
         out = out.clone() if hasattr(out, "clone") else out.copy()
-        _abi.check(self.lib, fn(self._ctx, law, observable, n, d, self._ptr(y), self._ptr(mask), self._ptr(data), G, self._ptr(out)))
+        _abi.check(self.lib, fn(self._ctx, law, observable, *k, n, d, self._ptr(y), self._ptr(mask), self._ptr(data), G, self._ptr(out)))
         return out
 
-    def law_gn_factor(self, law, observable, q, data, rel_step=1e-4):
+    def law_gn_factor(self, law, observable, q, data, rel_step=1e-4, stiffness=None):
         """The Gauss-Newton proposal at the point q (d,), d = 1 (Dc) or 3 (Dc, a, b) → (L, cov, ssq): from ONE law_observe call of
         1 + d lanes, q and q + rel_step q_p e_p, the Jacobian J of the series by forward differences; cov = (SSq / nout) (J^T J)^-1,
         the Laplace covariance of the posterior at q, and L = chol((2.38^2 / d) cov), the random walk's factor.  What factor="init"
         is for the tier kernels, without an init kernel and without a fit.  ValueError where a series is not finite or the matrix
-        has no Cholesky factor."""
-        self._need_model(law_aware=True)
+        has no Cholesky factor.  stiffness: None, the engine's model's; law_observe's."""
+        self._need_model(law_aware=True, stiff_aware=True)
         law, observable = self._law_codes(law, observable)
         q = np.asarray(_host(q), dtype=np.float64).reshape(-1)
         d = q.size
@@ -2792,12 +2859,12 @@ class Engine:
         obs = _host(data).reshape(-1)
         if obs.size != self.nout:
             raise ValueError(f"data has {obs.size} entries, the model produces {self.nout}")
-        self._law_dr_fn("rsf_law_dr_run")  # the factor of this family's sampler: a library without it is refused here
+        self._stiff_args("dr_run", stiffness)  # the factor of this family's sampler: a library without it is refused here
         h = float(rel_step) * q
         pts = np.tile(q, (1 + d, 1))
         pts[1:] += np.diag(h)
         ab = [np.ascontiguousarray(pts[:, p]) for p in (1, 2)] if d == 3 else [None, None]
-        series = _host(self.law_observe(law, observable, np.ascontiguousarray(pts[:, 0]), ab[0], ab[1], want_series=True)[1])
+        series = _host(self.law_observe(law, observable, np.ascontiguousarray(pts[:, 0]), ab[0], ab[1], want_series=True, stiffness=stiffness)[1])
         if not np.isfinite(series).all():
             raise ValueError(f"law_gn_factor: the series at q = {q.tolist()} or beside it is not finite")
         r = series[:, 0] - obs
@@ -2814,25 +2881,28 @@ class Engine:
         return L, cov, ssq
 
     def law_dr(self, law, observable, q0, data, lo, hi, chol, n_iter, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iters_per_launch=16, keep=None,
-               thin=1, adapt_launches=0, iter0=1, l0=None):
+               thin=1, adapt_launches=0, iter0=1, l0=None, stiffness=None):
         """Engine.dr — its arguments, groups, adaptation, continuation and result, through the same driver — for the device model
         under the state law `law` against `data`, series of `observable`: the launch is law_dr_run, and the start's l is what
         dr_from_ssq forms, -shape log SSq in NumPy on the host from law_ssq_fn(law, data_g, observable) (-inf where SSq is not
         finite and > 0; such a start is refused).  With adapt_launches = 0 the run is dr_from_ssq(law_ssq_fn(...), ...)'s bit for
-        bit, from the first state on."""
-        self._need_model(law_aware=True)
+        bit, from the first state on.  stiffness: None, the engine's model's; with one in force the launches are rsf_stiff_dr_run's
+        and the start's l stiff_observe's."""
+        self._need_model(law_aware=True, stiff_aware=True)
+        stiffness = self._stiffness(stiffness)
         codes = self._law_codes(law, observable)
         if codes[1] not in _OBSERVABLE_NAMES:
             raise ValueError(f"observable is one of {sorted(_OBSERVABLE_NAMES)} (RSF_OBS_*), not {codes[1]}")
 
         def start_l(q, obs, lo, hi, shape):
-            s = np.asarray(self.law_ssq_fn(codes[0], obs, _OBSERVABLE_NAMES[codes[1]])(_host(q)), dtype=np.float64).reshape(-1)
+            s = np.asarray(self.law_ssq_fn(codes[0], obs, _OBSERVABLE_NAMES[codes[1]], stiffness=stiffness)(_host(q)), dtype=np.float64).reshape(-1)
             with np.errstate(divide="ignore", invalid="ignore"):
                 return np.where(np.isfinite(s) & (s > 0), -shape * np.log(s), -np.inf)
 
-        run = lambda q, l, obs, lo, hi, L, k, counters, **kw: self.law_dr_run(codes[0], codes[1], q, l, obs, lo, hi, L, k, counters, **kw)
+        run = lambda q, l, obs, lo, hi, L, k, counters, **kw: self.law_dr_run(codes[0], codes[1], q, l, obs, lo, hi, L, k, counters,
+                                                                              stiffness=stiffness, **kw)
         return self._dr_drive(run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin,
-                              adapt_launches, iter0, l0, ready=lambda: self._law_dr_fn("rsf_law_dr_run"))
+                              adapt_launches, iter0, l0, ready=lambda: self._stiff_args("dr_run", stiffness))
 
     # -- Levenberg-Marquardt under either state law and any observable (include/rsf_law_fit.h) ---------------------------
     def _law_fit_fn(self, name):
@@ -3053,7 +3123,7 @@ class Engine:
         ridge Dc a = const), axes 1 and 2 uniform over [lo, hi] with the faces, Simpson on every axis (odd n).  → GridPosterior.
         ssq_fn (d = 1 only; data is then not read): the same two stages with the nodes' sums of squares from the caller — ssq_fn(points
         (m, 1) float64 on the host) → SSq (m,), as grid_from_ssq calls it; law_ssq_fn(law, data) makes one for either state law."""
-        self._need_model(law_aware=ssq_fn is not None)
+        self._need_model(law_aware=ssq_fn is not None, stiff_aware=ssq_fn is not None)
         blo, bhi, d = self._smc_box(lo, hi)
         if d not in (1, 3):
             raise ValueError("the box has d = 1 (Dc) or 3 (Dc, a, b) parameters")
@@ -3422,8 +3492,8 @@ class Engine:
         return res
 
     # -- posterior predictive checks of pooled draws (include/rsf_predict.h) ---------------------
-    def _predict_args(self, q, std2, data, law_aware=False):
-        self._need_model(law_aware)
+    def _predict_args(self, q, std2, data, law_aware=False, stiff_aware=False):
+        self._need_model(law_aware, stiff_aware)
         q, std2, data = self._in(q), self._in(std2), self._in(data)
         if q.ndim == 1:
             q = q.reshape(-1, 1)
@@ -3570,10 +3640,10 @@ class Engine:
         return self._predictive(self.predictive_partials, lambda dc, a, b: self.forward(dc, a=a, b=b)[1], False, q, std2, data, probs, center,
                                 return_series, loo, r_eff, noise_probs)
 
-    def _predictive(self, partials, solve, law_aware, q, std2, data, probs, center, return_series, loo, r_eff, noise_probs):
+    def _predictive(self, partials, solve, law_aware, q, std2, data, probs, center, return_series, loo, r_eff, noise_probs, stiff_aware=False):
         """predictive's and law_predictive's body; partials: predictive_partials or law_predictive_partials behind its law,
         solve(dc, a, b): the series (nout, 1) at one point, for the default centre"""
-        q, std2, data, n, d = self._predict_args(q, std2, data, law_aware)
+        q, std2, data, n, d = self._predict_args(q, std2, data, law_aware, stiff_aware)
         probs, noise_probs = _probs(probs, False, True, "probs"), _probs(noise_probs, True, True, "noise_probs")
 
         if center is None:
@@ -3638,16 +3708,28 @@ class Engine:
         """predictive — its arguments, checks and result, key for key — for a model under the state law `law` whose data is a series
         of `observable` (law_observe's names, aliases or integers), under the loading table in use: the fused solve and reduction is
         rsf_law_predict_partials, the default centre the series of one law_observe call at the draws' mean point, and the
-        quantiles, the PSIS-LOO entries and noise_quantiles come from the series entry points predictive uses."""
-        self._need_model(law_aware=True)
+        quantiles, the PSIS-LOO entries and noise_quantiles come from the series entry points predictive uses.  A model with a
+        stiffness independent of Dc (set_model) runs the split route: law_observe's series of every draw (rsf_stiff_observe), then
+        series_partials on it — the fused kernel integrates k' = 0.1 / Dc."""
+        self._need_model(law_aware=True, stiff_aware=True)
         law, observable = self._law_codes(law, observable)
+        stiff = self._stiffness(None) is not None
 
         def centre(dc, a, b):
-            self._law_predict_fn("rsf_law_predict_partials")  # a library without this family is refused under its name, before any solve
+            # a library without this family is refused under its name, before any solve
+            self._law_predict_fn("rsf_predict_series_partials" if stiff else "rsf_law_predict_partials")
             return self.law_observe(law, observable, dc, a, b)[1]
 
-        return self._predictive(lambda *a, **kw: self.law_predictive_partials(law, observable, *a, **kw), centre, True, q, std2, data, probs, center,
-                                return_series, loo, r_eff, noise_probs)
+        def split(q, std2, data, center_y, center_l, return_series=False):
+            q, std2, data, n, d = self._predict_args(q, std2, data, True, True)
+            ab = [q[:, p] for p in (1, 2)] if d == 3 else [None, None]
+            series = self.law_observe(law, observable, q[:, 0], ab[0], ab[1])[1]
+            out = self.series_partials(series, std2, data, center_y, center_l)
+            return (out, series) if return_series else out
+
+        fused = lambda *a, **kw: self.law_predictive_partials(law, observable, *a, **kw)
+        return self._predictive(split if stiff else fused, centre, True, q, std2, data, probs, center, return_series, loo, r_eff, noise_probs,
+                                stiff_aware=True)
 
     # -- multi-GPU posterior pool through the C ABI (RCCL bound inside the library; SURVEY §8e) -----
     def comm_unique_id(self):
