@@ -20,17 +20,18 @@ reference would and the device runs the chain step on the sum of squares it is h
 (rsf_mcmc_init_state / rsf_mcmc_propose / rsf_mcmc_replay_ssq).
 """
 import contextlib
+import math
 
 import numpy as np
 
 if __package__:
     from . import _figures
     from ._abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from .engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, stiffness_of, whole_islands  # noqa: F401
+    from .engine import Engine, _host, bayes_factor, check_law_options, law_name, observable_of, state_law_of, stiffness_of, whole_islands  # noqa: F401
 else:  # flat layout: this directory on sys.path, the reference's own import style (main.py:44-46)
     import _figures
     from _abi import ADAPT_MODES, ERR_NOT_POSDEF, RsfError
-    from engine import Engine, _host, bayes_factor, law_name, observable_of, state_law_of, stiffness_of, whole_islands  # noqa: F401
+    from engine import Engine, _host, bayes_factor, check_law_options, law_name, observable_of, state_law_of, stiffness_of, whole_islands  # noqa: F401
 
 
 @contextlib.contextmanager
@@ -886,6 +887,64 @@ class MCMC:
             std2 = res.std2(engine=eng, kept=True)
             eng.sync()
         return self._dr_pool(res, std2, nburn, {"adapt": bool(adapt), "path": "law_dr"})
+
+    def sample_stiffness(self, n_chains, n_iter, stiffness_prior, nburn=None, start="qstart", factor="gn", gamma=0.2, stages=2, adapt=True, seed=0,
+                         mem="device", device=-1, chain_offset=0, thin=1, iters_per_launch=16):
+        """sample_law with the STIFFNESS OF THE APPARATUS INFERRED jointly (additive; Engine.kstiff_dr, include/rsf_kstiff.h): the
+        chains run over (Dc, k) for a one-parameter MCMC and over (Dc, a, b, k) for a three-parameter one, the stiffness the LAST
+        parameter of the returned PosteriorPool, under a uniform prior stiffness_prior = (klo, khi) with
+        0 < klo < model.stiffness < khi.  model.stiffness, the calibration's value, is where the chains start and nothing more:
+        start="qstart" puts every chain at (qstart..., model.stiffness); an array (n_chains, d + 1): there.  factor="gn":
+        Engine.kstiff_gn_factor at the start point (chain 0's for an array); an array (d + 1, d + 1): that lower triangular factor.
+        Everything else — the sampler, adapt, the target, sigma^2, nburn, thin, the PosteriorPool and its stats — is sample_law's;
+        stats["path"] is "kstiff_dr".  The MCMC object itself stays d = 1 or 3.
+
+        Why: a stiffness from a calibration run is good to some 10-20 %, and a wrong fixed value moves Dc.  On friction data from
+        Dc = 20, k = 2e-3 (noise 5 %, 500 steps) k fixed 20 % off puts the best Dc at 19.0 or 21.0 under a velocity-step history
+        and at 16.75 or 24.5 under a hold history: an 18 % error.
+
+        WHAT THE DATA DETERMINE depends on the loading history.  Under a velocity-step history all of (Dc, a, b, k) are determined:
+        at the truth the Gauss-Newton (Laplace) SDs are 1.2 %, 0.9 %, 0.6 % and 1.5 % of the values under the ageing law (1.6 %,
+        1.1 %, 0.7 %, 1.4 % under the slip law), and the column-scaled Jacobian's condition number is 7 (8).  Under a HOLD history
+        the four-parameter problem is nearly degenerate: the SDs of (Dc, a, b, k) are 101 %, 8 %, 50 % and 1.7 % of the values and
+        the condition number is 160, so the d = 4 posterior there is set by the prior box as much as by the data, the Gauss-Newton
+        factor is a poor start and the chains mix slowly.  That is a fact about the experiment, not the sampler.  The two-parameter
+        problem (Dc, k), with (a, b) known, is well determined under both histories (SDs 0.6-1.6 %, condition number below 2).
+        (tests/test_kstiff_reference.py asserts every figure here to 3 % of it.)"""
+        n_chains, n_iter, ipl = int(n_chains), int(n_iter), int(iters_per_launch)
+        nburn = n_iter // 2 if nburn is None else int(nburn)
+        if n_chains < 1 or n_iter < 1 or not 0 <= nburn < n_iter or int(thin) < 1 or ipl < 1:
+            raise ValueError("n_chains >= 1, n_iter >= 1, 0 <= nburn < n_iter, thin >= 1, iters_per_launch >= 1")
+        if isinstance(start, str) and start != "qstart":
+            raise ValueError(f"start is 'qstart' or an array of chains, not {start!r}")
+        if isinstance(factor, str) and factor != "gn":
+            raise ValueError(f"factor is 'gn' or a (d + 1, d + 1) array, not {factor!r}")
+        if not self._device_model():
+            raise TypeError("sample_stiffness integrates the model on the device: `model` must be this package's RateStateModel")
+        k0 = self._stiffness()
+        if k0 is None:
+            raise ValueError("sample_stiffness starts the chains at model.stiffness, the calibration's value: the model has none")
+        klo, khi = (float(v) for v in stiffness_prior)
+        if not (math.isfinite(khi) and 0.0 < klo < k0 < khi):
+            raise ValueError(f"stiffness_prior = (klo, khi) with 0 < klo < model.stiffness < khi, not ({klo!r}, {khi!r}) around {k0!r}")
+        check_law_options(self.model)  # integrator='dop853', precision='float32': NotImplementedError, the solve is the float64 RK4
+        data = np.ascontiguousarray(self.data, dtype=np.float64).reshape(-1)
+        lo, hi = np.append(self.qstart_limits[:, 0], klo), np.append(self.qstart_limits[:, 1], khi)
+        d, law, observable = self.n_params + 1, self._law(), self._observable()
+        if isinstance(start, str):
+            q0 = np.tile(np.append(np.asarray(self.qstart, dtype=np.float64).reshape(-1), k0).reshape(1, d), (n_chains, 1))
+        else:
+            q0 = _host(start).reshape(-1, d)
+            if q0.shape[0] != n_chains:
+                raise ValueError(f"start holds {q0.shape[0]} chains, not {n_chains}")
+        with Engine(mem=mem, device=device) as eng:
+            eng.set_model(self.model, getattr(self.model, "substeps", 1))
+            L = eng.kstiff_gn_factor(law, observable, q0[0], data)[0] if isinstance(factor, str) else np.asarray(factor, dtype=np.float64).reshape(d, d)
+            res = eng.kstiff_dr(law, observable, q0, data, lo, hi, L, n_iter, gamma=gamma, stages=stages, seed=seed, offset=chain_offset,
+                                iters_per_launch=ipl, keep=n_iter - nburn, thin=thin, adapt_launches=nburn // ipl if adapt else 0)
+            std2 = res.std2(engine=eng, kept=True)
+            eng.sync()
+        return self._dr_pool(res, std2, nburn, {"adapt": bool(adapt), "path": "kstiff_dr"})
 
     def quadrature(self, n=None, n_draws=0, seed=0, coords=None, window_sd=12.0, mem="device", device=-1):
         """The exact posterior by quadrature on the GPU (additive; Engine.grid_posterior): the n0 = 0 target

@@ -342,6 +342,17 @@ STIFF_PROTOTYPES = {
     "rsf_stiff_dr_run": (c_int, [c_void_p, c_int32, c_int32, c_double] + DR_PROTOTYPES["rsf_dr_run"][1][1:]),
     "rsf_stiff_dr_ssq": (c_int, [c_void_p, c_int32, c_int32, c_double] + DR_PROTOTYPES["rsf_dr_ssq"][1][1:]),
 }
+# include/rsf_kstiff.h: the delayed-rejection sampler of the state-law solve with the stiffness among the parameters, the last of
+# d = 2 (Dc, k) or 4 (Dc, a, b, k) coordinates; exported by librsf_hip.so only, bound by load().  rsf_stiff_observe's arguments with
+# the stiffness an array behind b, rsf_law_dr_run's and rsf_law_dr_ssq's as they are, rsf_dr_propose's and rsf_dr_accept's
+KSTIFF_PROTOTYPES = {
+    "rsf_kstiff_observe": (c_int, OBSERVE_PROTOTYPES["rsf_law_observe"][1][:7] + [_P] + OBSERVE_PROTOTYPES["rsf_law_observe"][1][7:]),
+    "rsf_kstiff_dr_run": (c_int, list(LAW_DR_PROTOTYPES["rsf_law_dr_run"][1])),
+    "rsf_kstiff_dr_ssq": (c_int, list(LAW_DR_PROTOTYPES["rsf_law_dr_ssq"][1])),
+    "rsf_kstiff_dr_propose": (c_int, list(DR_PROTOTYPES["rsf_dr_propose"][1])),
+    "rsf_kstiff_dr_accept": (c_int, list(DR_PROTOTYPES["rsf_dr_accept"][1])),
+}
+KSTIFF_MAX_PARAMS = 4  # RSF_KSTIFF_MAX_PARAMS
 # include/rsf_law_fit.h: the Levenberg-Marquardt fit under either state law and any observable; exported by librsf_hip.so only, bound by
 # load().  rsf_fit_normal's and rsf_fit_run's arguments behind (ctx, law, observable)
 LAW_FIT_PROTOTYPES = {
@@ -413,7 +424,7 @@ def load():
         for table in (DIAG_PROTOTYPES, PREDICT_PROTOTYPES, PSIS_PROTOTYPES, PREDICT_NOISE_PROTOTYPES, JOINT_PROTOTYPES, EVIDENCE_PROTOTYPES,
                       SMC_PROTOTYPES, SMC_BATCH_PROTOTYPES, FIT_PROTOTYPES, MALA_PROTOTYPES, ENSEMBLE_PROTOTYPES, GRID_PROTOTYPES,
                       DR_PROTOTYPES, LAW_PROTOTYPES, OBSERVE_PROTOTYPES, LAW_DR_PROTOTYPES, LAW_PREDICT_PROTOTYPES, LAW_FIT_PROTOTYPES,
-                      LAW_GRID_PROTOTYPES, STIFF_PROTOTYPES):
+                      LAW_GRID_PROTOTYPES, STIFF_PROTOTYPES, KSTIFF_PROTOTYPES):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = restype, argtypes

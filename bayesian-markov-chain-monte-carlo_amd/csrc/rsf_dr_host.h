@@ -1,7 +1,9 @@
 // rsf_dr_host.h — the host-side argument checks the delayed-rejection entry points share (internal: not installed): rsf_dr.hip's
-// rsf_dr_*, rsf_law_dr.hip's rsf_law_dr_* and rsf_stiff.hip's rsf_stiff_*.  Host code only; the argument block DrArgs is rsf_kernels_dr.h's.
+// rsf_dr_*, rsf_law_dr.hip's rsf_law_dr_*, rsf_stiff.hip's rsf_stiff_* and rsf_kstiff.hip's rsf_kstiff_*.  Host code only; the argument block DrArgs is
+// rsf_kernels_dr.h's, the wider one of the rsf_kstiff_* calls rsf_kernels_kstiff.h's.
 #pragma once
 #include <cmath>
+#include <type_traits>
 
 #include "../../include/rsf_observe.h"
 #include "rsf_host.h"
@@ -13,11 +15,22 @@ namespace rsfh {
 
 using rsfk::DrArgs;
 
+// The trait of an argument block whose chains carry the stiffness as the LAST of d = 2 or 4 coordinates, in every call of the
+// family; the unit that owns such a block says so by a specialisation (rsf_kstiff.hip for rsf_kernels_kstiff.h's KDrArgs).  Every
+// other block takes rsf_dr.h's dimensions: d = 1 or 3 where the call solves, 1 to RSF_DR_MAX_PARAMS where it does not.
+template <class ARGS> struct stiffness_last : std::false_type {};
+
 // what the calls share: the chains and their groups, the box and the Philox stream; iterations first .. first + count - 1.
 // whole_blocks: a group's chains are whole workgroups (the calls that solve)
+// ARGS: DrArgs, or a family's own block; the dimensions a block takes are its trait's (stiffness_last)
+template <class ARGS>
 inline int set_chains(const char *fn, const rsf_ctx *c, int64_t n, int32_t d, bool solve, int32_t n_groups, const double *lo, const double *hi, uint64_t seed,
-               int64_t offset, int64_t first, int64_t count, DrArgs &A) {
-  if (solve ? (d != 1 && d != 3) : (d < 1 || d > RSF_DR_MAX_PARAMS)) return fail(RSF_ERR_INVALID, "%s: need %s", fn, solve ? "d = 1 or 3" : "1 <= d <= 3");
+               int64_t offset, int64_t first, int64_t count, ARGS &A) {
+  if constexpr (stiffness_last<ARGS>::value) {
+    if (d != 2 && d != 4) return fail(RSF_ERR_INVALID, "%s: need d = 2 or 4", fn);
+  } else if (solve ? (d != 1 && d != 3) : (d < 1 || d > RSF_DR_MAX_PARAMS)) {
+    return fail(RSF_ERR_INVALID, "%s: need %s", fn, solve ? "d = 1 or 3" : "1 <= d <= 3");
+  }
   if (n < 1) return fail(RSF_ERR_INVALID, "%s: need n >= 1", fn);
   if (n_groups < 1 || n_groups > RSF_DR_MAX_GROUPS) return fail(RSF_ERR_INVALID, "%s: need 1 <= n_groups <= %d", fn, RSF_DR_MAX_GROUPS);
   if (n_groups > 1 && (n % n_groups || (solve && (n / n_groups) % c->block)))
@@ -35,7 +48,8 @@ inline int set_chains(const char *fn, const rsf_ctx *c, int64_t n, int32_t d, bo
 
 // chol[n_groups][d (d + 1) / 2], HOST: every entry finite, every diagonal entry positive → the ctx's poolws workspace, in A.chol.
 // One copy; the stream is synchronised before the caller's array may go away.
-inline int set_factors(const char *fn, rsf_ctx *c, int32_t d, int32_t n_groups, const double *chol, DrArgs &A) {
+template <class ARGS>
+inline int set_factors(const char *fn, rsf_ctx *c, int32_t d, int32_t n_groups, const double *chol, ARGS &A) {
   const int ne = d * (d + 1) / 2;
   for (int g = 0; g < n_groups; ++g)
     for (int p = 0, e = 0; p < d; ++p)
@@ -52,7 +66,7 @@ inline int set_factors(const char *fn, rsf_ctx *c, int32_t d, int32_t n_groups, 
   return RSF_OK;
 }
 
-// the law and the observable of a call (rsf_law_dr.hip, rsf_stiff.hip): rsf_law_observe's checks and messages under the caller's name
+// the law and the observable of a call (rsf_law_dr.hip, rsf_stiff.hip, rsf_kstiff.hip): rsf_law_observe's checks and messages under the caller's name
 inline int check_law(const char *fn, int32_t law, int32_t observable) {
   if (law != RSF_LAW_AGEING && law != RSF_LAW_SLIP) return fail(RSF_ERR_INVALID, "%s: law is RSF_LAW_AGEING (0) or RSF_LAW_SLIP (1), not %d", fn, law);
   if (observable != RSF_OBS_ACC && observable != RSF_OBS_MU && observable != RSF_OBS_THETA && observable != RSF_OBS_VELOCITY)

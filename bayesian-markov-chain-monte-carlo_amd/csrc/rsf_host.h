@@ -59,6 +59,8 @@ enum Slot : int {
   SLOT_Q_NEW = SLOT_TQ, SLOT_IN_BOUNDS = SLOT_TA,
   // rsf_forward_batch
   SLOT_DC = SLOT_Z, SLOT_A = SLOT_U, SLOT_B = SLOT_G, SLOT_DATA = SLOT_TQ, SLOT_SSQ_OUT = SLOT_TS, SLOT_ACC_OUT = SLOT_TA,
+  // rsf_kstiff_observe: rsf_forward_batch's slots, and the stiffness of each point
+  SLOT_STIFFNESS = SLOT_SSQ_NEW,
   // rsf_mcmc_init (q0 in SLOT_Q), rsf_mcmc_get_state / _set_state / _init_state
   SLOT_Q = SLOT_Z, SLOT_V = SLOT_U,
   // rsf_pool_summary / _kde / _histogram, rsf_diag_partials, rsf_diag_rank_prepare: the samples or the trace in SLOT_X

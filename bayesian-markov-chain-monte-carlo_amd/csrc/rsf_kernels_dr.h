@@ -34,15 +34,18 @@ __device__ __forceinline__ double dr_logtarget(double ssq, double shape) {
   return (__builtin_isfinite(ssq) && ssq > 0.0) ? -shape * log(ssq) : -INFINITY;
 }
 
+// The pieces below take the argument block as a deduced parameter ARGS: DrArgs here, and rsf_kernels_kstiff.h's wider block
+// (lo / hi of four parameters) — DrArgs itself is a kernel argument of every instance of this family and stays as it is.
+
 // a chain that may move: strictly inside the box with a finite l
-template <int D>
-__device__ __forceinline__ bool dr_healthy(const DrArgs &A, const double (&x)[D], double l) {
+template <int D, class ARGS>
+__device__ __forceinline__ bool dr_healthy(const ARGS &A, const double (&x)[D], double l) {
   return in_box<D>(x, A) && __builtin_isfinite(l);
 }
 
 // the D normals of (seed, gid, it) from the slots s01 (components 0 and 1) and s2 (component 2): smc_proposal's draws for slots 0 and 1
-template <int D>
-__device__ __forceinline__ void dr_normals(const DrArgs &A, uint64_t gid, uint32_t it, uint32_t s01, uint32_t s2, double (&z)[4]) {
+template <int D, class ARGS>
+__device__ __forceinline__ void dr_normals(const ARGS &A, uint64_t gid, uint32_t it, uint32_t s01, uint32_t s2, double (&z)[4]) {
   uint32_t w[4];
   z[0] = z[1] = z[2] = z[3] = 0.0;
   rsf::draw_words(A.seed, gid, it, s01, w);
@@ -51,7 +54,8 @@ __device__ __forceinline__ void dr_normals(const DrArgs &A, uint64_t gid, uint32
 }
 
 // the logarithms of the two accept uniforms of (seed, gid, it): U1 = u53(w0, w1), U2 = u53(w2, w3) of the accept slot
-__device__ __forceinline__ void dr_log_uniforms(const DrArgs &A, uint64_t gid, uint32_t it, double &log_u1, double &log_u2) {
+template <class ARGS>
+__device__ __forceinline__ void dr_log_uniforms(const ARGS &A, uint64_t gid, uint32_t it, double &log_u1, double &log_u2) {
   uint32_t w[4];
   rsf::draw_words(A.seed, gid, it, rsf::SLOT_U, w);
   log_u1 = rsf::rng_log(rsf::u53(w[0], w[1]));
@@ -59,8 +63,8 @@ __device__ __forceinline__ void dr_log_uniforms(const DrArgs &A, uint64_t gid, u
 }
 
 // Stage 1: y1 = q + L z1 in propose<D>'s own arithmetic (smc_proposal's point) → inside the strict box?  L: the group's factor
-template <int D>
-__device__ __forceinline__ bool dr_stage1(const DrArgs &A, const double *__restrict__ L, uint64_t gid, uint32_t it, const double (&q)[D],
+template <int D, class ARGS>
+__device__ __forceinline__ bool dr_stage1(const ARGS &A, const double *__restrict__ L, uint64_t gid, uint32_t it, const double (&q)[D],
                                           double (&y)[D]) {
   double z[4];
   dr_normals<D>(A, gid, it, rsf::SLOT_Z01, rsf::SLOT_Z2, z);
@@ -69,8 +73,8 @@ __device__ __forceinline__ bool dr_stage1(const DrArgs &A, const double *__restr
 }
 
 // Stage 2: y2 = q + gamma (L z2), every product and sum rounded, in the specification's order → inside the strict box?
-template <int D>
-__device__ __forceinline__ bool dr_stage2(const DrArgs &A, const double *__restrict__ L, uint64_t gid, uint32_t it, const double (&q)[D],
+template <int D, class ARGS>
+__device__ __forceinline__ bool dr_stage2(const ARGS &A, const double *__restrict__ L, uint64_t gid, uint32_t it, const double (&q)[D],
                                           double (&y)[D]) {
 #pragma clang fp contract(off)
   double z[4];
@@ -89,8 +93,8 @@ __device__ __forceinline__ bool dr_stage2(const DrArgs &A, const double *__restr
 // The stage 2 decision for a proposal INSIDE the box, after a stage 1 that was rejected with l1 (-inf: outside the box or no
 // target value there): log alpha2 = (l2 - l) + log q + log(1 - alpha1(y2, y1)) - log(1 - alpha1(q, y1)) against log U2.  Both
 // stages' normals come from the stream again: nothing of them is kept across a solve.
-template <int D>
-__device__ __forceinline__ bool dr_decide2(const DrArgs &A, uint64_t gid, uint32_t it, double l, double l1, double l2, double log_u2) {
+template <int D, class ARGS>
+__device__ __forceinline__ bool dr_decide2(const ARGS &A, uint64_t gid, uint32_t it, double l, double l1, double l2, double log_u2) {
 #pragma clang fp contract(off)
   if (!__builtin_isfinite(l2)) return false;
   double z1[4], z2[4];
@@ -112,8 +116,8 @@ __device__ __forceinline__ bool dr_decide2(const DrArgs &A, uint64_t gid, uint32
 }
 
 // the factor of chain j's group
-template <int D>
-__device__ __forceinline__ const double *dr_factor(const DrArgs &A, int64_t j) {
+template <int D, class ARGS>
+__device__ __forceinline__ const double *dr_factor(const ARGS &A, int64_t j) {
   return A.chol + (A.group_chains > 0 ? j / A.group_chains : 0) * (D * (D + 1) / 2);
 }
 
@@ -206,7 +210,8 @@ __device__ __forceinline__ double dr_solve(double *lds, const Consts &K, bool in
 }
 
 // the observation series of the workgroup whose first chain is `first` (a group's chains are whole workgroups)
-__device__ __forceinline__ void dr_select_group(Consts &K, const DrArgs &A, int64_t first) {
+template <class ARGS>
+__device__ __forceinline__ void dr_select_group(Consts &K, const ARGS &A, int64_t first) {
   if (A.group_chains > 0) K.data += (first / A.group_chains) * K.nout;
 }
 

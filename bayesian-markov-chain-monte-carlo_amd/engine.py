@@ -2554,13 +2554,17 @@ class Engine:
         inside the box with a finite l proposes y1; stage 2: the chains whose `pending` byte (dr_accept's of stage 1) is 1 propose
         y2.  mask is 1 for a proposal inside the box; a chain that does not propose has y = q and mask 0.  chol (d, d), or
         (G, d, d) with the chains split evenly over the G factors."""
+        return self._dr_propose(self.lib.rsf_dr_propose, q, l, lo, hi, chol, stage, gamma, pending, seed, offset, iteration)
+
+    def _dr_propose(self, fn, q, l, lo, hi, chol, stage, gamma, pending, seed, offset, iteration):
+        """dr_propose through the entry point fn: rsf_dr_propose, or rsf_kstiff_dr_propose (kstiff_dr_propose)"""
         n, d = self._dr_state(q, l)
         L = self._dr_factors(chol, d)
         y, mask = self._empty((n, d)), self._bytes(np.zeros(n, dtype=np.uint8))
         pend = None if pending is None else self._bytes(pending)
-        _abi.check(self.lib, self.lib.rsf_dr_propose(self._ctx, n, d, self._ptr(q), self._ptr(l), int(L.shape[0]), _dp(_vec(lo, d, "lo")),
-                                                     _dp(_vec(hi, d, "hi")), _dp(self._dr_pack(L)), float(gamma), int(stage), int(seed), int(offset),
-                                                     int(iteration), self._ptr(pend), self._ptr(y), self._ptr(mask)))
+        _abi.check(self.lib, fn(self._ctx, n, d, self._ptr(q), self._ptr(l), int(L.shape[0]), _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")),
+                                _dp(self._dr_pack(L)), float(gamma), int(stage), int(seed), int(offset), int(iteration), self._ptr(pend), self._ptr(y),
+                                self._ptr(mask)))
         return y, mask
 
     def dr_ssq(self, y, mask, data, ssq=None):
@@ -2582,6 +2586,10 @@ class Engine:
         """rsf_dr_accept: the decision of one stage with the caller's sums of squares ssq (n,), read where mask is 1, at dr_propose's
         y, IN PLACE in q, l and the five int32 counters.  Stage 1 → (l1 (n,), pending (n,) uint8): l(y1) (-inf outside the box) and
         1 for the chains that go on to stage 2, which stage 2 takes back."""
+        return self._dr_accept(self.lib.rsf_dr_accept, q, l, lo, hi, stage, y, mask, ssq, counters, shape, gamma, l1, pending, seed, offset, iteration)
+
+    def _dr_accept(self, fn, q, l, lo, hi, stage, y, mask, ssq, counters, shape, gamma, l1, pending, seed, offset, iteration):
+        """dr_accept through the entry point fn: rsf_dr_accept, or rsf_kstiff_dr_accept (kstiff_dr_accept)"""
         n, d = self._dr_state(q, l, counters)
         y, mask, ssq = self._in(y), self._bytes(mask), self._in(ssq)
         if (tuple(y.shape), tuple(mask.shape), tuple(ssq.shape)) != ((n, d), (n,), (n,)):
@@ -2594,10 +2602,9 @@ class Engine:
             l1, pending = self._in(l1), self._bytes(pending)
             if (tuple(l1.shape), tuple(pending.shape)) != ((n,), (n,)):
                 raise ValueError(f"l1 and pending are ({n},)")
-        _abi.check(self.lib, self.lib.rsf_dr_accept(self._ctx, n, d, self._ptr(q), self._ptr(l), _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")),
-                                                    float(gamma), int(stage), float(shape), int(seed), int(offset), int(iteration), self._ptr(y),
-                                                    self._ptr(mask), self._ptr(ssq), self._ptr(l1), self._ptr(pending),
-                                                    *(self._ptr(c) for c in counters)))
+        _abi.check(self.lib, fn(self._ctx, n, d, self._ptr(q), self._ptr(l), _dp(_vec(lo, d, "lo")), _dp(_vec(hi, d, "hi")), float(gamma), int(stage),
+                                float(shape), int(seed), int(offset), int(iteration), self._ptr(y), self._ptr(mask), self._ptr(ssq), self._ptr(l1),
+                                self._ptr(pending), *(self._ptr(c) for c in counters)))
         return l1, pending
 
     def _dr_args(self, q0, lo, hi, chol, dims, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches, iter0):
@@ -2673,13 +2680,13 @@ class Engine:
                               adapt_launches, iter0, l0)
 
     def _dr_drive(self, run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches,
-                  iter0, l0, ready=None):
-        """What Engine.dr and Engine.law_dr share, everything but the solve: the checks, the groups, the launches of `run`
-        (dr_run's signature) with the burn-in adaptation between them, the kept traces.  start_l(q (per, d) in this engine's
-        memory space, obs (nout,) on the host, lo, hi, shape) → the start's l of one group on the host; ready(): called after the
-        argument checks and before the first library call."""
+                  iter0, l0, ready=None, dims=(1, 3)):
+        """What Engine.dr, Engine.law_dr and Engine.kstiff_dr share, everything but the solve: the checks, the groups, the launches
+        of `run` (dr_run's signature) with the burn-in adaptation between them, the kept traces.  start_l(q (per, d) in this
+        engine's memory space, obs (nout,) on the host, lo, hi, shape) → the start's l of one group on the host; ready(): called
+        after the argument checks and before the first library call; dims: the chain dimensions `run` takes."""
         q0, lo, hi, d, L, n_iter, gamma, stages, shape, seed, offset, ipl, keep, thin, adapt, iter0 = self._dr_args(
-            q0, lo, hi, chol, (1, 3), n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches, iter0)
+            q0, lo, hi, chol, dims, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin, adapt_launches, iter0)
         shape = 0.5 * self.nout if shape is None else shape
         obs = _host(data)
         obs = obs.reshape(1, -1) if obs.ndim == 1 else obs
@@ -2815,12 +2822,18 @@ class Engine:
         series of `observable` (law_observe's names, aliases or integers), under the loading table in use.  stiffness: None, the
         engine's model's; with one in force the launch is rsf_stiff_dr_run."""
         self._need_model(law_aware=True, stiff_aware=True)
+        return self._law_dr_run(lambda: self._stiff_args("dr_run", stiffness), law, observable, q, l, data, lo, hi, chol, n_iter, counters, gamma,
+                                stages, shape, seed, offset, iter0, trace)
+
+    def _law_dr_run(self, entry, law, observable, q, l, data, lo, hi, chol, n_iter, counters, gamma, stages, shape, seed, offset, iter0, trace):
+        """law_dr_run through entry() → (the entry point, the arguments between `observable` and the chains), asked for after the
+        argument checks: rsf_law_dr_run (), rsf_stiff_dr_run (stiffness,) or rsf_kstiff_dr_run () (kstiff_dr_run)"""
         law, observable = self._law_codes(law, observable)
         n, d = self._dr_state(q, l, counters)
         data = self._in(data)
         G = int(data.shape[0]) if data.ndim == 2 else 1
         tri = self._dr_pack(self._dr_factors(chol, d, G))
-        fn, k = self._stiff_args("dr_run", stiffness)
+        fn, k = entry()
         tq, tl = (self._empty((int(n_iter), n, d)), self._empty((int(n_iter), n))) if trace else (None, None)
         _abi.check(self.lib, fn(self._ctx, law, observable, *k, n, d, self._ptr(q), self._ptr(l), self._ptr(data), G, _dp(_vec(lo, d, "lo")),
                                 _dp(_vec(hi, d, "hi")), _dp(tri), float(gamma), int(stages), float(0.5 * self.nout if shape is None else shape),
@@ -2832,13 +2845,17 @@ class Engine:
         y (n, d) for the chains whose mask is 1, solved in law_dr_run's arrangement.  The other entries are ssq's (by default 1).
         stiffness: None, the engine's model's; with one in force the launch is rsf_stiff_dr_ssq."""
         self._need_model(law_aware=True, stiff_aware=True)
+        return self._law_dr_ssq(lambda: self._stiff_args("dr_ssq", stiffness), law, observable, y, mask, data, ssq)
+
+    def _law_dr_ssq(self, entry, law, observable, y, mask, data, ssq):
+        """law_dr_ssq through entry(), as _law_dr_run"""
         law, observable = self._law_codes(law, observable)
         y, mask, data = self._in(y), self._bytes(mask), self._in(data)
         if y.ndim != 2 or tuple(mask.shape) != (int(y.shape[0]),):
             raise ValueError("y is (n, d), mask (n,)")
         n, d = int(y.shape[0]), int(y.shape[1])
         G = int(data.shape[0]) if data.ndim == 2 else 1
-        fn, k = self._stiff_args("dr_ssq", stiffness)
+        fn, k = entry()
         out = self._in(np.ones(n) if ssq is None else ssq)
         out = out.clone() if hasattr(out, "clone") else out.copy()
         _abi.check(self.lib, fn(self._ctx, law, observable, *k, n, d, self._ptr(y), self._ptr(mask), self._ptr(data), G, self._ptr(out)))
@@ -2865,8 +2882,13 @@ class Engine:
         pts[1:] += np.diag(h)
         ab = [np.ascontiguousarray(pts[:, p]) for p in (1, 2)] if d == 3 else [None, None]
         series = _host(self.law_observe(law, observable, np.ascontiguousarray(pts[:, 0]), ab[0], ab[1], want_series=True, stiffness=stiffness)[1])
+        return self._gn_factor("law_gn_factor", q, h, obs, series)
+
+    def _gn_factor(self, name, q, h, obs, series):
+        """The rule law_gn_factor and kstiff_gn_factor share: series (nout, 1 + d) at q and at q + h_p e_p, the data obs → (L, cov, ssq)"""
+        d = q.size
         if not np.isfinite(series).all():
-            raise ValueError(f"law_gn_factor: the series at q = {q.tolist()} or beside it is not finite")
+            raise ValueError(f"{name}: the series at q = {q.tolist()} or beside it is not finite")
         r = series[:, 0] - obs
         ssq = float(r @ r)
         J = (series[:, 1:] - series[:, :1]) / h
@@ -2876,7 +2898,7 @@ class Engine:
                 raise np.linalg.LinAlgError
             L = np.linalg.cholesky((2.38 ** 2 / d) * cov)
         except np.linalg.LinAlgError:
-            raise ValueError(f"law_gn_factor: (SSq / nout) (J^T J)^-1 at q = {q.tolist()} has no Cholesky factor (a parameter the series "
+            raise ValueError(f"{name}: (SSq / nout) (J^T J)^-1 at q = {q.tolist()} has no Cholesky factor (a parameter the series "
                              "does not depend on, or a step too small for it)") from None
         return L, cov, ssq
 
@@ -2903,6 +2925,120 @@ class Engine:
                                                                               stiffness=stiffness, **kw)
         return self._dr_drive(run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin,
                               adapt_launches, iter0, l0, ready=lambda: self._stiff_args("dr_run", stiffness))
+
+    # -- the stiffness among the parameters: chains over (Dc, k) or (Dc, a, b, k) (include/rsf_kstiff.h) -----------------
+    # These calls take the stiffness from the points, its last coordinate, whatever the engine's model's stiffness is.
+    def _kstiff_fn(self, name):
+        """a function of include/rsf_kstiff.h, which librsf_hip.so alone exports"""
+        try:
+            return getattr(self.lib, name)
+        except AttributeError:
+            raise _abi.RsfError(-5, f"{name} is exported by librsf_hip.so only: the {self.lib.rsf_backend().decode()!r} library has no such "
+                                    "symbol (include/rsf_kstiff.h)") from None
+
+    def kstiff_observe(self, law, observable, dc, k, a=None, b=None, data=None, want_ssq=False, want_series=True):
+        """rsf_kstiff_observe: stiff_observe — its arguments, checks and results — with the stiffness k[C] of each point in place of
+        the call's one stiffness; every k[i] is finite and > 0."""
+        self._need_model(law_aware=True, stiff_aware=True)
+        law, observable = self._law_codes(law, observable)
+        dc = self._in(np.atleast_1d(dc) if not hasattr(dc, "data_ptr") else dc)
+        k = self._in(np.atleast_1d(k) if not hasattr(k, "data_ptr") else k)
+        C = int(dc.shape[0])
+        if tuple(k.shape) != (C,):
+            raise ValueError(f"k has shape {tuple(k.shape)}: one stiffness per point, ({C},)")
+        a, b, data = self._in(a), self._in(b), self._in(data)
+        if want_ssq and data is None:
+            raise ValueError("want_ssq needs data")
+        if data is not None and int(data.shape[0]) != self.nout:
+            raise ValueError(f"data has {int(data.shape[0])} entries, the model produces {self.nout}")
+        ssq = self._empty((C,)) if want_ssq else None
+        series = self._empty((self.nout, C)) if want_series else None
+        _abi.check(self.lib, self._kstiff_fn("rsf_kstiff_observe")(self._ctx, law, observable, C, self._ptr(dc), self._ptr(a), self._ptr(b),
+                                                                   self._ptr(k), self._ptr(data), self._ptr(ssq), self._ptr(series)))
+        return ssq, series
+
+    @staticmethod
+    def _kstiff_columns(pts):
+        """points (m, 2) of (Dc, k) or (m, 4) of (Dc, a, b, k) on the host → (dc, a, b, k), contiguous columns (a, b None at d = 2)"""
+        pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] not in (2, 4):
+            raise ValueError(f"the points have shape {pts.shape}: (m, 2) of (Dc, k) or (m, 4) of (Dc, a, b, k)")
+        col = lambda p: np.ascontiguousarray(pts[:, p])
+        return (col(0), col(1), col(2), col(3)) if pts.shape[1] == 4 else (col(0), None, None, col(1))
+
+    def kstiff_ssq_fn(self, law, data, observable="acc"):
+        """law_ssq_fn with the stiffness among the parameters: points (m, 2) of (Dc, k) or (m, 4) of (Dc, a, b, k) on the host → SSq
+        (m,) on the host, solved by kstiff_observe."""
+        obs = self._in(data)
+
+        def ssq_fn(pts):
+            dc, a, b, k = self._kstiff_columns(pts)
+            return _host(self.kstiff_observe(law, observable, dc, k, a, b, data=obs, want_ssq=True, want_series=False)[0])
+
+        return ssq_fn
+
+    def kstiff_dr_run(self, law, observable, q, l, data, lo, hi, chol, n_iter, counters, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iter0=1,
+                      trace=False):
+        """rsf_kstiff_dr_run, the fused hot path of include/rsf_kstiff.h: law_dr_run — its arguments, checks and results — on chains
+        q (n, 2) of (Dc, k) or (n, 4) of (Dc, a, b, k); lo[d - 1] > 0."""
+        self._need_model(law_aware=True, stiff_aware=True)
+        return self._law_dr_run(lambda: (self._kstiff_fn("rsf_kstiff_dr_run"), ()), law, observable, q, l, data, lo, hi, chol, n_iter, counters, gamma,
+                                stages, shape, seed, offset, iter0, trace)
+
+    def kstiff_dr_ssq(self, law, observable, y, mask, data, ssq=None):
+        """rsf_kstiff_dr_ssq: law_dr_ssq at points y (n, 2) or (n, 4) with the stiffness last → kstiff_observe's SSq bit for bit."""
+        self._need_model(law_aware=True, stiff_aware=True)
+        return self._law_dr_ssq(lambda: (self._kstiff_fn("rsf_kstiff_dr_ssq"), ()), law, observable, y, mask, data, ssq)
+
+    def kstiff_dr_propose(self, q, l, lo, hi, chol, stage, gamma=0.2, pending=None, seed=0, offset=0, iteration=1):
+        """rsf_kstiff_dr_propose: dr_propose — its arguments and results — at d = 2 or 4 (at d = 2 bit for bit); lo[d - 1] > 0."""
+        return self._dr_propose(self._kstiff_fn("rsf_kstiff_dr_propose"), q, l, lo, hi, chol, stage, gamma, pending, seed, offset, iteration)
+
+    def kstiff_dr_accept(self, q, l, lo, hi, stage, y, mask, ssq, counters, shape, gamma=0.2, l1=None, pending=None, seed=0, offset=0, iteration=1):
+        """rsf_kstiff_dr_accept: dr_accept — its arguments and results — at d = 2 or 4 (at d = 2 bit for bit); lo[d - 1] > 0."""
+        return self._dr_accept(self._kstiff_fn("rsf_kstiff_dr_accept"), q, l, lo, hi, stage, y, mask, ssq, counters, shape, gamma, l1, pending, seed,
+                               offset, iteration)
+
+    def kstiff_gn_factor(self, law, observable, q, data, rel_step=1e-4):
+        """law_gn_factor's rule at the point q = (Dc, k) or (Dc, a, b, k) → (L, cov, ssq), from ONE kstiff_observe call of 1 + d
+        lanes: cov = (SSq / nout) (J^T J)^-1 and L = chol((2.38^2 / d) cov).  Under a hold history the four-parameter matrix is
+        nearly singular (MCMC.sample_stiffness)."""
+        self._need_model(law_aware=True, stiff_aware=True)
+        law, observable = self._law_codes(law, observable)
+        q = np.asarray(_host(q), dtype=np.float64).reshape(-1)
+        d = q.size
+        if d not in (2, 4) or not np.isfinite(q).all() or not (q != 0.0).all() or not (math.isfinite(float(rel_step)) and float(rel_step) > 0.0):
+            raise ValueError(f"q has shape {q.shape}: a finite point (Dc, k) or (Dc, a, b, k) without a zero, and rel_step is finite and > 0")
+        obs = _host(data).reshape(-1)
+        if obs.size != self.nout:
+            raise ValueError(f"data has {obs.size} entries, the model produces {self.nout}")
+        self._kstiff_fn("rsf_kstiff_dr_run")  # the factor of this family's sampler: a library without it is refused here
+        h = float(rel_step) * q
+        pts = np.tile(q, (1 + d, 1))
+        pts[1:] += np.diag(h)
+        dc, a, b, k = self._kstiff_columns(pts)
+        return self._gn_factor("kstiff_gn_factor", q, h, obs, _host(self.kstiff_observe(law, observable, dc, k, a, b, want_series=True)[1]))
+
+    def kstiff_dr(self, law, observable, q0, data, lo, hi, chol, n_iter, gamma=0.2, stages=2, shape=None, seed=0, offset=0, iters_per_launch=16,
+                  keep=None, thin=1, adapt_launches=0, iter0=1, l0=None):
+        """Engine.law_dr — its arguments, groups, adaptation, continuation and DrResult, through the same driver — with the
+        stiffness among the parameters: q0 (n, 2) chains over (Dc, k) or (n, 4) over (Dc, a, b, k), lo[d - 1] > 0.  The launch is
+        kstiff_dr_run and the start's l is -shape log SSq from kstiff_ssq_fn."""
+        self._need_model(law_aware=True, stiff_aware=True)
+        codes = self._law_codes(law, observable)
+        if codes[1] not in _OBSERVABLE_NAMES:
+            raise ValueError(f"observable is one of {sorted(_OBSERVABLE_NAMES)} (RSF_OBS_*), not {codes[1]}")
+        if not (np.asarray(_host(lo), dtype=np.float64).reshape(-1)[-1] > 0.0):
+            raise ValueError("the box of the stiffness, the last coordinate, lies in k > 0")
+
+        def start_l(q, obs, lo, hi, shape):
+            s = np.asarray(self.kstiff_ssq_fn(codes[0], obs, _OBSERVABLE_NAMES[codes[1]])(_host(q)), dtype=np.float64).reshape(-1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return np.where(np.isfinite(s) & (s > 0), -shape * np.log(s), -np.inf)
+
+        run = lambda q, l, obs, lo, hi, L, k, counters, **kw: self.kstiff_dr_run(codes[0], codes[1], q, l, obs, lo, hi, L, k, counters, **kw)
+        return self._dr_drive(run, start_l, q0, data, lo, hi, chol, n_iter, gamma, stages, shape, seed, offset, iters_per_launch, keep, thin,
+                              adapt_launches, iter0, l0, ready=lambda: self._kstiff_fn("rsf_kstiff_dr_run"), dims=(2, 4))
 
     # -- Levenberg-Marquardt under either state law and any observable (include/rsf_law_fit.h) ---------------------------
     def _law_fit_fn(self, name):
